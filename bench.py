@@ -12,6 +12,13 @@ For N>1 every rank owns 500 further imagesets of the same camera/pattern (weak s
 sharding) and the reduced system is summed with one RCCL all-reduce per Gauss-Newton step.
 Synthetic observations are produced by the engine's own iterative projection of the ground-truth
 model (cba_project), rounded to fp32 with 0.03 px noise; inputs are resident in HBM before timing.
+
+A plain run sets up, warms up, times the --steps steps and prints the result line.  Everything else it can
+measure runs only with --full: the CPU baseline, the short side legs of BASELINE configs[2] and configs[3],
+the wall-clock to a converged calibration, the library DGEMM next to the roofline, and with more than one
+rank the second (distributed) reduced solve.  --dump-outputs DIR writes what the last timed step returned
+(the calibration state and the step's report, float64) as DIR/<name>.npy; the inputs are seeded, so two
+builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -37,24 +44,29 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", type=int, default=2, help="BASELINE.json config id (1-5)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short side legs of BASELINE configs[2] and configs[3] behind the headline leg (config 2, one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline, side legs of other configs, wall-clock to convergence, "
+                         "library DGEMM, and with more than one rank the second (distributed) reduced solve")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (calibration state + step report, float64) as DIR/<name>.npy")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short side legs of BASELINE configs[2] and configs[3] behind the headline leg (config 2, one GPU)")
     ap.add_argument("--elimination", type=int, default=0, help="cba_solver_options.elimination: 0 = automatic (default), 1 = pose-first (the reference's order), 2 = grid-first")
     ap.add_argument("--grid-single-tiles", action="store_true", help="cba_solver_options.grid_single_tile_tasks (grid-first order: one task per 64-column border tile)")
     ap.add_argument("--grid-strips", type=int, default=0, help="cba_solver_options.grid_strips (grid-first order; 0 = automatic)")
     ap.add_argument("--factor-tail-rows", type=int, default=0, help="cba_solver_options.factor_tail_rows (0 = the library default); schedule sweeps only")
     ap.add_argument("--imagesets", type=int, default=0, help="imagesets per GPU (0 = the config's count)")
     ap.add_argument("--fd-schedule", type=int, default=-1, help="cba_set_fd_schedule (0 pooled, 1 one task per lane); -1 = the library default; A/B runs only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--force-allreduce", action="store_true",
                     help="exercise the multi-GPU all-reduce path even with one rank (1-GPU validation of the N>1 code)")
     ap.add_argument("--cpu-sample-images", type=int, default=250)
-    ap.add_argument("--no-convergence", action="store_true", help="skip the wall-clock-to-convergence run")
+    ap.add_argument("--no-convergence", action="store_true", help="with --full: skip the wall-clock-to-convergence run")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="exercise only the self-launch path (spawn --gpus ranks, one gloo all-reduce on CPU, rank 0 prints a JSON "
                          "line); needs no GPU -- tests/test_bench_launcher.py")
     ap.add_argument("--distributed-solve", type=int, default=-1,
                     help="1 / 0: only the distributed / only the replicated factorisation of the reduced system (cba_config."
-                         "distributed_solve, DESIGN.md section 6); default with more than one rank: BOTH legs are timed in this one "
+                         "distributed_solve, DESIGN.md section 6); default with more than one rank and --full: BOTH legs are timed in this one "
                          "invocation -- replicated (one packed-upper all-reduce, the design north_star names) first, distributed "
                          "second -- the headline is always the replicated leg, the distributed one is carried in config.legs")
     ap.add_argument("--both-legs", action="store_true",
@@ -246,6 +258,24 @@ def _stage_b(t_B: float, atomics_B: float, config: int, world: int) -> dict:
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, st, rep) -> None:
+    """What a caller of the timed path receives from its last step: the calibration state the step left on the device (cba_get_state)
+    and the step's report, as float64 .npy files."""
+    arrays = {"rig_tr_global": st.rig_tr_global, "camera_tr_rig": st.camera_tr_rig, "points": st.points,
+              **{f"grid{c}": g for c, g in enumerate(st.grids)},
+              "step_report": np.array([rep.initial_cost, rep.final_cost, rep.final_lambda, rep.accepted, rep.lm_attempts,
+                                       rep.n_residuals_valid, rep.n_jacobians_dropped], dtype=np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def launcher_selftest(args) -> None:
     """What a rank does under --launcher-selftest: the rendezvous and one collective of the real path, on CPU."""
     import torch
@@ -338,9 +368,10 @@ def main():
             e.set_fd_schedule(args.fd_schedule)
         return e, keep
 
-    def run_leg(dist_solve: bool) -> dict:
+    def run_leg(dist_solve: bool, dump: bool = False) -> dict:
         """One complete measurement with its own engine: warm-up, barrier + synchronize, exactly --steps timed steps, barrier +
-        synchronize, MAX over ranks.  The engine stays open in the result (the caller closes it)."""
+        synchronize, MAX over ranks; with `dump`, rank 0 then writes the last step's outputs (--dump-outputs).  The engine stays
+        open in the result (the caller closes it)."""
         e, keep = open_engine(dist_solve)
         order = e.elimination_order()
         e.set_state(st0)
@@ -378,6 +409,8 @@ def main():
         if use_dist:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = float(el.item())
+        if dump and rank == 0:
+            dump_outputs(args.dump_outputs, e.get_state(st0), reports[-1])
         # every rank holds the same replicated state and takes the same LM decisions: the last report must agree bit for bit
         ranks_consistent = None
         if use_dist and reports:
@@ -407,17 +440,17 @@ def main():
         leg_kinds = [False]
     elif args.distributed_solve >= 0:
         leg_kinds = [bool(args.distributed_solve)]
-    elif world > 1 or args.both_legs:
+    elif (world > 1 and args.full) or args.both_legs:
         leg_kinds = [False, True]
     else:
         leg_kinds = [False]
     legs_info = []
-    best = run_leg(leg_kinds[0])
+    best = run_leg(leg_kinds[0], dump=args.dump_outputs is not None)
     legs_info.append(leg_summary(best))
     # the library's DGEMM on the same device, measured once outside the timed region: the in-situ gap of the hand-written GEMM
     # (roofline.frac_vs_library) is visible in the line itself
     lib_tflops = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             n_l = ((pb.dense_dof + 1 + 127) // 128) * 128
             K_l = 2048          # the K of a super-panel update (ldlt_factor), the launch shape that carries most of the flops
@@ -576,7 +609,7 @@ def main():
                 "launches": agg[3]["launches"], "avg_launch_ms": fd_s / fd_launches * 1e3, "flops_per_launch": fd_flops,
                 "model": "algorithmic flops = observations x (3 + K_cell) projections x 3.5 spline evaluations x 0.6 kflop "
                          "(DESIGN.md section 3); peak = MI355X fp64 vector peak"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(pb, st0, min(args.cpu_sample_images, pb.n_images), n_obs_total, n_img)
             except Exception as ex:  # the baseline is a reported extra, never a reason to lose the line
@@ -587,7 +620,7 @@ def main():
 
     # ---- BASELINE configs[2] and configs[3] (stereo rig, 1000 imagesets; non-central camera, 800 imagesets) as short side legs:
     # ---- outside the headline's timed region, their own engines, 2 warm-up + 5 timed steps each, same step definition
-    if rank == 0 and args.config == 2 and world == 1 and not use_dist and not args.no_other_configs:
+    if rank == 0 and args.full and args.config == 2 and world == 1 and not use_dist and not args.no_other_configs:
         others = {}
         for cfg_o in (3, 4):
             try:
@@ -685,14 +718,14 @@ def main():
                                           "replicated factorisation behind one packed-upper all-reduce per Gauss-Newton step, the design "
                                           "BASELINE.json's north_star names -- so the headline is comparable from run to run; the "
                                           "distributed factorisation is the side figure in config.legs[1]")
-    if best["engine"] is None:                           # the winner was the replicated leg: a fresh engine for the convergence run
-        best["engine"], best["keep"] = open_engine(best["dist_solve"])
-    e = best["engine"]
     # second BASELINE metric: wall-clock to converged calibration under the reference's stopping rule
     # (RunBundleAdjustment, APP/calibration.cc:298: cost >= last_cost - 1e-4, at most 100 iterations),
     # from the same perturbed start; reported next to the headline metric, outside the timed region.
     conv = None
-    if not args.no_convergence:
+    if args.full and not args.no_convergence:
+        if best["engine"] is None:                       # the winner was the replicated leg: a fresh engine for the convergence run
+            best["engine"], best["keep"] = open_engine(best["dist_solve"])
+        e = best["engine"]
         torch.cuda.synchronize()
         tc = time.perf_counter()
         final_cost, iters, reps = eng.run_bundle_adjustment(e, st0, 100, 1e-4)
@@ -705,7 +738,8 @@ def main():
                 "seconds_in_solves": sum(r.t_solve for r in reps), "seconds_in_jacobian_passes": sum(r.t_jac for r in reps),
                 "seconds_in_cost_passes": sum(r.t_cost for r in reps),
                 "initial_cost": reps[0].initial_cost}
-    e.close()
+    if best["engine"] is not None:
+        best["engine"].close()
     if watchdog["timer"] is not None:
         watchdog["timer"].cancel()
     if use_dist:

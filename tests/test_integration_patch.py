@@ -59,6 +59,11 @@ def test_patched_adapter_compiles_against_the_reference_s_own_types(tmp_path):
                     scratch / "applications" / "camera_calibration" / "src")
     shutil.copy(os.path.join(REFERENCE, "applications", "camera_calibration", "CMakeLists.txt"),
                 scratch / "applications" / "camera_calibration" / "CMakeLists.txt")
+    # the copy keeps the read-only modes of the reference tree: patch(1) needs to write next to the files it edits
+    for d, _, files in os.walk(scratch):
+        os.chmod(d, 0o755)
+        for f in files:
+            os.chmod(os.path.join(d, f), 0o644)
     r = subprocess.run(["patch", "-p1", "--batch", "-s", "-d", str(scratch), "-i", PATCH], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     app = scratch / "applications" / "camera_calibration" / "src"

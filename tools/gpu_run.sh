@@ -1,6 +1,6 @@
 #!/bin/bash
 # One parameterised GPU-box script:  tools/gpu_run.sh <what> [tag] [args]          (outputs -> gpurun_out/<tag>_*)
-#   suite     whole GPU test suite + smoke + default bench line
+#   suite     whole GPU test suite + smoke + the bench line with --full
 #   record    suite + bench lines of configs 2 / 3 / 4 (+ cfg 2 in the pose-first order) + kernel stats, step timelines, PMC traffic
 #             (FETCH / WRITE, separate passes, configs 2 and 4), MFMA counters
 #   profile   record without the test suite / smoke
@@ -57,11 +57,11 @@ print(d['config']['elimination'], 'ms/step', round(d['ms_per_step'],3), {k: roun
       timeout 2400 python -m pytest tests -q -m gpu --timeout 900 > $O/${TAG}_gputests.log 2>&1; echo "pytest rc=$?"; tail -4 $O/${TAG}_gputests.log
       timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
     fi
-    timeout 900 python bench.py --steps 20 --warmup 2 > $O/${TAG}_bench_cfg2.log 2>&1; tail -1 $O/${TAG}_bench_cfg2.log > $O/${TAG}_bench_cfg2.json; summary $O/${TAG}_bench_cfg2.json
+    timeout 900 python bench.py --full --steps 20 --warmup 2 > $O/${TAG}_bench_cfg2.log 2>&1; tail -1 $O/${TAG}_bench_cfg2.log > $O/${TAG}_bench_cfg2.json; summary $O/${TAG}_bench_cfg2.json
     [ "$WHAT" = suite ] && exit 0
-    timeout 400 python bench.py --steps 20 --warmup 2 --elimination 1 --no-cpu-baseline --no-other-configs > $O/${TAG}_bench_cfg2_posefirst.log 2>&1; tail -1 $O/${TAG}_bench_cfg2_posefirst.log > $O/${TAG}_bench_cfg2_posefirst.json; summary $O/${TAG}_bench_cfg2_posefirst.json
-    timeout 400 python bench.py --config 3 --steps 8 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_cfg3.log 2>&1; tail -1 $O/${TAG}_bench_cfg3.log > $O/${TAG}_bench_cfg3.json; summary $O/${TAG}_bench_cfg3.json
-    timeout 300 python bench.py --config 4 --steps 8 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_cfg4.log 2>&1; tail -1 $O/${TAG}_bench_cfg4.log > $O/${TAG}_bench_cfg4.json; summary $O/${TAG}_bench_cfg4.json
+    timeout 400 python bench.py --full --steps 20 --warmup 2 --elimination 1 --no-cpu-baseline --no-other-configs > $O/${TAG}_bench_cfg2_posefirst.log 2>&1; tail -1 $O/${TAG}_bench_cfg2_posefirst.log > $O/${TAG}_bench_cfg2_posefirst.json; summary $O/${TAG}_bench_cfg2_posefirst.json
+    timeout 400 python bench.py --full --config 3 --steps 8 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_cfg3.log 2>&1; tail -1 $O/${TAG}_bench_cfg3.log > $O/${TAG}_bench_cfg3.json; summary $O/${TAG}_bench_cfg3.json
+    timeout 300 python bench.py --full --config 4 --steps 8 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_cfg4.log 2>&1; tail -1 $O/${TAG}_bench_cfg4.log > $O/${TAG}_bench_cfg4.json; summary $O/${TAG}_bench_cfg4.json
     for c in 2 3 4; do
       trace /tmp/prof_c$c $O/${TAG}_bench_cfg${c}_kernel_stats.txt $O/${TAG}_step_timeline_cfg$c.txt --config $c --steps 5 --warmup 1 --no-cpu-baseline --no-convergence --no-other-configs
     done

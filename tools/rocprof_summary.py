@@ -2,7 +2,7 @@
 """Summarises a rocprofv3 rocpd sqlite database (kernel-trace) into a per-kernel table
 (count, total / average / min / max duration), like `rocprofv3 --stats` prints.
   rocprof_summary.py <db> [out] [bygrid]     bygrid: one row per (kernel, grid size) -- a command that runs several problem sizes
-                                             (bench.py's default line: the headline configuration and two side legs) launches the same
+                                             (bench.py --full: the headline configuration and two side legs) launches the same
                                              kernel with different grids; their durations must not be averaged together"""
 import sqlite3
 import sys

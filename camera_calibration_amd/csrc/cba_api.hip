@@ -47,7 +47,15 @@ int launch_gf_activity(const PassArgs& pa, const uint8_t* flags, const int* cell
                        int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
                        unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
                        int mask_words, hipStream_t s);
-int launch_gf_scatter(const double* xF, int Gf, int n_rp, int block_dof, int G, const int* f_of_grid, double* x, hipStream_t s);
+int launch_gf_touch(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
+                    int n_rp, int rig_dof, int n_tiles, int words, int slot0, unsigned long long* act, hipStream_t s);
+int launch_gf_close_masks(int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
+                          unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
+                          int mask_words, hipStream_t s);
+int launch_gf_scatter(const double* xF, int Gf, int n_rp, int block_dof, int G, const int* f_of_grid, int pose0, double* x, hipStream_t s);
+int launch_gf_shared(const GfShared& L, const int* col, double* Hdd, int ld, double* bd, double* buf, int unpack, hipStream_t s);
+int launch_gf_words_to_doubles(const unsigned long long* w, int n, double* out, hipStream_t s);
+int launch_gf_or_words(const double* blocks, int world, long long block_stride, int n, unsigned long long* w, hipStream_t s);
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static double now_s() {
@@ -205,6 +213,17 @@ struct cba_problem {
   int gf_tile_list_entries = 0;     // slots of the launch (eight interleaved per-XCD lists, padded)
   bool gf_tile_list_dirty = false;  // the host copy was rebuilt since the last upload
   size_t gf_tile_list_capacity = 0; // ints
+  // image sharding with the grid-first order: per Gauss-Newton step the shared blocks of H_dd / b_d are
+  // all-reduced as one buffer (GfShared), the pose rows D_i / b_i / B_i and the activity words of every rank are all-gathered, and the
+  // solve of F is replicated.  The border's pose order is rank-major: rank r's imagesets hold slots gf_offsets[r] ... in its own slot order.
+  bool gf_sharded = false;
+  GfShared gfs;
+  int* gfs_col = nullptr;                      // [gfs.G] band position -> engine dense column
+  int gf_rank = 0, gf_world = 1, gf_img0 = 0, gf_max_local = 0;
+  std::vector<int> gf_counts, gf_offsets;      // imagesets of every rank / first border slot of every rank
+  double* gDblk = nullptr; double* gbblk = nullptr; double* gB = nullptr;      // pose rows of ALL ranks (border order)
+  double* gsend = nullptr; double* grecv = nullptr; int64_t gblk = 0;          // all-gather staging: [words | D | b | B] of one rank, padded
+  int64_t P_cap = 0;                           // doubles of the reduce buffer P
 };
 
 namespace cba {
@@ -360,6 +379,73 @@ static int allreduce(cba_problem* p, double* dev, int64_t count) {
   return CBA_OK;
 }
 
+// Grid-first sharding: sum of the reduce buffer P over the ranks (cba_config.collective if set, else the all-reduce callback)
+static int gf_sum(cba_problem* p, int64_t count) {
+  CBA_HIP(hipStreamSynchronize(p->stream));
+  const int rc = p->cfg.collective ? p->cfg.collective(CBA_COLL_ALLREDUCE_SUM, p->P, p->P, count, p->cfg.collective_user)
+                                   : p->cfg.allreduce(p->P, count, p->cfg.allreduce_user);
+  if (rc != 0) { set_error("grid-first sharding: a collective callback failed"); return CBA_ERR_STATE; }
+  return CBA_OK;
+}
+// gsend (gblk doubles) of every rank into block r of grecv.  Without a collective callback: sums through P with zeros in the other
+// ranks' blocks, in chunks of P's size (exact: finite values and integer-valued mask halves)
+static int gf_allgather(cba_problem* p) {
+  const int64_t n = p->gblk, total = n * p->gf_world, own0 = n * p->gf_rank;
+  if (p->cfg.collective) {
+    CBA_HIP(hipStreamSynchronize(p->stream));
+    if (p->cfg.collective(CBA_COLL_ALLGATHER, p->gsend, p->grecv, n, p->cfg.collective_user) != 0) {
+      set_error("grid-first sharding: a collective callback failed"); return CBA_ERR_STATE;
+    }
+    return CBA_OK;
+  }
+  for (int64_t c0 = 0; c0 < total; c0 += p->P_cap) {
+    const int64_t len = std::min<int64_t>(p->P_cap, total - c0);
+    CBA_HIP(hipMemsetAsync(p->P, 0, sizeof(double) * (size_t)len, p->stream));
+    const int64_t a = std::max(c0, own0), b = std::min(c0 + len, own0 + n);
+    if (a < b) CBA_HIP(hipMemcpyAsync(p->P + (a - c0), p->gsend + (a - own0), sizeof(double) * (size_t)(b - a), hipMemcpyDeviceToDevice, p->stream));
+    CBA_TRY(gf_sum(p, len));
+    CBA_HIP(hipMemcpyAsync(p->grecv + c0, p->P, sizeof(double) * (size_t)len, hipMemcpyDeviceToDevice, p->stream));
+  }
+  return CBA_OK;
+}
+// The exchange of one Gauss-Newton step (after the accumulation; the activity words of this rank's observations are in gfd.act):
+//   1. shared blocks: H_dd / b_d packed (k_gf_shared), summed over the ranks, unpacked into H_dd / b_d -- launch_gf_form reads them as
+//      it reads a single process's accumulator;
+//   2. pose rows and activity words: gathered, the pose rows placed rank-major into gDblk / gbblk / gB, the words OR-ed;
+//   3. closure and masks of the union (the single-process masks up to the order of the pose columns), their host copy.
+static int gf_exchange(cba_problem* p) {
+  const Layout& L = p->L;
+  const GfPlan& g = p->gf;
+  GfDevice& d = p->gfd;
+  hipStream_t s = p->stream;
+  const int ld = p->n_pad;
+  CBA_TRY(launch_gf_shared(p->gfs, p->gfs_col, p->Hdd, ld, p->bd, p->P, 0, s));
+  CBA_TRY(gf_sum(p, p->gfs.doubles));
+  CBA_TRY(launch_gf_shared(p->gfs, p->gfs_col, p->Hdd, ld, p->bd, p->P, 1, s));
+  const int nw = d.n_act_tiles * d.act_words, M = p->gf_max_local, nloc = L.n_images;
+  const int64_t oD = 2 * (int64_t)nw, ob = oD + 36 * (int64_t)M, oB = ob + 6 * (int64_t)M;
+  CBA_TRY(launch_gf_words_to_doubles(d.act, nw, p->gsend, s));
+  if (nloc > 0) {
+    CBA_HIP(hipMemcpyAsync(p->gsend + oD, p->Dblk, sizeof(double) * 36 * (size_t)nloc, hipMemcpyDeviceToDevice, s));
+    CBA_HIP(hipMemcpyAsync(p->gsend + ob, p->bblk, sizeof(double) * 6 * (size_t)nloc, hipMemcpyDeviceToDevice, s));
+    CBA_HIP(hipMemcpyAsync(p->gsend + oB, p->B, sizeof(double) * 6 * (size_t)nloc * ld, hipMemcpyDeviceToDevice, s));
+  }
+  CBA_TRY(gf_allgather(p));
+  for (int r = 0; r < p->gf_world; ++r) {
+    const size_t cnt = (size_t)p->gf_counts[r], off = (size_t)p->gf_offsets[r];
+    if (!cnt) continue;
+    const double* src = p->grecv + (size_t)r * p->gblk;
+    CBA_HIP(hipMemcpyAsync(p->gDblk + 36 * off, src + oD, sizeof(double) * 36 * cnt, hipMemcpyDeviceToDevice, s));
+    CBA_HIP(hipMemcpyAsync(p->gbblk + 6 * off, src + ob, sizeof(double) * 6 * cnt, hipMemcpyDeviceToDevice, s));
+    CBA_HIP(hipMemcpyAsync(p->gB + 6 * off * ld, src + oB, sizeof(double) * 6 * cnt * ld, hipMemcpyDeviceToDevice, s));
+  }
+  CBA_TRY(launch_gf_or_words(p->grecv, p->gf_world, p->gblk, nw, d.act, s));
+  CBA_TRY(launch_gf_close_masks(d.n_act_tiles, d.act_words, g.nbg, g.nbf, d.gridrow, d.act, d.kmask, d.kmask_words, g.Gf / 128, d.rowmask,
+                                d.rowmask_dyn, d.mask_words, s));
+  CBA_HIP(hipMemcpyAsync(p->gf_kmask_host, d.kmask, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words, hipMemcpyDeviceToHost, s));
+  return CBA_OK;
+}
+
 // residual pass on state `which`; fills cost vector `cost_vec` and reduces to out8 (host)
 static int residual_pass(cba_problem* p, int which, double* cost_vec, const int* guard = nullptr) {
   CBA_TRY(launch_compose_poses(p->st[which], p->L.n_images, p->L.n_cameras, p->itg, p->stream));
@@ -448,10 +534,15 @@ static int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
       // the side stream behind the per-cell accumulation, underneath the strips kernel of the main stream (waited for at the end of the pass)
       const GfPlan& g = p->gf;
       GfDevice& d = p->gfd;
-      CBA_TRY(launch_gf_activity(a, p->flags, p->cells, p->img_start, L.n_images, p->gf_f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
-                                 d.n_act_tiles, d.act_words, g.nbg, g.nbf, d.gridrow, d.act, d.kmask, d.kmask_words, g.Gf / 128, d.rowmask, d.rowmask_dyn,
-                                 d.mask_words, aux));
-      CBA_HIP(hipMemcpyAsync(p->gf_kmask_host, d.kmask, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words, hipMemcpyDeviceToHost, aux));
+      if (p->gf_sharded) {        // this rank's rows only (pose columns at their global tiles): the union and the masks follow the exchange
+        CBA_TRY(launch_gf_touch(a, p->flags, p->cells, p->img_start, L.n_images, p->gf_f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
+                                d.n_act_tiles, d.act_words, p->gf_img0, d.act, aux));
+      } else {
+        CBA_TRY(launch_gf_activity(a, p->flags, p->cells, p->img_start, L.n_images, p->gf_f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
+                                   d.n_act_tiles, d.act_words, g.nbg, g.nbf, d.gridrow, d.act, d.kmask, d.kmask_words, g.Gf / 128, d.rowmask, d.rowmask_dyn,
+                                   d.mask_words, aux));
+        CBA_HIP(hipMemcpyAsync(p->gf_kmask_host, d.kmask, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words, hipMemcpyDeviceToHost, aux));
+      }
     }
     CBA_HIP(hipEventRecord(p->ev_aux1, aux));
   }
@@ -471,6 +562,7 @@ static int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   }
   CBA_TRY(timer_end(p, 2, 0, 0, 1));
   if (t_acc) *t_acc += now_s() - t0;
+  if (p->gf_sharded) CBA_TRY(gf_exchange(p));
   // The block-sparsity mask of B is only read by the Schur product: it is built on the side stream, underneath the cost reduction,
   // the block inverses and W = D^-1 B of the solve that follows (solve_system waits for that stream in front of the product).
   if (!p->gridfirst) {
@@ -514,7 +606,8 @@ static void gf_build_tile_list(cba_problem* p, int nt, int n_slabs, Weight weigh
   int w_max = 0;
   for (int tm = 0; tm < nt; ++tm)
     for (int tn = tm; tn < nt; ++tn) { const int w = weight(tm, tn); all.push_back(Tile{w, tm, tn, 0, 0}); w_max = std::max(w_max, w); }
-  if (!p->cfg.deterministic) {
+  // (image sharding: not either -- every rank must factor F bit for bit alike, or the replicas' LM decisions and collectives part)
+  if (!p->cfg.deterministic && !p->gf_sharded) {
     // unit: a third of the heaviest tile (measured at BASELINE configs[1] / [2] / [3], launch ms with units of 1/2, 1/3, 1/4, 1/6:
     // 3.31 / 3.31 / 3.26 / 3.26, 12.17 / 12.03 / 12.09 / 12.18, 5.40 / 5.27 / 5.37 / 5.41; whole tiles: 3.50 / 12.34 / 5.53)
     const int unit = std::max(8, w_max / 3);
@@ -593,8 +686,10 @@ static int solve_enqueue_gridfirst(cba_problem* p, double lambda) {
   CBA_HIP(hipMemsetAsync(p->ldlt.status, 0, sizeof(int), p->stream));
   CBA_TRY(ldlt_clear_ctrl(p->ldlt, p->stream));
   const GfDevice& d = p->gfd;
-  CBA_TRY(launch_gf_form(p->F, ld, g.Gf, g.n_rp, g.n_border, p->gf_grid_of_f, p->Hdd, p->n_pad, p->bd, p->B, p->Dblk, p->bblk, lambda,
-                         p->gf_tiles, p->n_gf_tiles, d.act, d.act_words, p->stream));
+  // (image sharding: H_dd / b_d hold the sums over the ranks, the pose rows of all ranks are in gDblk / gbblk / gB -- gf_exchange)
+  const bool sh = p->gf_sharded;
+  CBA_TRY(launch_gf_form(p->F, ld, g.Gf, g.n_rp, g.n_border, p->gf_grid_of_f, p->Hdd, p->n_pad, p->bd, sh ? p->gB : p->B, sh ? p->gDblk : p->Dblk,
+                         sh ? p->gbblk : p->bblk, lambda, p->gf_tiles, p->n_gf_tiles, d.act, d.act_words, p->stream));
   GemmStats gs;
   CBA_TRY(timer_begin(p, 1));
   const int* tile_list = nullptr;
@@ -609,7 +704,7 @@ static int solve_enqueue_gridfirst(cba_problem* p, double lambda) {
                                 tile_list ? p->gf_tile_list_entries : 0));
   CBA_TRY(timer_end(p, 1, gs.flops, 0, gs.launches));
   CBA_TRY(ldlt_back_solve(p->F, g.n_fact, ld, ld - 1, p->ldlt, p->xF, p->stream, d.rowmask_dyn, d.mask_words));
-  CBA_TRY(launch_gf_scatter(p->xF, g.Gf, g.n_rp, L.block_dof, g.G, p->gf_f_of_grid, p->x, p->stream));
+  CBA_TRY(launch_gf_scatter(p->xF, g.Gf, g.n_rp, L.block_dof, g.G, p->gf_f_of_grid, sh ? 6 * p->gf_img0 : 0, p->x, p->stream));
   if (!p->pin_status) CBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->pin_status), 4 * sizeof(double)));
   hipLaunchKernelGGL(k_solve_status, dim3(1), dim3(64), 0, p->stream, p->status, p->ldlt.status, p->x, p->pin_status, p->status + 1);
   CBA_HIP(hipGetLastError());
@@ -784,6 +879,11 @@ int64_t cba_reduce_buffer_doubles(const cba_config* config) {
   Layout L; make_layout(*config, L);
   int n_pad, n_fact; padded_dims(L.dense_dof, &n_pad, &n_fact);
   if (config->distributed_solve) return (int64_t)ldlt_dist_buffer_doubles(n_pad, config->world_size);
+  if (config->solver.elimination == 2) {      // grid-first order: the shared blocks, all-reduced as one buffer (gf_exchange)
+    GfShared s;
+    gf_shared_layout(config->cameras, config->n_cameras, config->n_points, &s);
+    return s.doubles;
+  }
   return packed_upper_doubles(n_pad);
 }
 
@@ -844,12 +944,19 @@ int cba_create(const cba_config* config, cba_problem** out) {
   for (int c = 0; c < L.n_cameras; ++c) CBA_TRY(dev_alloc(&p->tangents[c], 6 * (size_t)p->cams[c].grid_w * p->cams[c].grid_h));
   {
     // elimination order (cba_solver_options.elimination)
-    const bool eligible = !L.eliminate_points && !L.localize_only && !config->allreduce && L.n_images > 0;
+    // image sharding: the plan covers the imagesets of all ranks (the border is [rig | points | poses of every rank])
+    const bool sharded = config->allreduce != nullptr;
+    const int n_glob = (sharded && config->n_images_global > 0) ? config->n_images_global : L.n_images;
+    const bool eligible = !L.eliminate_points && !L.localize_only && n_glob > 0 && (sharded || L.n_images > 0);
     const int want = config->solver.elimination;
-    if (want == 2 && !eligible) { set_error("cba_create: the grid-first elimination order needs eliminate_points = 0, localize_only = 0 and one rank"); return CBA_ERR_UNSUPPORTED; }
+    if (want == 2 && !eligible) { set_error("cba_create: the grid-first elimination order needs eliminate_points = 0 and localize_only = 0"); return CBA_ERR_UNSUPPORTED; }
+    if (want == 2 && sharded && config->distributed_solve) { set_error("cba_create: the grid-first elimination order has no distributed factorisation (distributed_solve = 1)"); return CBA_ERR_UNSUPPORTED; }
     if (want < 0 || want > 2 || config->solver.grid_strips < 0) { set_error("cba_create: bad solver options"); return CBA_ERR_ARG; }
+    if (want == 2 && sharded && (config->world_size < 1 || config->rank < 0 || config->rank >= config->world_size)) {
+      set_error("cba_create: grid-first sharding needs 0 <= rank < world_size"); return CBA_ERR_ARG;
+    }
     bool use = want == 2;
-    if (want == 0 && eligible) {
+    if (want == 0 && eligible && !sharded) {
       double pf = 0, gfl = 0;
       gf_flop_model(p->cams.data(), L.n_cameras, L.n_images, L.n_points, &pf, &gfl);
       int G = 0;
@@ -857,8 +964,23 @@ int cba_create(const cba_config* config, cba_problem** out) {
       use = G >= 2048 && gfl < 0.85 * pf;
     }
     if (use) {
-      if (gf_build_plan(p->cams.data(), L.n_cameras, L.n_images, L.n_points, config->solver.grid_strips, config->solver.grid_single_tile_tasks, &p->gf) != CBA_OK) { set_error("cba_create: grid-first plan failed"); return CBA_ERR_ARG; }
+      if (gf_build_plan(p->cams.data(), L.n_cameras, n_glob, L.n_points, config->solver.grid_strips, config->solver.grid_single_tile_tasks, &p->gf) != CBA_OK) { set_error("cba_create: grid-first plan failed"); return CBA_ERR_ARG; }
       p->gridfirst = true;
+      if (sharded) {
+        // limits of the launches, checked here rather than at the first pass: activity words of k_gf_touch (1024 grid block
+        // rows), its LDS bit sets, the control words of the block-sparse launch, 32-bit offsets inside the sections of k_gf_shared
+        const GfPlan& g = p->gf;
+        const int64_t words = (g.nbg + 63) / 64, touch_lds = 8 * words * ((g.n_pad - g.Gf) / 128);
+        gf_shared_layout(p->cams.data(), L.n_cameras, L.n_points, &p->gfs);
+        int64_t band_max = 0;
+        for (int c = 0; c < L.n_cameras; ++c) band_max = std::max(band_max, p->gfs.band_off[c + 1] - p->gfs.band_off[c]);
+        if (g.nbg > 1024) { set_error("cba_create: grid-first sharding: more than 1024 grid block rows"); return CBA_ERR_UNSUPPORTED; }
+        if (touch_lds > 65536) { set_error("cba_create: grid-first sharding: the activity bit sets of the border need more than 64 KB of LDS"); return CBA_ERR_UNSUPPORTED; }
+        if ((int)g.chains.size() > ldlt_gridfirst_max_chains()) { set_error("cba_create: grid-first sharding: more pivot chains than the block-sparse launch has control words for"); return CBA_ERR_UNSUPPORTED; }
+        if (band_max >= INT32_MAX || (int64_t)p->gfs.n_rp * p->gfs.G >= INT32_MAX) { set_error("cba_create: grid-first sharding: shared blocks too large"); return CBA_ERR_UNSUPPORTED; }
+        p->gf_sharded = true;
+        p->gf_rank = config->rank; p->gf_world = config->world_size;
+      }
     }
   }
   CBA_TRY(build_grid_order(p));
@@ -985,8 +1107,8 @@ int cba_create(const cba_config* config, cba_problem** out) {
     CBA_TRY(dev_alloc(&p->S, (size_t)p->n_pad * p->n_pad));
   }
   if (config->allreduce) {
-    // the reduced system crosses ranks as its upper 128-row blocks only (half the all-reduce volume)
-    int64_t need = packed_upper_doubles(p->n_pad);
+    // the reduced system crosses ranks as its upper 128-row blocks only (half the all-reduce volume); grid-first: the shared blocks
+    int64_t need = p->gf_sharded ? p->gfs.doubles : packed_upper_doubles(p->n_pad);
     if (config->distributed_solve) {       // staging of the reduce-scatter / all-gathers (send: P, receive: P2)
       need = (int64_t)ldlt_dist_buffer_doubles(p->n_pad, config->world_size);
       p->dist_buf_doubles = (size_t)need;
@@ -998,6 +1120,41 @@ int cba_create(const cba_config* config, cba_problem** out) {
     } else {
       CBA_TRY(dev_alloc(&p->P, (size_t)need));
     }
+    p->P_cap = config->reduce_buffer ? config->reduce_buffer_doubles : need;
+  }
+  if (p->gf_sharded) {
+    // imagesets of every rank (the one collective of cba_create; every rank computes the same plan, so all of them get here)
+    const int W = p->gf_world;
+    if (p->P_cap < W) { set_error("reduce_buffer too small"); return CBA_ERR_ARG; }
+    std::vector<double> cnt(W, 0.0);
+    cnt[p->gf_rank] = (double)L.n_images;
+    CBA_HIP(hipMemcpy(p->P, cnt.data(), sizeof(double) * W, hipMemcpyHostToDevice));
+    CBA_TRY(gf_sum(p, W));
+    CBA_HIP(hipMemcpy(cnt.data(), p->P, sizeof(double) * W, hipMemcpyDeviceToHost));
+    p->gf_counts.assign(W, 0); p->gf_offsets.assign(W, 0);
+    int total = 0;
+    for (int r = 0; r < W; ++r) {
+      p->gf_counts[r] = (int)cnt[r]; p->gf_offsets[r] = total; total += p->gf_counts[r];
+      p->gf_max_local = std::max(p->gf_max_local, p->gf_counts[r]);
+    }
+    if (total != p->gf.n_images || p->gf_counts[p->gf_rank] != L.n_images) {
+      set_error("cba_create: grid-first sharding: the imagesets of the ranks do not add up to n_images_global"); return CBA_ERR_ARG;
+    }
+    p->gf_img0 = p->gf_offsets[p->gf_rank];
+    const size_t Ng = (size_t)total, ld = (size_t)p->n_pad;
+    CBA_TRY(dev_alloc(&p->gDblk, 36 * Ng));
+    CBA_TRY(dev_alloc(&p->gbblk, 6 * Ng));
+    CBA_TRY(dev_alloc(&p->gB, 6 * Ng * ld));
+    const GfDevice& d = p->gfd;
+    p->gblk = 2 * (int64_t)d.n_act_tiles * d.act_words + (int64_t)p->gf_max_local * (42 + 6 * (int64_t)ld);
+    CBA_TRY(dev_alloc(&p->gsend, (size_t)p->gblk));
+    CBA_HIP(hipMemset(p->gsend, 0, sizeof(double) * (size_t)p->gblk));
+    CBA_TRY(dev_alloc(&p->grecv, (size_t)p->gblk * W));
+    // band position -> engine dense column (the engine's grid order is the plan's elimination order, build_grid_order)
+    std::vector<int> col(p->gfs.ref_col.size());
+    for (size_t k = 0; k < col.size(); ++k) col[k] = p->dense_perm_host[p->gfs.ref_col[k]];
+    CBA_TRY(dev_alloc(&p->gfs_col, col.size()));
+    CBA_HIP(hipMemcpy(p->gfs_col, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
   }
   if (p->S) CBA_HIP(hipMemset(p->S, 0, sizeof(double) * (size_t)p->n_pad * p->n_pad));
   if (p->W) CBA_HIP(hipMemset(p->W, 0, sizeof(double) * (size_t)p->Kpad * p->n_pad));
@@ -1042,6 +1199,7 @@ void cba_destroy(cba_problem* p) {
   F(p->P2);
   F(p->x); F(p->scal); F(p->status); F(p->gemv_ws); F(p->kmask);
   F(p->F); F(p->Xb); F(p->xF); F(p->gf_tiles); F(p->gf_grid_of_f); F(p->gf_f_of_grid);
+  F(p->gfs_col); F(p->gDblk); F(p->gbblk); F(p->gB); F(p->gsend); F(p->grecv);
   F(p->gfd.tasks); F(p->gfd.ivals); F(p->gfd.chains); F(p->gfd.rowmask);
   F(p->gfd.act); F(p->gfd.gridrow); F(p->gfd.kmask); F(p->gfd.rowmask_dyn);
   if (p->gf_kmask_host) hipHostFree(p->gf_kmask_host);
@@ -1196,7 +1354,7 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
           }
       }
       std::vector<int> slot_of;
-      gf_order_imagesets(g, touched, L.n_images, g.n_rp, &slot_of);
+      gf_order_imagesets(g, touched, L.n_images, g.n_rp + 6 * p->gf_img0, &slot_of);      // (sharding: this rank's slots of the border)
       for (int i = 0; i < L.n_images; ++i) order[slot_of[i]] = i;
       // First tile order of the border update, predicted from the same rows (the first solve would otherwise run its tiles in
       // row-major order: 4.7 instead of 3.5 ms at BASELINE configs[1]): per 128-column tile of the border the union of its imagesets'
@@ -1207,6 +1365,7 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
         auto all_rows = [&](int t) { for (int w = 0; w < W; ++w) tact[(size_t)t * W + w] = ~0ull; };
         for (int t = 0; t < nt && 128 * t < g.n_rp; ++t) all_rows(t);
         all_rows(nt - 1);
+        if (p->gf_sharded) for (int t = 0; t < nt; ++t) all_rows(t);        // (the other ranks' rows are not known here: dense)
         for (int i = 0; i < L.n_images; ++i)
           for (int t : {(g.n_rp + 6 * slot_of[i]) >> 7, (g.n_rp + 6 * slot_of[i] + 5) >> 7})
             for (int w = 0; w < W; ++w) tact[(size_t)t * W + w] |= touched[(size_t)i * W + w];
@@ -1438,8 +1597,12 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
   if (init_lambda >= 0) {
     lambda = init_lambda;
   } else {  // lm_optimizer.h:766-781
-    CBA_TRY(launch_diag_sum(p->Dblk, L.block_size, L.n_blocks, p->Hdd, p->n_pad, L.dense_dof, p->scal, p->stream));
-    CBA_TRY(allreduce(p, p->scal, 1));
+    if (p->gf_sharded) {       // the exchange of the pass has summed H_dd and gathered every pose block: the whole diagonal is here
+      CBA_TRY(launch_diag_sum(p->gDblk, L.block_size, p->gf.n_images, p->Hdd, p->n_pad, L.dense_dof, p->scal, p->stream));
+    } else {
+      CBA_TRY(launch_diag_sum(p->Dblk, L.block_size, L.n_blocks, p->Hdd, p->n_pad, L.dense_dof, p->scal, p->stream));
+      CBA_TRY(allreduce(p, p->scal, 1));
+    }
     double sum;
     CBA_TRY(read_scalars(p, p->scal, &sum, 1));
     const int n_img_global = (multi && p->cfg.n_images_global > 0) ? p->cfg.n_images_global : L.n_images;
@@ -1833,6 +1996,13 @@ int64_t cba_gridfirst_plan_query(const cba_camera* cameras, int32_t n_cameras, i
     case 4: return give(pl.ivals.data(), pl.ivals.size() * sizeof(GfIval));
     case 5: return give(pl.rowmask.data(), pl.rowmask.size() * sizeof(uint64_t));
     case 6: { const double f[3] = {pl.flops_grid, pl.flops_update, pl.flops_border}; return give(f, sizeof(f)); }
+    case 7: case 8: {
+      GfShared sl;
+      gf_shared_layout(cameras, n_cameras, n_points, &sl);
+      if (what == 8) return give(sl.ref_col.data(), sl.ref_col.size() * sizeof(int));
+      const int64_t h[6] = {sl.doubles, sl.off_rp_grid, sl.off_rig, sl.off_pp, sl.off_b, sl.G};
+      return give(h, sizeof(h));
+    }
     default:
       if (what >= 16 && what < 16 + n_cameras) return give(pl.gperm[what - 16].data(), pl.gperm[what - 16].size() * sizeof(int));
       set_error("cba_gridfirst_plan_query: unknown item");

@@ -203,6 +203,8 @@ struct GfDevice {
 // ranges [s0, s1) cover all slabs (added atomically), tm = -1 = an empty slot
 int ldlt_factor_gridfirst(double* F, int n_fact, int ld, const GfDevice& g, double* Xb, int ldxb, LdltWorkspace& w, hipStream_t s,
                           GemmStats* st, const unsigned long long* kmask, int kmask_words, const int* tile_list, int tile_list_entries);
+// pivot chains the block-sparse launch has control words for
+int ldlt_gridfirst_max_chains();
 // Rows that the final dataflow launch factors (w.tail_rows clamped to the workspace's flag storage)
 int ldlt_tail_rows(const LdltWorkspace& w, int world = 1);
 int ldlt_clear_ctrl(LdltWorkspace& w, hipStream_t s);

@@ -78,6 +78,24 @@ int gf_build_plan(const cba_camera* cams, int n_cameras, int n_images, int n_poi
 // first column (tiles are counted in border columns).
 void gf_order_imagesets(const GfPlan& plan, const std::vector<uint64_t>& touched_rows, int n_images, int first_col, std::vector<int>* slot_of_image);
 
+// Image sharding with the grid-first order: the ONE buffer of shared blocks that is all-reduced per Gauss-Newton
+// step -- [grid x grid, banded | rig / point rows x grid columns | rig rows x (rig, point) columns | 3 x 3 point blocks (upper) | J^T r of
+// the dense part].  Band: per camera, the unknowns numbered along the SHORT grid dimension inside a line of the long one (position k =
+// ppg (t + ns l) + d), each with its hb + 1 right neighbours in that numbering, hb = (3 ns + 3) ppg + ppg - 1: an observation touches
+// a 4 x 4 window of control points, so no grid x grid coupling lies outside.  Entries past the end of a camera's numbering are zero.
+// Sizes equal distributed.GridFirstSharedLayout (tests/test_gridfirst_sharded_layout.py).  The plan's elimination order is NOT used
+// as the band's numbering: its separators sit at the end, far from their neighbours.
+struct GfShared {
+  int n_cameras = 0;
+  int rig = 0, n_rp = 0, G = 0, dense_dof = 0, n_points = 0;
+  int cam_pos[17] = {};            // first band position of every camera (+ end = G)
+  int width[16] = {};              // hb + 1 per camera
+  int64_t band_off[17] = {};       // first double of every camera's band (+ end)
+  int64_t off_rp_grid = 0, off_rig = 0, off_pp = 0, off_b = 0, doubles = 0;
+  std::vector<int> ref_col;        // [G] band position -> dense column in the REFERENCE order (rig | points | grids row-major)
+};
+void gf_shared_layout(const cba_camera* cams, int n_cameras, int n_points, GfShared* out);
+
 // flop model of the two elimination orders (dense border columns): used by the automatic choice
 void gf_flop_model(const cba_camera* cams, int n_cameras, int n_images, int n_points, double* pose_first, double* grid_first);
 

@@ -49,6 +49,41 @@ void gf_flop_model(const cba_camera* cams, int C, int N, int P, double* pose_fir
   if (grid_first) *grid_first = band + strip + A * A * G + A * A * A / 3.0;
 }
 
+void gf_shared_layout(const cba_camera* cams, int C, int P, GfShared* out) {
+  GfShared& s = *out;
+  s = GfShared();
+  s.n_cameras = C; s.n_points = P;
+  s.rig = C > 1 ? 6 * C : 0;
+  s.n_rp = s.rig + 3 * P;
+  int off = s.n_rp, pos = 0;
+  int64_t n = 0;
+  for (int c = 0; c < C; ++c) {
+    const int ppg = cams[c].model_type == CBA_CENTRAL_GENERIC ? 2 : 5;
+    const int gw = cams[c].grid_w, gh = cams[c].grid_h;
+    const bool long_is_x = gw >= gh;
+    const int nl = long_is_x ? gw : gh, ns = long_is_x ? gh : gw;
+    s.cam_pos[c] = pos;
+    s.width[c] = (3 * ns + 3) * ppg + ppg;
+    s.band_off[c] = n;
+    for (int l = 0; l < nl; ++l)
+      for (int t = 0; t < ns; ++t) {
+        const int gx = long_is_x ? l : t, gy = long_is_x ? t : l;
+        for (int d = 0; d < ppg; ++d) s.ref_col.push_back(off + ppg * (gx + gy * gw) + d);
+      }
+    const int cnt = ppg * gw * gh;
+    pos += cnt;
+    n += (int64_t)cnt * s.width[c];
+    off += cnt;
+  }
+  s.cam_pos[C] = pos; s.band_off[C] = n;
+  s.G = pos; s.dense_dof = off;
+  s.off_rp_grid = n;  n += (int64_t)s.n_rp * s.G;
+  s.off_rig = n;      n += (int64_t)s.rig * s.n_rp;
+  s.off_pp = n;       n += 6 * (int64_t)P;
+  s.off_b = n;        n += s.dense_dof;
+  s.doubles = n;
+}
+
 void gf_order_imagesets(const GfPlan& pl, const std::vector<uint64_t>& touched, int N, int first_col, std::vector<int>* slot_of_image) {
   const int W = pl.grid_words, nbg = pl.nbg;
   slot_of_image->assign(N, 0);

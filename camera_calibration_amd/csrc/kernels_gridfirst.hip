@@ -9,7 +9,10 @@
 // source is stored "the other way round" -- grid rows against rig / point / pose columns, rig / point rows against pose columns:
 // H_dd and B are row-major with the EARLIER engine unknown as the row -- are transposed through LDS, so that both the reads and the
 // writes of a tile move whole 512-byte rows.
+#include <algorithm>
+
 #include "cba_internal.h"
+#include "gridfirst_plan.h"
 
 namespace cba {
 
@@ -110,6 +113,7 @@ struct GfTouchArgs {
   const int* obs_point; const int* obs_image; const int* obs_camera; const uint8_t* flags; const int* cells; const int64_t* img_start;
   const int* pose_slot; const CamDev* cams; const int* f_of_grid;
   int n_rp, rig_dof, n_tiles, words;
+  int slot0;                       // border slot of this rank's first imageset (image sharding: rank-major pose order; else 0)
   unsigned long long* act;
 };
 __global__ void __launch_bounds__(256) k_gf_touch(GfTouchArgs a) {
@@ -119,7 +123,7 @@ __global__ void __launch_bounds__(256) k_gf_touch(GfTouchArgs a) {
   for (int i = tid; i < nw; i += 256) sbits[i] = 0ull;
   __syncthreads();
   const int64_t o0 = a.img_start[img], o1 = a.img_start[img + 1];
-  const int slot = a.pose_slot ? a.pose_slot[img] : img;
+  const int slot = a.slot0 + (a.pose_slot ? a.pose_slot[img] : img);
   for (int64_t o = o0 + tid; o < o1; o += 256) {
     if (!(a.flags[o] & 2)) continue;                      // no Jacobian: nothing accumulated
     const int cam = a.obs_camera[o];
@@ -217,41 +221,158 @@ __global__ void k_gf_masks(const unsigned long long* __restrict__ act, int n_til
     rowmask[j] = v;
   }
 }
-int launch_gf_activity(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
-                       int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
-                       unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
-                       int mask_words, hipStream_t s) {
+// the two halves of launch_gf_activity: the touched rows of this process's observations (image sharding: OR-ed over the ranks in
+// between, cba_api.hip gf_exchange), then their closure and the masks derived from it
+int launch_gf_touch(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
+                    int n_rp, int rig_dof, int n_tiles, int words, int slot0, unsigned long long* act, hipStream_t s) {
   if (words > 16) { set_error("grid-first: more than 1024 grid block rows"); return CBA_ERR_UNSUPPORTED; }
   CBA_HIP(hipMemsetAsync(act, 0, sizeof(unsigned long long) * (size_t)n_tiles * words, s));
   if (pa.n_obs > 0 && n_images > 0) {
     GfTouchArgs a{};
     a.obs_point = pa.obs_point; a.obs_image = pa.obs_image; a.obs_camera = pa.obs_camera; a.flags = flags; a.cells = cells; a.img_start = img_start;
     a.pose_slot = pa.pose_slot; a.cams = pa.cams; a.f_of_grid = f_of_grid;
-    a.n_rp = n_rp; a.rig_dof = rig_dof; a.n_tiles = n_tiles; a.words = words; a.act = act;
+    a.n_rp = n_rp; a.rig_dof = rig_dof; a.n_tiles = n_tiles; a.words = words; a.slot0 = slot0; a.act = act;
     hipLaunchKernelGGL(k_gf_touch, dim3((unsigned)n_images), dim3(256), sizeof(unsigned long long) * (size_t)n_tiles * words, s, a);
   }
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+int launch_gf_close_masks(int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
+                          unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
+                          int mask_words, hipStream_t s) {
   hipLaunchKernelGGL(k_gf_close, dim3((n_tiles + 63) / 64), dim3(64), 0, s, act, n_tiles, words, nbg, gridrow);
   const int total = n_tiles * kwords + nbf * mask_words;
   hipLaunchKernelGGL(k_gf_masks, dim3((total + 255) / 256), dim3(256), 0, s, act, n_tiles, words, nbg, nbf, tile0, kmask, kwords, rowmask_static, rowmask, mask_words);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
+int launch_gf_activity(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
+                       int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
+                       unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
+                       int mask_words, hipStream_t s) {
+  int rc = launch_gf_touch(pa, flags, cells, img_start, n_images, f_of_grid, n_rp, rig_dof, n_tiles, words, 0, act, s);
+  if (rc != CBA_OK) return rc;
+  return launch_gf_close_masks(n_tiles, words, nbg, nbf, gridrow, act, kmask, kwords, tile0, rowmask_static, rowmask, mask_words, s);
+}
 
-// x (engine layout: 6 N pose entries in slot order, then the dense columns [rig | points | grid]) from xF (rows of F)
+// x (engine layout: 6 N pose entries in slot order, then the dense columns [rig | points | grid]) from xF (rows of F); pose0: first
+// pose row of this process's imagesets in the border (image sharding: 6 x the imagesets of the ranks before it; else 0)
 __global__ void __launch_bounds__(256) k_gf_scatter(const double* __restrict__ xF, int Gf, int n_rp, int block_dof, int G,
-                                                    const int* __restrict__ f_of_grid, double* __restrict__ x) {
+                                                    const int* __restrict__ f_of_grid, int pose0, double* __restrict__ x) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int total = block_dof + n_rp + G;
   if (i >= total) return;
   int f;
-  if (i < block_dof) f = Gf + n_rp + i;
+  if (i < block_dof) f = Gf + n_rp + pose0 + i;
   else if (i < block_dof + n_rp) f = Gf + (i - block_dof);
   else f = f_of_grid[i - block_dof - n_rp];
   x[i] = xF[f];
 }
-int launch_gf_scatter(const double* xF, int Gf, int n_rp, int block_dof, int G, const int* f_of_grid, double* x, hipStream_t s) {
+int launch_gf_scatter(const double* xF, int Gf, int n_rp, int block_dof, int G, const int* f_of_grid, int pose0, double* x, hipStream_t s) {
   const int total = block_dof + n_rp + G;
-  hipLaunchKernelGGL(k_gf_scatter, dim3((total + 255) / 256), dim3(256), 0, s, xF, Gf, n_rp, block_dof, G, f_of_grid, x);
+  hipLaunchKernelGGL(k_gf_scatter, dim3((total + 255) / 256), dim3(256), 0, s, xF, Gf, n_rp, block_dof, G, f_of_grid, pose0, x);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+
+// ---- image sharding: the shared blocks in and out of the one all-reduced buffer ----
+// Buffer layout: gridfirst_plan.h, GfShared.  One lane per double of the buffer, consecutive lanes on consecutive doubles: the
+// buffer side moves whole 512-byte rows; on the H_dd side a band row is (inside a strip of the engine's grid order) a run of
+// neighbouring columns of one row, the rig / point rows x grid part one row per G lanes.  H_dd keeps its layout (upper, row-major,
+// the earlier engine unknown as the row), so launch_gf_form reads the sums as it reads a single process's accumulator.
+struct GfSharedArgs {
+  double* Hdd; int ld; double* bd; double* buf;
+  const int* col;                  // [G] band position -> engine dense column
+  int n_cams, rig, n_rp, G;
+  int cam_pos[17]; int width[16];
+  long long band_off[17];
+  long long off_rp_grid, off_rig, off_pp, off_b, doubles;
+};
+template <bool kUnpack>
+__global__ void __launch_bounds__(256) k_gf_shared(GfSharedArgs a) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < a.doubles; e += stride) {
+    long long h = -1;              // element of H_dd, or -1: none (band padding / lower copy of a rig x rig entry on unpack)
+    if (e < a.off_rp_grid) {       // band of camera c: unknown i (band numbering) x its k-th right neighbour
+      int c = 0;
+      while (e >= a.band_off[c + 1]) ++c;
+      const int w = a.width[c];
+      const int local = (int)(e - a.band_off[c]);
+      const int i = local / w, k = local - i * w;
+      const int n = a.cam_pos[c + 1] - a.cam_pos[c];
+      if (i + k < n) {
+        const int u = a.col[a.cam_pos[c] + i], v = a.col[a.cam_pos[c] + i + k];
+        h = (long long)min(u, v) * a.ld + max(u, v);
+      }
+    } else if (e < a.off_rig) {    // rig / point row r x grid column j (every grid column lies right of every rig / point row)
+      const int local = (int)(e - a.off_rp_grid);
+      const int r = local / a.G, j = local - r * a.G;
+      h = (long long)r * a.ld + a.col[j];
+    } else if (e < a.off_pp) {     // rig row r x rig / point column q
+      const int local = (int)(e - a.off_rig);
+      const int r = local / a.n_rp, q = local - r * a.n_rp;
+      if (!kUnpack || r <= q) h = (long long)min(r, q) * a.ld + max(r, q);
+    } else if (e < a.off_b) {      // 3 x 3 block of point p, upper triangle row by row
+      const int local = (int)(e - a.off_pp);
+      const int p = local / 6, q = local - 6 * p;
+      const int di = q < 3 ? 0 : (q < 5 ? 1 : 2);
+      const int dj = q < 3 ? q : (q < 5 ? q - 2 : 2);
+      const int r0 = a.rig + 3 * p;
+      h = (long long)(r0 + di) * a.ld + r0 + dj;
+    } else {                       // J^T r of the dense part
+      const int j = (int)(e - a.off_b);
+      if (kUnpack) a.bd[j] = a.buf[e];
+      else a.buf[e] = a.bd[j];
+      continue;
+    }
+    if (kUnpack) { if (h >= 0) a.Hdd[h] = a.buf[e]; }
+    else a.buf[e] = h >= 0 ? a.Hdd[h] : 0.0;
+  }
+}
+int launch_gf_shared(const GfShared& L, const int* col, double* Hdd, int ld, double* bd, double* buf, int unpack, hipStream_t s) {
+  GfSharedArgs a{};
+  a.Hdd = Hdd; a.ld = ld; a.bd = bd; a.buf = buf; a.col = col;
+  a.n_cams = L.n_cameras; a.rig = L.rig; a.n_rp = L.n_rp; a.G = L.G;
+  for (int c = 0; c <= L.n_cameras; ++c) { a.cam_pos[c] = L.cam_pos[c]; a.band_off[c] = L.band_off[c]; }
+  for (int c = 0; c < L.n_cameras; ++c) a.width[c] = L.width[c];
+  for (int c = L.n_cameras + 1; c < 17; ++c) { a.cam_pos[c] = L.cam_pos[L.n_cameras]; a.band_off[c] = L.band_off[L.n_cameras]; }
+  a.off_rp_grid = L.off_rp_grid; a.off_rig = L.off_rig; a.off_pp = L.off_pp; a.off_b = L.off_b; a.doubles = L.doubles;
+  const long long blocks = std::min<long long>((L.doubles + 255) / 256, 16384);
+  if (blocks <= 0) return CBA_OK;
+  if (unpack) hipLaunchKernelGGL(k_gf_shared<true>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_gf_shared<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+
+// Activity words cross the ranks inside an fp64 gather (or a sum with zeros in the other ranks' blocks): as their two 32-bit halves,
+// each an exact integer in a double, then OR-ed over the ranks' blocks
+__global__ void k_gf_words_to_doubles(const unsigned long long* __restrict__ w, int n, double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long v = w[i];
+  out[2 * i] = (double)(unsigned)(v & 0xffffffffull);
+  out[2 * i + 1] = (double)(unsigned)(v >> 32);
+}
+__global__ void k_gf_or_words(const double* __restrict__ blocks, int world, long long block_stride, int n, unsigned long long* __restrict__ w) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  unsigned long long v = 0;
+  for (int r = 0; r < world; ++r) {
+    const double* b = blocks + (size_t)r * block_stride;
+    v |= (unsigned long long)(unsigned)b[2 * i] | ((unsigned long long)(unsigned)b[2 * i + 1] << 32);
+  }
+  w[i] = v;
+}
+int launch_gf_words_to_doubles(const unsigned long long* w, int n, double* out, hipStream_t s) {
+  if (n <= 0) return CBA_OK;
+  hipLaunchKernelGGL(k_gf_words_to_doubles, dim3((n + 255) / 256), dim3(256), 0, s, w, n, out);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+int launch_gf_or_words(const double* blocks, int world, long long block_stride, int n, unsigned long long* w, hipStream_t s) {
+  if (n <= 0) return CBA_OK;
+  hipLaunchKernelGGL(k_gf_or_words, dim3((n + 255) / 256), dim3(256), 0, s, blocks, world, block_stride, n, w);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

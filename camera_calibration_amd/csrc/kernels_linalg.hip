@@ -792,6 +792,7 @@ __device__ __forceinline__ int bits_next(const unsigned long long* bits, int k, 
 constexpr int kCtrlWords = 128;     // control words of a dataflow launch: [1] abort, [2] role tickets, [3] CU of the chain (dense launch),
 constexpr int kCtrlChainCu = 16;    // [8 + x] task tickets of list x, [kCtrlChainCu + i] CU of chain i (block-sparse launch)
 constexpr int kMaxChains = kCtrlWords - kCtrlChainCu;
+int ldlt_gridfirst_max_chains() { return kMaxChains; }
 constexpr unsigned long long kTailTimeoutTicks = 300000000ull;   // 3 s
 
 typedef unsigned v4u32_t __attribute__((ext_vector_type(4)));

@@ -99,19 +99,20 @@ def make_allreduce_host_staged():
 
 
 class GridFirstSharedLayout:
-    """FOLLOW-UP DESIGN (not used by the engine yet): what would cross the ranks per Gauss-Newton step if the
-    image-sharded path used the grid-first elimination order -- literally BASELINE.json's "shared intrinsics and pattern J^T J /
-    J^T r blocks" instead of the packed reduced system S of the pose-first order:
+    """What crosses the ranks per Gauss-Newton step when the image-sharded path uses the grid-first elimination order
+    (cba_solver_options.elimination = 2 with an all-reduce callback) -- literally BASELINE.json's "shared
+    intrinsics and pattern J^T J / J^T r blocks" instead of the packed reduced system S of the pose-first order:
 
         [ grid x grid, BANDED: unknown g of a camera (numbered along the short grid dimension) x its hb + 1 right neighbours |
           rig / point rows x grid columns, dense | rig rows x (rig, point) columns | 3 x 3 point blocks (upper) | J^T r of all of them ]
 
     An observation touches a 4 x 4 window of control points (APP/models/central_grid.h:199-209), so nothing else of the dense part of
     the reference's accumulator (LV/lm_optimizer_update_accumulator.h:108-155: rig | points | intrinsics) can be non-zero.  At BASELINE
-    configs[1] this is 228 MB against the 642 MB of the packed upper triangle of S (cba_reduce_buffer_doubles).  The pose blocks D_i /
-    strips B_i stay on their owners in both designs.  pack / unpack work on the reference-order dense part (oracle.System.dense_H /
-    dense_b layout); tests/test_distributed_gloo.py sums the buffer over two ranks with gloo and compares with the single-process
-    accumulator."""
+    configs[1] this is 227 MB against the 649 MB of the packed upper triangle of S.  The engine all-reduces exactly this buffer (its pack /
+    unpack kernels, kernels_gridfirst.hip: k_gf_shared, map the band to its own column order; the pose rows D_i / b_i / B_i are
+    all-gathered next to it).  pack / unpack here work on the reference-order dense part (oracle.System.dense_H / dense_b layout);
+    tests/test_gridfirst_sharded_layout.py checks the library's layout against this one (cba_gridfirst_plan_query items 7 / 8) and sums
+    the buffer over two gloo ranks."""
 
     def __init__(self, cameras, n_points: int):
         self.cameras = list(cameras)

@@ -159,7 +159,9 @@ def gridfirst_plan(cameras: Sequence[Camera], n_images: int, n_points: int, stri
 
     Keys: the header fields (G, Gf, n_rp, n_border, n_fact, n_pad, nbg, nbf, ntc, n_tasks0, mask_words, half_bandwidth, strips0),
     f_of_grid (G,), chains (n, 4), tasks (n, 4: kind | intervals << 8, r, c, first interval), ivals (n, 2), rowmask (nbf, words),
-    flops (3,), gperm (list per camera)."""
+    flops (3,), gperm (list per camera), shared (the buffer of shared blocks that image sharding all-reduces per step: doubles, section
+    offsets off_rp_grid / off_rig / off_pp / off_b, G, band_ref_col = reference dense column of every band position; the layout of
+    distributed.GridFirstSharedLayout)."""
     L = load()
     cams = (CbaCamera * len(cameras))(*[_cam_struct(c) for c in cameras])
 
@@ -183,6 +185,9 @@ def gridfirst_plan(cameras: Sequence[Camera], n_images: int, n_points: int, stri
     plan["rowmask"] = q(5, np.uint64).reshape(plan["nbf"], plan["mask_words"])
     plan["flops"] = q(6, np.float64)
     plan["gperm"] = [q(16 + c, np.int32) for c in range(len(cameras))]
+    sh = q(7, np.int64)
+    plan["shared"] = {k: int(v) for k, v in zip(["doubles", "off_rp_grid", "off_rig", "off_pp", "off_b", "G"], sh)}
+    plan["shared"]["band_ref_col"] = q(8, np.int32)
     return plan
 
 

@@ -85,7 +85,13 @@ typedef struct {
                                  factored instead (5 445 instead of 12 525 rows at BASELINE configs[1]: 0.39 instead of 0.77 TFLOP per
                                  solve).  0 = automatic: grid-first on one GPU when a flop model of the two orders favours it (poses the
                                  Schur blocks, intrinsics optimised, at least 2048 grid unknowns), pose-first otherwise (always with image
-                                 sharding: the reduced system that crosses the ranks is the pose-first one).  DESIGN.md section 3a */
+                                 sharding).  2 with `allreduce` set: image sharding in the grid-first order -- per Gauss-Newton step one
+                                 all-reduce of the shared blocks of the dense part (banded grid x grid, rig / point rows x grid, rig rows,
+                                 3 x 3 point blocks, J^T r: cba_reduce_buffer_doubles), one all-gather of every rank's pose rows (6 x its
+                                 imagesets), and the solve of the whole system replicated on every rank; the result is the single-process
+                                 one up to the rounding of the cross-rank sums.  Needs rank / world_size; refused (CBA_ERR_UNSUPPORTED) with
+                                 distributed_solve = 1 and for plans over the launches' limits (1024 grid block rows, 64 KB of LDS for the
+                                 activity bit sets of the border).  DESIGN.md sections 3a, 6a */
   int32_t grid_strips;        /* grid-first order: independent strips the long grid dimension is cut into (separated by 3-line
                                  separators that are eliminated after the strips): one pivot chain per strip instead of one chain of
                                  all grid unknowns.  0 = automatic (at most 4) */
@@ -104,7 +110,10 @@ typedef struct {
   int32_t eliminate_points;      /* OptimizeJointly argument (0 = eliminate imageset poses, the CLI's mode) */
   int32_t device;                /* HIP device ordinal */
   /* multi-GPU (optional): this rank owns a contiguous range of the imagesets; dense-part blocks are
-   * summed over ranks with `allreduce` once per Gauss-Newton step. */
+   * summed over ranks with `allreduce` once per Gauss-Newton step (pose-first order: the packed reduced system; grid-first order,
+   * solver.elimination = 2: the shared blocks, plus the pose rows of every rank gathered -- through `collective` if set, otherwise
+   * as sums through `reduce_buffer` / the engine's own buffer in chunks of its size, with zeros in the other ranks' blocks).
+   * `allreduce` is only ever called on that buffer and on library buffers of at most 8 doubles. */
   cba_allreduce_fn allreduce;
   void* allreduce_user;
   int32_t n_images_global;       /* total imagesets over all ranks (0 = n_images) */
@@ -133,8 +142,9 @@ typedef struct {
   int32_t distributed_solve;
   int32_t rank;
   int32_t world_size;
-  /* reduce-scatter / all-gather of the distributed solve (optional: without it they are emulated with `allreduce`, same
-   * results, 2-world x the bytes) */
+  /* reduce-scatter / all-gather of the distributed solve and, with the grid-first order under sharding, the all-reduce of the
+   * shared blocks and the all-gather of the pose rows (optional: without it they are emulated with `allreduce`, same results,
+   * 2-world x the bytes for the distributed solve) */
   cba_collective_fn collective;
   void* collective_user;
   cba_solver_options solver;     /* scheduling options of the reduced solve (all zero = defaults) */
@@ -305,7 +315,10 @@ int cba_debug_apply_update(cba_problem* p, const double* x);
  * n_border, n_fact, n_pad, nbg, nbf, ntc, chains, tasks, tasks of list 0, intervals, mask words, half-bandwidth, strips of camera 0),
  * 1 = row of F of every grid unknown in the engine's order (int32 x G), 2 = chains (int32 x 4: r0, r1, dep, 0), 3 = tasks (int32 x 4:
  * kind | intervals << 8, r, c, first interval; kinds: gridfirst_plan.h), 4 = K intervals (int32 x 2), 5 = row masks (uint64 x nbf x mask words), 6 = flop model
- * (double x 3: dataflow launch of the grid rows, border update, border factorisation), 16 + c = control point -> elimination rank of
+ * (double x 3: dataflow launch of the grid rows, border update, border factorisation), 7 = shared blocks of image sharding in this order
+ * (int64 x 6: doubles, first double of the rig / point rows x grid part, of the rig rows, of the point blocks, of J^T r, grid unknowns;
+ * = distributed.GridFirstSharedLayout), 8 = band numbering of the shared blocks (int32 x G: reference dense column of every band
+ * position), 16 + c = control point -> elimination rank of
  * camera c (int32 x grid_w grid_h).  Returns the number of bytes of the item (written if capacity_bytes suffices) or a negative
  * error code.  (No reference counterpart: LV/lm_optimizer.h:1247-1369 has one elimination order.) */
 int64_t cba_gridfirst_plan_query(const cba_camera* cameras, int32_t n_cameras, int32_t n_images, int32_t n_points, int32_t strips,
@@ -318,6 +331,8 @@ int32_t cba_total_dof(const cba_problem* p);
 int32_t cba_dense_dof(const cba_problem* p);
 /* layout of one CBA_DUMP_JACOBIANS record: [res 2][weight 1][pose 2x6][rig 2x6][point 2x3][grid 2xK] */
 int32_t cba_jacobian_record_doubles(const cba_problem* p);
+/* doubles of the reduce buffer the configuration needs: the packed reduced system (pose-first), the staging of the distributed solve,
+ * or with solver.elimination = 2 the shared blocks of the grid-first order (227 MB at BASELINE configs[1]; never chunked) */
 int64_t cba_reduce_buffer_doubles(const cba_config* config);
 /* device-side event timing of the dominant kernels of the last cba_step (bench roofline):
  * which: 0 = Schur GEMM launch, 1 = the whole factorisation (flops = its trailing updates), 2 = accumulation,

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 
 #include "cba_internal.h"
@@ -119,7 +120,7 @@ using namespace cba;
 // Stage timers: HIP events on the stream the kernels run on, read back only at the end of the step (a wait on the
 // host in the middle of a step would keep the next stage's launches from being queued behind the running one).
 struct KernelTimer {
-  struct Span { hipEvent_t e0 = nullptr, e1 = nullptr; };
+  struct Span { Event e0, e1; };
   std::vector<Span> spans;     // event pairs, reused from step to step
   int used = 0;                // spans recorded since the last collect
   double seconds = 0, flops = 0, bytes = 0;
@@ -139,77 +140,79 @@ struct cba_problem {
   int model_mask = 0;
   int tasks_per_obs = 0, rec_doubles = 0;
   // observations
-  float* obs_xy = nullptr; int* obs_point = nullptr; int* obs_image = nullptr; int* obs_camera = nullptr;
-  double* last_projection = nullptr;
+  DevBuf<float> obs_xy; DevBuf<int> obs_point, obs_image, obs_camera;
+  DevBuf<double> last_projection;
   // state (double buffered)
   DevState st[2];
   int cur = 0;
-  double* itg = nullptr;
-  double* tangents[kMaxCameras] = {};
-  CamDev* cams_dev[2] = {nullptr, nullptr};
+  DevBuf<double> itg;
+  DevBuf<double> tangents[kMaxCameras];
+  DevBuf<CamDev> cams_dev[2];
   // pass outputs
-  double* cost_ref = nullptr; double* cost_test = nullptr; double* pixels = nullptr; uint8_t* flags = nullptr;
-  double* fd_out = nullptr; uint8_t* fd_ok = nullptr; double* jrec = nullptr; int* cells = nullptr;
-  uint32_t* pair_tables = nullptr; int* pair_counts = nullptr;
-  int* pt_start = nullptr; int* pt_obs = nullptr;   // observations bucketed by (camera, pattern point): k_accumulate_points
-  std::vector<int> cell_base_host; int* cell_base = nullptr; int* cell_count = nullptr; int* cell_start = nullptr; int* cell_fill = nullptr;
-  int* cell_order = nullptr;
+  DevBuf<double> cost_ref, cost_test, pixels; DevBuf<uint8_t> flags;
+  DevBuf<double> fd_out; DevBuf<uint8_t> fd_ok; DevBuf<double> jrec; DevBuf<int> cells;
+  DevBuf<uint32_t> pair_tables; DevBuf<int> pair_counts;
+  DevBuf<int> pt_start, pt_obs;   // observations bucketed by (camera, pattern point): k_accumulate_points
+  std::vector<int> cell_base_host; DevBuf<int> cell_base, cell_count, cell_start, cell_fill;
+  DevBuf<int> cell_order;
   // imageset -> position of its 6x6 block / rows of B.  Imagesets are sorted along a Z-order curve of the
   // centre of their observations so that the 16-row K slabs of the Schur product touch few grid tiles.
-  std::vector<int> pose_slot_host; int* pose_slot = nullptr;
+  std::vector<int> pose_slot_host; DevBuf<int> pose_slot;
   // straggler split of the Jacobian pass (see PassArgs)
-  uint8_t* slow_skip = nullptr; uint8_t* fd_slow = nullptr; int* slow_list = nullptr; int* slow_count = nullptr;
+  DevBuf<uint8_t> slow_skip, fd_slow; DevBuf<int> slow_list, slow_count;
   int slow_cap = kSlowCapMin;
   int straggler_threshold = 8;    // outer projection iterations before an observation goes to the straggler kernel
   int fd_schedule = -1;           // finite-difference kernel: -1 = automatic (default), 0 = pooled tasks, 1 = one task per lane (cba_set_fd_schedule)
-  int64_t* img_start = nullptr;          // first observation of every imageset (+ end), for the strip accumulation
-  unsigned long long* band_mask = nullptr;   // per observation: column bands of B it touches
+  DevBuf<int64_t> img_start;             // first observation of every imageset (+ end), for the strip accumulation
+  DevBuf<unsigned long long> band_mask;      // per observation: column bands of B it touches
   // the side stream is the factorisation's far stream (idle during the Jacobian pass): the process must stay
   // within four HIP streams -- a fifth shares a hardware queue with another one and serialises the LDL^T streams
   // (measured twice, also with GPU_MAX_HW_QUEUES=8)
-  hipEvent_t ev_aux0 = nullptr, ev_aux1 = nullptr, ev_aux2 = nullptr, ev_clear = nullptr, ev_mask = nullptr;
+  Event ev_aux0, ev_aux1, ev_aux2, ev_clear, ev_mask;
   // control point -> rank in the engine's tiled order of the grid unknowns, per camera (see build_grid_order)
-  int* gperm[kMaxCameras] = {};
+  DevBuf<int> gperm[kMaxCameras];
   std::vector<int> dense_perm_host;   // reference dense column -> engine dense column (identity outside the grids)
-  double* red_partials = nullptr; double* red8 = nullptr;
+  DevBuf<double> red_partials, red8;
   // system
   int n_pad = 0, n_fact = 0, Kpad = 0;
-  double* Dblk = nullptr; double* bblk = nullptr; double* B = nullptr; double* Hdd = nullptr; double* bd = nullptr;
-  double* Dinv = nullptr; double* dinvb = nullptr; double* W = nullptr; double* S = nullptr; bool S_owned = true; double* P = nullptr; bool P_owned = true; double* P2 = nullptr; size_t dist_buf_doubles = 0;
-  double* x = nullptr; double* scal = nullptr; double* gemv_ws = nullptr;
-  unsigned long long* kmask = nullptr;   // block-sparsity of B per (column tile, K slab), rebuilt after every accumulation
-  unsigned long long* kmask_host = nullptr; size_t kmask_host_words = 0;   // pinned copy (flop count of the Schur product)
+  DevBuf<double> Dblk, bblk, B, Hdd, bd;
+  DevBuf<double> Dinv, dinvb, W, S;
+  double* P = nullptr; DevBuf<double> P_own;   // reduce buffer of the multi-rank paths: the caller's cba_config.reduce_buffer, or P_own
+  DevBuf<double> P2; size_t dist_buf_doubles = 0;
+  DevBuf<double> x, scal, gemv_ws;
+  DevBuf<unsigned long long> kmask;      // block-sparsity of B per (column tile, K slab), rebuilt after every accumulation
+  PinnedBuf<unsigned long long> kmask_host;   // pinned copy (flop count of the Schur product)
   // chunk order of the Schur launch (heaviest first) from the masks of the PREVIOUS solve: the sparsity of B only changes with
   // the validity flags, and the order is a scheduling hint (any permutation is correct)
-  int* chunk_order = nullptr; int* chunk_order_host = nullptr; bool chunk_order_valid = false; unsigned chunk_order_age = 0;
-  int* status = nullptr;
+  DevBuf<int> chunk_order; PinnedBuf<int> chunk_order_host; bool chunk_order_valid = false; unsigned chunk_order_age = 0;
+  DevBuf<int> status;
   LdltWorkspace ldlt;
   KernelTimer timers[8];     // 0 ... 4: see cba_kernel_stats; 5: Jacobian pass, 6: solves, 7: cost passes queued behind a solve (cba_report.t_jac / t_solve / t_cost)
   // deterministic mode (cba_config.deterministic): fixed-point scale of the current pass
-  unsigned long long* det_bits = nullptr; double* det_scale = nullptr;
+  DevBuf<unsigned long long> det_bits; DevBuf<double> det_scale;
   // finite-difference kernel: work lists of the tasks that leave their staged patch (main launch / side-stream launch)
-  int64_t* fd_redo[2] = {nullptr, nullptr}; int* fd_redo_count = nullptr;   // counts: [0] main list, [1] side-stream list, [2] tasks that found a list full
+  DevBuf<int64_t> fd_redo[2]; DevBuf<int> fd_redo_count;   // counts: [0] main list, [1] side-stream list, [2] tasks that found a list full
   int fd_redo_cap = 0;
   double last_lambda = 0;
   bool mask_pending = false;      // a touch-mask launch of the last Jacobian pass may still read B on the side stream
-  double* pin_status = nullptr;   // pinned host memory: {status, ldlt status, x[0]} of the last solve
-  double* pin_cost = nullptr;     // pinned host memory: the 8 reduced scalars of the Jacobian pass when their read is deferred
+  PinnedBuf<double> pin_status;   // pinned host memory: {status, ldlt status, x[0]} of the last solve
+  PinnedBuf<double> pin_cost;     // pinned host memory: the 8 reduced scalars of the Jacobian pass when their read is deferred
   double last_x0 = 0;     // x[0] of the last solve (read back with the status words: the NaN test of lm_optimizer.h:905 needs no second wait)
   // grid-first elimination order (cba_solver_options.elimination; gridfirst_plan.h): the full normal matrix F = [grid | rig | points |
   // poses] is formed from Dblk / B / Hdd per LM attempt and factored in place; S, W, Dinv and the touch masks are not allocated
   bool gridfirst = false;
   GfPlan gf;
   GfDevice gfd;
-  double* F = nullptr;            // gf.n_pad x gf.n_pad, upper triangle, row-major
-  double* Xb = nullptr;           // gf.Gf x (gf.n_pad - gf.Gf): X = D L of the border columns (B operand of the border update)
-  double* xF = nullptr;           // gf.n_fact: solution in the order of F
-  int* gf_tiles = nullptr; int n_gf_tiles = 0;        // tiles of F the forming kernel writes
-  int* gf_grid_of_f = nullptr; int* gf_f_of_grid = nullptr;
-  unsigned long long* gf_kmask_host = nullptr;    // pinned copy of the border update's K-slab masks (executed flops of the launch)
+  DevBuf<double> F;               // gf.n_pad x gf.n_pad, upper triangle, row-major
+  DevBuf<double> Xb;              // gf.Gf x (gf.n_pad - gf.Gf): X = D L of the border columns (B operand of the border update)
+  DevBuf<double> xF;              // gf.n_fact: solution in the order of F
+  DevBuf<int> gf_tiles; int n_gf_tiles = 0;        // tiles of F the forming kernel writes
+  DevBuf<int> gf_grid_of_f, gf_f_of_grid;
+  PinnedBuf<unsigned long long> gf_kmask_host;    // pinned copy of the border update's K-slab masks (executed flops of the launch)
   double gf_update_flops = 0;                     // executed flops of the border update with the masks of the last pass
   // order of the border update's tiles, heaviest first, from the masks of the PREVIOUS solve (a scheduling hint: any permutation is
   // correct, and the activity hardly moves from pass to pass)
-  int* gf_tile_list = nullptr; int* gf_tile_list_host = nullptr; bool gf_tile_list_valid = false; unsigned gf_tile_list_age = 0;
+  DevBuf<int> gf_tile_list; PinnedBuf<int> gf_tile_list_host; bool gf_tile_list_valid = false; unsigned gf_tile_list_age = 0;
   int gf_tile_list_entries = 0;     // slots of the launch (eight interleaved per-XCD lists, padded)
   bool gf_tile_list_dirty = false;  // the host copy was rebuilt since the last upload
   size_t gf_tile_list_capacity = 0; // ints
@@ -218,11 +221,11 @@ struct cba_problem {
   // solve of F is replicated.  The border's pose order is rank-major: rank r's imagesets hold slots gf_offsets[r] ... in its own slot order.
   bool gf_sharded = false;
   GfShared gfs;
-  int* gfs_col = nullptr;                      // [gfs.G] band position -> engine dense column
+  DevBuf<int> gfs_col;                         // [gfs.G] band position -> engine dense column
   int gf_rank = 0, gf_world = 1, gf_img0 = 0, gf_max_local = 0;
   std::vector<int> gf_counts, gf_offsets;      // imagesets of every rank / first border slot of every rank
-  double* gDblk = nullptr; double* gbblk = nullptr; double* gB = nullptr;      // pose rows of ALL ranks (border order)
-  double* gsend = nullptr; double* grecv = nullptr; int64_t gblk = 0;          // all-gather staging: [words | D | b | B] of one rank, padded
+  DevBuf<double> gDblk, gbblk, gB;             // pose rows of ALL ranks (border order)
+  DevBuf<double> gsend, grecv; int64_t gblk = 0;                   // all-gather staging: [words | D | b | B] of one rank, padded
   int64_t P_cap = 0;                           // doubles of the reduce buffer P
 };
 
@@ -233,8 +236,8 @@ static int timer_begin(cba_problem* p, int which, hipStream_t s = nullptr) {
   KernelTimer& t = p->timers[which];
   if (t.used == (int)t.spans.size()) {
     KernelTimer::Span sp;
-    CBA_HIP(hipEventCreate(&sp.e0)); CBA_HIP(hipEventCreate(&sp.e1));
-    t.spans.push_back(sp);
+    CBA_TRY(sp.e0.create()); CBA_TRY(sp.e1.create());
+    t.spans.push_back(std::move(sp));
   }
   CBA_HIP(hipEventRecord(t.spans[t.used].e0, s ? s : p->stream));
   return CBA_OK;
@@ -263,26 +266,6 @@ static int timers_collect(cba_problem* p) {
   return CBA_OK;
 }
 
-template <typename T>
-static int dev_alloc(T** p, size_t n) {
-  *p = nullptr;
-  if (n == 0) n = 1;
-  CBA_HIP(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  return CBA_OK;
-}
-#define CBA_TRY(expr) do { int _rc = (expr); if (_rc != CBA_OK) return _rc; } while (0)
-
-// device buffers of one stateless call: freed on every exit path
-struct DevPool {
-  std::vector<void*> ptrs;
-  ~DevPool() { for (void* q : ptrs) if (q) hipFree(q); }
-  template <typename T> int alloc(T** p, size_t n) {
-    int rc = dev_alloc(p, n);
-    if (rc == CBA_OK) ptrs.push_back(*p);
-    return rc;
-  }
-};
-struct LdltGuard { LdltWorkspace* w; ~LdltGuard() { if (w) ldlt_workspace_free(*w); } };
 // cba_solver_options -> the workspace of a problem / call (zero fields keep the defaults)
 static void apply_solver_options(LdltWorkspace& w, const cba_solver_options* o) {
   if (!o) return;
@@ -291,12 +274,12 @@ static void apply_solver_options(LdltWorkspace& w, const cba_solver_options* o) 
 }
 
 static int alloc_state(cba_problem* p, DevState& s) {
-  CBA_TRY(dev_alloc(&s.rig_tr_global, 7 * (size_t)p->L.n_images));
-  CBA_TRY(dev_alloc(&s.camera_tr_rig, 7 * (size_t)p->L.n_cameras));
-  CBA_TRY(dev_alloc(&s.points, 3 * (size_t)p->L.n_points));
+  CBA_TRY(s.rig_tr_global.alloc(7 * (size_t)p->L.n_images));
+  CBA_TRY(s.camera_tr_rig.alloc(7 * (size_t)p->L.n_cameras));
+  CBA_TRY(s.points.alloc(3 * (size_t)p->L.n_points));
   for (int c = 0; c < p->L.n_cameras; ++c) {
     size_t G = (size_t)p->cams[c].grid_w * p->cams[c].grid_h;
-    CBA_TRY(dev_alloc(&s.grids[c], (p->cams[c].model_type == CBA_CENTRAL_GENERIC ? 3 : 6) * G));
+    CBA_TRY(s.grids[c].alloc((p->cams[c].model_type == CBA_CENTRAL_GENERIC ? 3 : 6) * G));
   }
   return CBA_OK;
 }
@@ -324,7 +307,7 @@ static int build_grid_order(cba_problem* p) {
       for (int tx = 0; tx < gw; tx += tile)
         for (int y = ty; y < std::min(gh, ty + tile); ++y)
           for (int x = tx; x < std::min(gw, tx + tile); ++x) perm[x + (size_t)y * gw] = rank++;
-    CBA_TRY(dev_alloc(&p->gperm[c], perm.size()));
+    CBA_TRY(p->gperm[c].alloc(perm.size()));
     CBA_HIP(hipMemcpy(p->gperm[c], perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice));
     for (size_t g = 0; g < perm.size(); ++g)
       for (int d = 0; d < per; ++d)
@@ -340,6 +323,13 @@ static int upload_camdevs(cba_problem* p, int which) {
   CBA_HIP(hipMemcpyAsync(p->cams_dev[which], h.data(), sizeof(CamDev) * h.size(), hipMemcpyHostToDevice, p->stream));
   CBA_HIP(hipStreamSynchronize(p->stream));
   return CBA_OK;
+}
+// launch_apply_update takes the grid orders as an array of raw device pointers
+struct GpermView { int* v[kMaxCameras] = {}; };
+static GpermView gperm_view(const cba_problem* p) {
+  GpermView g;
+  for (int c = 0; c < kMaxCameras; ++c) g.v[c] = p->gperm[c];
+  return g;
 }
 
 // -1 (default): pooled wherever the projections of one wavefront differ in length -- the non-central model (83 tasks per observation) and
@@ -515,7 +505,7 @@ static int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   AccumTargets T{p->Dblk, p->bblk, p->B, p->Hdd, p->bd};
   Layout Lp = L;
   Lp.dense_dof = p->n_pad;  // Hdd / B use the padded leading dimension as row stride
-  const double* det = p->cfg.deterministic ? p->det_scale : nullptr;
+  const double* det = p->cfg.deterministic ? (const double*)p->det_scale : nullptr;
   if (det) CBA_TRY(launch_det_scale(p->n_obs, p->rec_doubles, p->rec_doubles, p->flags, p->jrec, p->det_bits, p->det_scale, p->stream));
   const int points_separate = (!L.eliminate_points && p->pt_start) ? 1 : 0;
   // The four accumulation kernels write disjoint parts of the system (or add atomically).  The per-cell kernel runs on the side
@@ -705,7 +695,6 @@ static int solve_enqueue_gridfirst(cba_problem* p, double lambda) {
   CBA_TRY(timer_end(p, 1, gs.flops, 0, gs.launches));
   CBA_TRY(ldlt_back_solve(p->F, g.n_fact, ld, ld - 1, p->ldlt, p->xF, p->stream, d.rowmask_dyn, d.mask_words));
   CBA_TRY(launch_gf_scatter(p->xF, g.Gf, g.n_rp, L.block_dof, g.G, p->gf_f_of_grid, sh ? 6 * p->gf_img0 : 0, p->x, p->stream));
-  if (!p->pin_status) CBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->pin_status), 4 * sizeof(double)));
   hipLaunchKernelGGL(k_solve_status, dim3(1), dim3(64), 0, p->stream, p->status, p->ldlt.status, p->x, p->pin_status, p->status + 1);
   CBA_HIP(hipGetLastError());
   CBA_TRY(timer_end(p, 6, 0, 0, 1));
@@ -724,11 +713,6 @@ static int solve_enqueue(cba_problem* p, double lambda, cba_report* rep) {
   // side B^T D^-1 b (one pass over B), the touch masks on their way to the host, and the control words of the factorisation's first
   // dataflow launch.  Round 3 had all three between the Schur product and the factorisation: 0.15 ms of small launches and gaps.
   const int mask_tiles = p->n_pad / 128, mask_words = schur_mask_words(p->Kpad);
-  if (p->kmask_host_words < (size_t)mask_tiles * mask_words) {
-    if (p->kmask_host) CBA_HIP(hipHostFree(p->kmask_host));
-    p->kmask_host_words = (size_t)mask_tiles * mask_words;
-    CBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->kmask_host), p->kmask_host_words * sizeof(unsigned long long)));
-  }
   {
     hipStream_t side = p->ldlt.far_stream;
     CBA_HIP(hipEventRecord(p->ev_aux0, p->stream));
@@ -782,7 +766,6 @@ static int solve_enqueue(cba_problem* p, double lambda, cba_report* rep) {
   CBA_TRY(launch_gemv_n(p->W, L.block_dof, dd, ld, p->x + L.block_dof, p->dinvb, p->x, p->stream));
   // the two status words and x[0] reach the host through ONE launch that writes pinned host memory (three device-to-host copies in
   // a row cost 20 us each in front of the host's decision)
-  if (!p->pin_status) CBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->pin_status), 4 * sizeof(double)));
   hipLaunchKernelGGL(k_solve_status, dim3(1), dim3(64), 0, p->stream, p->status, p->ldlt.status, p->x, p->pin_status, p->status + 1);
   CBA_HIP(hipGetLastError());
   CBA_TRY(timer_end(p, 6, 0, 0, 1));
@@ -850,6 +833,432 @@ static int solve_finish(cba_problem* p) {
   return CBA_OK;
 }
 
+
+// ---- cba_create, step by step ----
+static int check_config(const cba_config* config) {
+  if (!config || !config->cameras || config->n_cameras < 1 || config->n_cameras > kMaxCameras ||
+      config->n_images < 0 || config->n_points < 0 || !(config->numerical_diff_delta > 0)) {
+    set_error("cba_create: bad config"); return CBA_ERR_ARG;
+  }
+  for (int c = 0; c < config->n_cameras; ++c)
+    if (!camera_ok(config->cameras[c])) { set_error("cba_create: bad camera"); return CBA_ERR_ARG; }
+  if (config->allreduce && config->eliminate_points) { set_error("image sharding requires eliminate_points = 0"); return CBA_ERR_UNSUPPORTED; }
+  if (config->distributed_solve) {
+    // the distributed factorisation walks the column groups by rank: an invalid rank would loop for ever or leave groups unowned
+    if (!config->allreduce) { set_error("cba_create: distributed_solve needs an allreduce callback"); return CBA_ERR_ARG; }
+    if (config->world_size < 1 || config->rank < 0 || config->rank >= config->world_size) {
+      set_error("cba_create: distributed_solve needs 0 <= rank < world_size"); return CBA_ERR_ARG;
+    }
+  }
+  return CBA_OK;
+}
+
+// elimination order (cba_solver_options.elimination); grid-first: the plan, and with image sharding the limits of its launches
+static int choose_elimination_order(cba_problem* p, const cba_config* config) {
+  const Layout& L = p->L;
+  // image sharding: the plan covers the imagesets of all ranks (the border is [rig | points | poses of every rank])
+  const bool sharded = config->allreduce != nullptr;
+  const int n_glob = (sharded && config->n_images_global > 0) ? config->n_images_global : L.n_images;
+  const bool eligible = !L.eliminate_points && !L.localize_only && n_glob > 0 && (sharded || L.n_images > 0);
+  const int want = config->solver.elimination;
+  if (want == 2 && !eligible) { set_error("cba_create: the grid-first elimination order needs eliminate_points = 0 and localize_only = 0"); return CBA_ERR_UNSUPPORTED; }
+  if (want == 2 && sharded && config->distributed_solve) { set_error("cba_create: the grid-first elimination order has no distributed factorisation (distributed_solve = 1)"); return CBA_ERR_UNSUPPORTED; }
+  if (want < 0 || want > 2 || config->solver.grid_strips < 0) { set_error("cba_create: bad solver options"); return CBA_ERR_ARG; }
+  if (want == 2 && sharded && (config->world_size < 1 || config->rank < 0 || config->rank >= config->world_size)) {
+    set_error("cba_create: grid-first sharding needs 0 <= rank < world_size"); return CBA_ERR_ARG;
+  }
+  bool use = want == 2;
+  if (want == 0 && eligible && !sharded) {
+    double pf = 0, gfl = 0;
+    gf_flop_model(p->cams.data(), L.n_cameras, L.n_images, L.n_points, &pf, &gfl);
+    int G = 0;
+    for (int c = 0; c < L.n_cameras; ++c) G += (p->cams[c].model_type == CBA_CENTRAL_GENERIC ? 2 : 5) * p->cams[c].grid_w * p->cams[c].grid_h;
+    use = G >= 2048 && gfl < 0.85 * pf;
+  }
+  if (use) {
+    if (gf_build_plan(p->cams.data(), L.n_cameras, n_glob, L.n_points, config->solver.grid_strips, config->solver.grid_single_tile_tasks, &p->gf) != CBA_OK) { set_error("cba_create: grid-first plan failed"); return CBA_ERR_ARG; }
+    p->gridfirst = true;
+    if (sharded) {
+      // limits of the launches, checked here rather than at the first pass: activity words of k_gf_touch (1024 grid block
+      // rows), its LDS bit sets, the control words of the block-sparse launch, 32-bit offsets inside the sections of k_gf_shared
+      const GfPlan& g = p->gf;
+      const int64_t words = (g.nbg + 63) / 64, touch_lds = 8 * words * ((g.n_pad - g.Gf) / 128);
+      gf_shared_layout(p->cams.data(), L.n_cameras, L.n_points, &p->gfs);
+      int64_t band_max = 0;
+      for (int c = 0; c < L.n_cameras; ++c) band_max = std::max(band_max, p->gfs.band_off[c + 1] - p->gfs.band_off[c]);
+      if (g.nbg > 1024) { set_error("cba_create: grid-first sharding: more than 1024 grid block rows"); return CBA_ERR_UNSUPPORTED; }
+      if (touch_lds > 65536) { set_error("cba_create: grid-first sharding: the activity bit sets of the border need more than 64 KB of LDS"); return CBA_ERR_UNSUPPORTED; }
+      if ((int)g.chains.size() > ldlt_gridfirst_max_chains()) { set_error("cba_create: grid-first sharding: more pivot chains than the block-sparse launch has control words for"); return CBA_ERR_UNSUPPORTED; }
+      if (band_max >= INT32_MAX || (int64_t)p->gfs.n_rp * p->gfs.G >= INT32_MAX) { set_error("cba_create: grid-first sharding: shared blocks too large"); return CBA_ERR_UNSUPPORTED; }
+      p->gf_sharded = true;
+      p->gf_rank = config->rank; p->gf_world = config->world_size;
+    }
+  }
+  return CBA_OK;
+}
+
+// pair tables (upper-triangle (row,col) pairs) for the two column-count classes
+static int upload_pair_tables(cba_problem* p) {
+  const Layout& L = p->L;
+  const size_t stride = (size_t)kMaxCols * (kMaxCols + 1) / 2;
+  std::vector<uint32_t> tab(2 * stride, 0);
+  int counts[2] = {0, 0};
+  for (int slot = 0; slot < 2; ++slot) {
+    int Kg = L.localize_only ? 0 : (slot == 0 ? 32 : 80);
+    int K = 6 + (L.rig_in_state ? 6 : 0) + 3 + Kg;
+    // pairs with both columns in the pose/rig ("hot") range are accumulated in registers by the kernel
+    const int nh = 6 + (L.rig_in_state ? 6 : 0), h0 = L.eliminate_points ? 3 : 0;
+    int e = 0;
+    for (int i = 0; i < K; ++i)
+      for (int k = i; k < K; ++k) {
+        const bool hot = i >= h0 && i < h0 + nh && k >= h0 && k < h0 + nh;
+        const bool grid_grid = i >= K - Kg && k >= K - Kg;   // summed per grid cell by k_accumulate_cells
+        // pose x (point | grid) goes through k_accumulate_strips when the poses are the Schur blocks
+        const bool strip = !L.eliminate_points && i < 6 && k >= nh;
+        // rig pose x grid is summed per grid cell by k_accumulate_cells as well (several cameras, poses eliminated)
+        const bool rig_grid = !L.eliminate_points && L.rig_in_state && i >= 6 && i < 12 && k >= K - Kg;
+        // every pair with a point column is summed per pattern point by k_accumulate_points (poses eliminated)
+        const bool point = !L.eliminate_points && ((i >= nh && i < nh + 3) || (k >= nh && k < nh + 3));
+        if (!hot && !grid_grid && !strip && !rig_grid && !point) tab[slot * stride + e++] = ((uint32_t)i << 16) | (uint32_t)k;
+      }
+    counts[slot] = e;
+  }
+  CBA_TRY(p->pair_tables.alloc(tab.size()));
+  CBA_TRY(p->pair_counts.alloc(2));
+  CBA_HIP(hipMemcpy(p->pair_tables, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(p->pair_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
+  return CBA_OK;
+}
+
+// what the passes over the observations need besides the observations: events, state, per-camera arrays, pair tables, cells
+static int alloc_pass_buffers(cba_problem* p) {
+  const Layout& L = p->L;
+  for (Event* e : {&p->ev_aux0, &p->ev_aux1, &p->ev_aux2, &p->ev_clear, &p->ev_mask}) CBA_TRY(e->create(hipEventDisableTiming));
+  CBA_TRY(p->slow_count.alloc(1));
+  CBA_HIP(hipMemset(p->slow_count, 0, sizeof(int)));
+  for (int c = 0; c < L.n_cameras; ++c) p->model_mask |= (p->cams[c].model_type == CBA_CENTRAL_GENERIC) ? 1 : 2;
+  const int maxKg = L.localize_only ? 0 : ((p->model_mask & 2) ? 80 : 32);
+  p->tasks_per_obs = 3 + maxKg;
+  p->rec_doubles = kRecHeader + 2 * maxKg;
+  CBA_TRY(alloc_state(p, p->st[0]));
+  CBA_TRY(alloc_state(p, p->st[1]));
+  CBA_TRY(p->itg.alloc(16 * (size_t)L.n_images * L.n_cameras));
+  for (int c = 0; c < L.n_cameras; ++c) CBA_TRY(p->tangents[c].alloc(6 * (size_t)p->cams[c].grid_w * p->cams[c].grid_h));
+  CBA_TRY(build_grid_order(p));
+  CBA_TRY(p->cams_dev[0].alloc(L.n_cameras));
+  CBA_TRY(p->cams_dev[1].alloc(L.n_cameras));
+  CBA_TRY(upload_camdevs(p, 0));
+  CBA_TRY(upload_camdevs(p, 1));
+  CBA_TRY(upload_pair_tables(p));
+  p->cell_base_host.assign(L.n_cameras + 1, 0);
+  for (int c = 0; c < L.n_cameras; ++c) p->cell_base_host[c + 1] = p->cell_base_host[c] + p->cams[c].grid_w * p->cams[c].grid_h;
+  const size_t nk = (size_t)p->cell_base_host.back();
+  CBA_TRY(p->cell_base.alloc(p->cell_base_host.size()));
+  CBA_HIP(hipMemcpy(p->cell_base, p->cell_base_host.data(), sizeof(int) * p->cell_base_host.size(), hipMemcpyHostToDevice));
+  CBA_TRY(p->cell_count.alloc(nk + 1)); CBA_TRY(p->cell_start.alloc(nk + 1)); CBA_TRY(p->cell_fill.alloc(nk + 1));
+  CBA_TRY(p->det_bits.alloc(2)); CBA_TRY(p->det_scale.alloc(2));
+  CBA_TRY(p->fd_redo_count.alloc(4));
+  CBA_HIP(hipMemset(p->fd_redo_count, 0, sizeof(int) * 4));
+  CBA_TRY(p->red_partials.alloc(256 * 8));
+  CBA_TRY(p->red8.alloc(16));
+  return CBA_OK;
+}
+
+// pose-first system: W = D^-1 B, the reduced matrix S, the pinned copy of the touch masks
+static int alloc_posefirst_system(cba_problem* p) {
+  CBA_TRY(p->W.alloc((size_t)p->Kpad * p->n_pad));
+  CBA_TRY(p->S.alloc((size_t)p->n_pad * p->n_pad));
+  CBA_HIP(hipMemset(p->S, 0, sizeof(double) * (size_t)p->n_pad * p->n_pad));
+  CBA_HIP(hipMemset(p->W, 0, sizeof(double) * (size_t)p->Kpad * p->n_pad));
+  return p->kmask_host.alloc((size_t)(p->n_pad / 128) * schur_mask_words(p->Kpad));
+}
+
+// grid-first system: F and the plan's arrays, the tiles the forming kernel writes, the activity masks, the tile-list buffers
+static int alloc_gridfirst_system(cba_problem* p) {
+  const GfPlan& g = p->gf;
+  const size_t nf = (size_t)g.n_pad, wb = (size_t)(g.n_pad - g.Gf);
+  CBA_TRY(p->F.alloc(nf * nf));
+  CBA_HIP(hipMemset(p->F, 0, sizeof(double) * nf * nf));          // tiles outside the plan's structure stay zero for ever
+  CBA_TRY(p->Xb.alloc((size_t)g.Gf * wb));
+  CBA_HIP(hipMemset(p->Xb, 0, sizeof(double) * (size_t)g.Gf * wb));
+  CBA_TRY(p->xF.alloc(nf));
+  CBA_TRY(p->gfd.tasks.alloc(g.tasks.size()));
+  CBA_TRY(p->gfd.ivals.alloc(g.ivals.size()));
+  CBA_TRY(p->gfd.chains.alloc(g.chains.size()));
+  CBA_TRY(p->gfd.rowmask.alloc(g.rowmask.size()));
+  CBA_HIP(hipMemcpy(p->gfd.tasks, g.tasks.data(), sizeof(GfTask) * g.tasks.size(), hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(p->gfd.ivals, g.ivals.data(), sizeof(GfIval) * g.ivals.size(), hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(p->gfd.chains, g.chains.data(), sizeof(GfChain) * g.chains.size(), hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(p->gfd.rowmask, g.rowmask.data(), sizeof(uint64_t) * g.rowmask.size(), hipMemcpyHostToDevice));
+  p->gfd.n_tasks0 = g.n_tasks0; p->gfd.n_tasks1 = (int)g.tasks.size() - g.n_tasks0; p->gfd.n_chains = (int)g.chains.size();
+  p->gfd.nbg = g.nbg; p->gfd.nbf = g.nbf; p->gfd.mask_words = g.mask_words; p->gfd.flops_grid = g.flops_grid;
+  // tiles the forming kernel writes per attempt: the structural tiles of the grid x grid part, the row strips of the grid rows
+  // (every border column block + the right-hand side's), the upper triangle of the border
+  // Rule: every tile that any launch of a solve WRITES is formed again for the next attempt (a broken solve -- zero pivot, NaN --
+  // must not leave anything behind: tests/test_gpu_gridfirst.py).  The dense border launch and the border update also write the
+  // padding-only block columns and the block rows behind the factored ones.
+  std::vector<int> tiles(g.grid_tiles);
+  for (int r = 0; r < g.nbg; ++r) {
+    for (int c = g.nbg; c < g.nbf; ++c) { tiles.push_back(r); tiles.push_back(c); }
+    tiles.push_back(r); tiles.push_back(g.ntc - 1);
+  }
+  for (int r = g.nbg; r < g.ntc; ++r)
+    for (int c = r; c < g.ntc; ++c) { tiles.push_back(r); tiles.push_back(c); }
+  p->n_gf_tiles = (int)(tiles.size() / 2);
+  CBA_TRY(p->gf_tiles.alloc(tiles.size()));
+  CBA_HIP(hipMemcpy(p->gf_tiles, tiles.data(), sizeof(int) * tiles.size(), hipMemcpyHostToDevice));
+  CBA_TRY(p->gf_grid_of_f.alloc(g.grid_of_f.size()));
+  CBA_HIP(hipMemcpy(p->gf_grid_of_f, g.grid_of_f.data(), sizeof(int) * g.grid_of_f.size(), hipMemcpyHostToDevice));
+  CBA_TRY(p->gf_f_of_grid.alloc(g.f_of_grid.size()));
+  CBA_HIP(hipMemcpy(p->gf_f_of_grid, g.f_of_grid.data(), sizeof(int) * g.f_of_grid.size(), hipMemcpyHostToDevice));
+  // activity of the row strips (per pass): bit sets over the grid block rows per 128-column border tile, and what is derived
+  {
+    GfDevice& d = p->gfd;
+    d.act_words = (g.nbg + 63) / 64;
+    d.n_act_tiles = (g.n_pad - g.Gf) / 128;
+    d.kmask_words = (g.Gf / 16 + 63) / 64;
+    CBA_TRY(d.act.alloc((size_t)d.n_act_tiles * d.act_words));
+    CBA_TRY(d.kmask.alloc((size_t)(g.n_pad / 128) * d.kmask_words));
+    CBA_HIP(hipMemset(d.kmask, 0, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words));
+    CBA_TRY(d.rowmask_dyn.alloc(g.rowmask.size()));
+    CBA_TRY(d.gridrow.alloc(g.gridrow.size()));
+    CBA_HIP(hipMemcpy(d.gridrow, g.gridrow.data(), sizeof(uint64_t) * g.gridrow.size(), hipMemcpyHostToDevice));
+    {
+      const size_t nt = (size_t)d.n_act_tiles;
+      // entries of four ints (tm, tn, K-slab range), eight interleaved per-XCD lists padded to the longest: 4 x 8 x (tiles in up to three
+      // parts each, dealt evenly) is a quarter of this
+      p->gf_tile_list_capacity = (size_t)32 * nt * (nt + 1) + 4096;
+      CBA_TRY(p->gf_tile_list.alloc(p->gf_tile_list_capacity));
+      CBA_TRY(p->gf_tile_list_host.alloc(p->gf_tile_list_capacity));
+    }
+    CBA_TRY(p->gf_kmask_host.alloc((size_t)(g.n_pad / 128) * d.kmask_words));
+    std::memset(p->gf_kmask_host, 0, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words);
+  }
+  return CBA_OK;
+}
+
+// normal equations: the accumulated parts, the system of the elimination order, the solve's buffers and pinned outputs
+static int alloc_system(cba_problem* p) {
+  const Layout& L = p->L;
+  padded_dims(L.dense_dof, &p->n_pad, &p->n_fact);
+  p->Kpad = round_up(L.block_dof > 0 ? L.block_dof : 1, 48);      // a multiple of the dense K slab (16) and of the block-sparse one (12)
+  const size_t bs = L.block_size, nb = L.n_blocks;
+  CBA_TRY(p->Dblk.alloc(nb * bs * bs));
+  CBA_TRY(p->bblk.alloc(nb * bs));
+  CBA_TRY(p->Dinv.alloc(nb * bs * bs));
+  CBA_TRY(p->dinvb.alloc((size_t)p->Kpad));
+  CBA_TRY(p->B.alloc((size_t)p->Kpad * p->n_pad));
+  CBA_TRY(p->Hdd.alloc((size_t)p->n_pad * p->n_pad));
+  CBA_TRY(p->bd.alloc((size_t)p->n_pad));
+  CBA_HIP(hipMemset(p->dinvb, 0, sizeof(double) * (size_t)p->Kpad));
+  CBA_TRY(p->gridfirst ? alloc_gridfirst_system(p) : alloc_posefirst_system(p));
+  CBA_TRY(p->x.alloc((size_t)L.block_dof + p->n_pad));
+  CBA_HIP(hipMemset(p->x, 0, sizeof(double) * ((size_t)L.block_dof + p->n_pad)));
+  CBA_TRY(p->scal.alloc(16));
+  CBA_TRY(p->kmask.alloc((size_t)(p->n_pad / 128) * schur_mask_words(p->Kpad)));
+  if (schur_chunk_count(p->n_pad) > 0) {
+    CBA_TRY(p->chunk_order.alloc((size_t)schur_chunk_count(p->n_pad)));
+    CBA_TRY(p->chunk_order_host.alloc((size_t)schur_chunk_count(p->n_pad)));
+  }
+  CBA_TRY(p->gemv_ws.alloc((size_t)gemv_t_workspace_doubles(p->n_pad)));
+  CBA_TRY(p->status.alloc(2));      // [0] block-inverse status, [1] guard word of the solve (k_solve_status)
+  CBA_TRY(p->pin_status.alloc(4));
+  CBA_TRY(p->pin_cost.alloc(16));
+  return CBA_OK;
+}
+
+// reduce buffer of the multi-rank paths: the caller's cba_config.reduce_buffer or an owned one (+ the receive buffer of the
+// distributed solve)
+static int alloc_reduce_buffer(cba_problem* p, const cba_config* config) {
+  if (!config->allreduce) return CBA_OK;
+  // the reduced system crosses ranks as its upper 128-row blocks only (half the all-reduce volume); grid-first: the shared blocks
+  int64_t need = p->gf_sharded ? p->gfs.doubles : packed_upper_doubles(p->n_pad);
+  if (config->distributed_solve) {       // staging of the reduce-scatter / all-gathers (send: P, receive: P2)
+    need = (int64_t)ldlt_dist_buffer_doubles(p->n_pad, config->world_size);
+    p->dist_buf_doubles = (size_t)need;
+    CBA_TRY(p->P2.alloc((size_t)need));
+  }
+  if (config->reduce_buffer) {
+    if (config->reduce_buffer_doubles < need) { set_error("reduce_buffer too small"); return CBA_ERR_ARG; }
+    p->P = static_cast<double*>(config->reduce_buffer);
+  } else {
+    CBA_TRY(p->P_own.alloc((size_t)need));
+    p->P = p->P_own;
+  }
+  p->P_cap = config->reduce_buffer ? config->reduce_buffer_doubles : need;
+  return CBA_OK;
+}
+
+// image sharding with the grid-first order: the imagesets of every rank (the one collective of cba_create; every rank computes
+// the same plan, so all of them get here), the pose rows of all ranks, the all-gather staging, the band columns of the shared blocks
+static int setup_gf_sharding(cba_problem* p) {
+  if (!p->gf_sharded) return CBA_OK;
+  const Layout& L = p->L;
+  const int W = p->gf_world;
+  if (p->P_cap < W) { set_error("reduce_buffer too small"); return CBA_ERR_ARG; }
+  std::vector<double> cnt(W, 0.0);
+  cnt[p->gf_rank] = (double)L.n_images;
+  CBA_HIP(hipMemcpy(p->P, cnt.data(), sizeof(double) * W, hipMemcpyHostToDevice));
+  CBA_TRY(gf_sum(p, W));
+  CBA_HIP(hipMemcpy(cnt.data(), p->P, sizeof(double) * W, hipMemcpyDeviceToHost));
+  p->gf_counts.assign(W, 0); p->gf_offsets.assign(W, 0);
+  int total = 0;
+  for (int r = 0; r < W; ++r) {
+    p->gf_counts[r] = (int)cnt[r]; p->gf_offsets[r] = total; total += p->gf_counts[r];
+    p->gf_max_local = std::max(p->gf_max_local, p->gf_counts[r]);
+  }
+  if (total != p->gf.n_images || p->gf_counts[p->gf_rank] != L.n_images) {
+    set_error("cba_create: grid-first sharding: the imagesets of the ranks do not add up to n_images_global"); return CBA_ERR_ARG;
+  }
+  p->gf_img0 = p->gf_offsets[p->gf_rank];
+  const size_t Ng = (size_t)total, ld = (size_t)p->n_pad;
+  CBA_TRY(p->gDblk.alloc(36 * Ng));
+  CBA_TRY(p->gbblk.alloc(6 * Ng));
+  CBA_TRY(p->gB.alloc(6 * Ng * ld));
+  const GfDevice& d = p->gfd;
+  p->gblk = 2 * (int64_t)d.n_act_tiles * d.act_words + (int64_t)p->gf_max_local * (42 + 6 * (int64_t)ld);
+  CBA_TRY(p->gsend.alloc((size_t)p->gblk));
+  CBA_HIP(hipMemset(p->gsend, 0, sizeof(double) * (size_t)p->gblk));
+  CBA_TRY(p->grecv.alloc((size_t)p->gblk * W));
+  // band position -> engine dense column (the engine's grid order is the plan's elimination order, build_grid_order)
+  std::vector<int> col(p->gfs.ref_col.size());
+  for (size_t k = 0; k < col.size(); ++k) col[k] = p->dense_perm_host[p->gfs.ref_col[k]];
+  CBA_TRY(p->gfs_col.alloc(col.size()));
+  CBA_HIP(hipMemcpy(p->gfs_col, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
+  return CBA_OK;
+}
+
+// LDL^T workspace (the grid-first one has flags for every grid block row), with the problem's solver options
+static int alloc_ldlt_workspace(cba_problem* p) {
+  if (p->gridfirst) CBA_TRY(ldlt_workspace_alloc(p->ldlt, p->gf.n_pad, p->gf.nbg));
+  else CBA_TRY(ldlt_workspace_alloc(p->ldlt, p->n_pad));
+  apply_solver_options(p->ldlt, &p->cfg.solver);
+  return CBA_OK;
+}
+
+// ---- block order of the imagesets (cba_set_observations): refinements of the Z-order `order` ----
+// Grid-first order: the pose columns of F are empty in the grid block rows the imageset does not reach (per-pass activity,
+// k_gf_touch), per 128-column tile = ~21 imagesets.  Imagesets are ordered by the first row of F their control patches touch
+// (under the MEASURED pixels: a heuristic, the activity itself comes from the projected ones), so that the imagesets of a tile
+// start at about the same place of the elimination order and their union stays small.
+static void order_imagesets_gridfirst(cba_problem* p, int64_t n, const float* xy, const int32_t* image_index, const int32_t* camera_index,
+                                      std::vector<int>& order) {
+  const Layout& L = p->L;
+  const GfPlan& g = p->gf;
+  const int W = g.grid_words;
+  std::vector<uint64_t> touched((size_t)L.n_images * W, 0ull);
+  for (int64_t i = 0; i < n; ++i) {
+    const int img = image_index[i], cam = camera_index[i];
+    const cba_camera& cm = p->cams[cam];
+    if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1])) continue;
+    const int per = cm.model_type == CBA_CENTRAL_GENERIC ? 2 : 5;
+    const double gx = 1.0 + (cm.grid_w - 3.0) * (xy[2 * i] - cm.calib_min_x) / (cm.calib_max_x + 1.0 - cm.calib_min_x);      // central_grid.h:150-154
+    const double gy = 1.0 + (cm.grid_h - 3.0) * (xy[2 * i + 1] - cm.calib_min_y) / (cm.calib_max_y + 1.0 - cm.calib_min_y);
+    const int fx = (int)std::floor(gx + 2) - 3, fy = (int)std::floor(gy + 2) - 3;
+    for (int r = 0; r < 4; ++r)
+      for (int q = 0; q < 4; ++q) {
+        const int cx = fx + q, cy = fy + r;
+        if (cx < 0 || cy < 0 || cx >= cm.grid_w || cy >= cm.grid_h) continue;
+        const int e = L.intr_offset[cam] - g.n_rp + per * g.gperm[cam][cx + (size_t)cy * cm.grid_w];
+        const int r0 = g.f_of_grid[e] >> 6, r1 = g.f_of_grid[e + per - 1] >> 6;
+        touched[(size_t)img * W + (r0 >> 6)] |= 1ull << (r0 & 63);
+        touched[(size_t)img * W + (r1 >> 6)] |= 1ull << (r1 & 63);
+      }
+  }
+  std::vector<int> slot_of;
+  gf_order_imagesets(g, touched, L.n_images, g.n_rp + 6 * p->gf_img0, &slot_of);      // (sharding: this rank's slots of the border)
+  for (int i = 0; i < L.n_images; ++i) order[slot_of[i]] = i;
+  // First tile order of the border update, predicted from the same rows (the first solve would otherwise run its tiles in
+  // row-major order: 4.7 instead of 3.5 ms at BASELINE configs[1]): per 128-column tile of the border the union of its imagesets'
+  // rows, closed under the fill of the grid factor; rig / point tiles and the right-hand side's tile reach every row.
+  if (p->gf_tile_list_host) {
+    const int nt = (g.n_pad - g.Gf) / 128;
+    std::vector<uint64_t> tact((size_t)nt * W, 0ull);
+    auto all_rows = [&](int t) { for (int w = 0; w < W; ++w) tact[(size_t)t * W + w] = ~0ull; };
+    for (int t = 0; t < nt && 128 * t < g.n_rp; ++t) all_rows(t);
+    all_rows(nt - 1);
+    if (p->gf_sharded) for (int t = 0; t < nt; ++t) all_rows(t);        // (the other ranks' rows are not known here: dense)
+    for (int i = 0; i < L.n_images; ++i)
+      for (int t : {(g.n_rp + 6 * slot_of[i]) >> 7, (g.n_rp + 6 * slot_of[i] + 5) >> 7})
+        for (int w = 0; w < W; ++w) tact[(size_t)t * W + w] |= touched[(size_t)i * W + w];
+    for (int t = 0; t < nt; ++t) {
+      uint64_t* a = &tact[(size_t)t * W];
+      for (int r = 0; r < g.nbg; ++r)
+        if ((a[r >> 6] >> (r & 63)) & 1ull)
+          for (int w = r >> 6; w < W; ++w) a[w] |= g.gridrow[(size_t)r * W + w];
+      for (int w = 0; w < W; ++w)
+        if (64 * w + 64 > g.nbg) a[w] &= (64 * w >= g.nbg) ? 0ull : (~0ull >> (64 - (g.nbg - 64 * w)));
+    }
+    gf_build_tile_list(p, nt, g.Gf / 16, [&](int tm, int tn) {
+      int rows = 0;
+      for (int w = 0; w < W; ++w) rows += __builtin_popcountll(tact[(size_t)tm * W + w] & tact[(size_t)tn * W + w]);
+      return 4 * rows;                                   // K slabs of 16 rows: four per block row
+    }, [&](int tm, int tn, int target) {
+      int seen = 0;
+      for (int r = 0; r < g.nbg; ++r)
+        if (((tact[(size_t)tm * W + (r >> 6)] & tact[(size_t)tn * W + (r >> 6)]) >> (r & 63)) & 1ull) {
+          if (seen + 4 > target) return 4 * r;
+          seen += 4;
+        }
+      return 0;
+    });
+    p->gf_tile_list_age = 0;
+  }
+}
+
+// Round 5: refine that order into a nearest-neighbour chain on the imagesets' FOOTPRINTS in the Schur product's own units.  What the
+// block-sparse K loop of the product executes is, per pair of 128-column tiles, the 16-row slabs (2.7 imagesets) whose rows are
+// non-zero in both tiles -- so the cost of an order is how much the tile sets of neighbouring imagesets differ, and the Z-order of the
+// footprint CENTRES only approximates that (footprints differ in size and shape).  Tile set of an imageset = the tiles of its points'
+// columns and of the 4 x 4 control patches under its measured pixels (the engine's tiled grid order, build_grid_order); chain: start
+// at the head of the Z-order, always append the unplaced imageset whose tile set has the smallest Hamming distance to the last one.
+// Executed slabs of the product, modelled from the observation lists: x 0.86 (cfg 2), 0.85 (cfg 4), 0.83 (cfg 3) against the
+// Z-order; measured: profiles/r05_schur_row_order.txt.  The order is internal (x and the dumps are un-permuted); the sum over the
+// pose blocks is taken in another order, which moves S by rounding only.  O(N^2 T / 64): skipped above 8192 imagesets.
+static void order_imagesets_chain(const cba_problem* p, int64_t n, const float* xy, const int32_t* point_index, const int32_t* image_index,
+                                  const int32_t* camera_index, std::vector<int>& order) {
+  const Layout& L = p->L;
+  const int T = (L.dense_dof + 127) / 128, W = (T + 63) / 64;
+  std::vector<unsigned long long> mask((size_t)L.n_images * W, 0ull);
+  auto set_col = [&](int img, int col) { if (col >= 0 && col < L.dense_dof) { const int t = col >> 7; mask[(size_t)img * W + (t >> 6)] |= 1ull << (t & 63); } };
+  for (int64_t i = 0; i < n; ++i) {
+    const int img = image_index[i], cam = camera_index[i];
+    const int pc = L.first_points - L.block_dof + 3 * point_index[i];
+    set_col(img, pc); set_col(img, pc + 2);
+    if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1])) continue;      // (the cast below is undefined for a non-finite pixel)
+    const cba_camera& cm = p->cams[cam];
+    const int per = cm.model_type == CBA_CENTRAL_GENERIC ? 2 : 5;
+    const double gx = 1.0 + (cm.grid_w - 3.0) * (xy[2 * i] - cm.calib_min_x) / (cm.calib_max_x + 1.0 - cm.calib_min_x);      // central_grid.h:150-154
+    const double gy = 1.0 + (cm.grid_h - 3.0) * (xy[2 * i + 1] - cm.calib_min_y) / (cm.calib_max_y + 1.0 - cm.calib_min_y);
+    const int fx = (int)std::floor(gx + 2) - 3, fy = (int)std::floor(gy + 2) - 3;
+    for (int r = 0; r < 4; ++r)
+      for (int q = 0; q < 4; ++q) {
+        const int cx = fx + q, cy = fy + r;
+        if (cx < 0 || cy < 0 || cx >= cm.grid_w || cy >= cm.grid_h) continue;
+        const int first = L.intr_offset[cam] + per * (cx + cy * cm.grid_w);
+        set_col(img, p->dense_perm_host[first]); set_col(img, p->dense_perm_host[first + per - 1]);
+      }
+  }
+  std::vector<int> chain; chain.reserve(L.n_images);
+  std::vector<char> placed(L.n_images, 0);
+  int cur = order[0];
+  chain.push_back(cur); placed[cur] = 1;
+  for (int step = 1; step < L.n_images; ++step) {
+    const unsigned long long* mc = &mask[(size_t)cur * W];
+    int best = -1, best_d = 0x7fffffff;
+    for (int r = 0; r < L.n_images; ++r) {                 // candidates in Z-order: ties go to the Z-order neighbour
+      const int v = order[r];
+      if (placed[v]) continue;
+      const unsigned long long* mv = &mask[(size_t)v * W];
+      int d = 0;
+      for (int w = 0; w < W; ++w) d += __builtin_popcountll(mc[w] ^ mv[w]);
+      if (d < best_d) { best_d = d; best = v; }
+    }
+    cur = best; chain.push_back(cur); placed[cur] = 1;
+  }
+  order.swap(chain);
+}
+
 }  // namespace cba
 
 // =================================================================================================
@@ -897,327 +1306,36 @@ int cba_prepare_device(int32_t device) {
 }
 
 int cba_create(const cba_config* config, cba_problem** out) {
-  if (!config || !out || !config->cameras || config->n_cameras < 1 || config->n_cameras > kMaxCameras ||
-      config->n_images < 0 || config->n_points < 0 || !(config->numerical_diff_delta > 0)) {
-    set_error("cba_create: bad config"); return CBA_ERR_ARG;
-  }
-  for (int c = 0; c < config->n_cameras; ++c)
-    if (!camera_ok(config->cameras[c])) { set_error("cba_create: bad camera"); return CBA_ERR_ARG; }
-  if (config->allreduce && config->eliminate_points) { set_error("image sharding requires eliminate_points = 0"); return CBA_ERR_UNSUPPORTED; }
-  if (config->distributed_solve) {
-    // the distributed factorisation walks the column groups by rank: an invalid rank would loop for ever or leave groups unowned
-    if (!config->allreduce) { set_error("cba_create: distributed_solve needs an allreduce callback"); return CBA_ERR_ARG; }
-    if (config->world_size < 1 || config->rank < 0 || config->rank >= config->world_size) {
-      set_error("cba_create: distributed_solve needs 0 <= rank < world_size"); return CBA_ERR_ARG;
-    }
-  }
+  if (!out) { set_error("cba_create: bad config"); return CBA_ERR_ARG; }
+  CBA_TRY(check_config(config));
   setenv("GPU_MAX_HW_QUEUES", "8", /*overwrite=*/0);   // read by the HIP runtime when it initialises (see cba_problem)
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available (the engine has no CPU fallback)"); return CBA_ERR_HIP; }
   if (config->device < 0 || config->device >= ndev) { set_error("cba_create: bad device ordinal"); return CBA_ERR_ARG; }
   CBA_HIP(hipSetDevice(config->device));
-  cba_problem* p = new cba_problem();
   // every early return below destroys the half-built problem (device memory, events); released on success
-  struct Guard { cba_problem* q; ~Guard() { if (q) cba_destroy(q); } } guard{p};
+  std::unique_ptr<cba_problem, decltype(&cba_destroy)> p(new cba_problem(), &cba_destroy);
   p->cfg = *config;
   p->cams.assign(config->cameras, config->cameras + config->n_cameras);
   p->cfg.cameras = p->cams.data();
   p->device = config->device;
   make_layout(p->cfg, p->L);
-  const Layout& L = p->L;
-  if (L.total_dof <= 0) { set_error("empty problem"); return CBA_ERR_ARG; }
+  if (p->L.total_dof <= 0) { set_error("empty problem"); return CBA_ERR_ARG; }
   CBA_TRY(make_main_stream(&p->stream));
-  CBA_HIP(hipEventCreateWithFlags(&p->ev_aux0, hipEventDisableTiming));
-  CBA_HIP(hipEventCreateWithFlags(&p->ev_aux1, hipEventDisableTiming));
-  CBA_HIP(hipEventCreateWithFlags(&p->ev_aux2, hipEventDisableTiming));
-  CBA_HIP(hipEventCreateWithFlags(&p->ev_clear, hipEventDisableTiming));
-  CBA_HIP(hipEventCreateWithFlags(&p->ev_mask, hipEventDisableTiming));
-  CBA_TRY(dev_alloc(&p->slow_count, 1));
-  CBA_HIP(hipMemset(p->slow_count, 0, sizeof(int)));
-  for (int c = 0; c < L.n_cameras; ++c) p->model_mask |= (p->cams[c].model_type == CBA_CENTRAL_GENERIC) ? 1 : 2;
-  const int maxKg = L.localize_only ? 0 : ((p->model_mask & 2) ? 80 : 32);
-  p->tasks_per_obs = 3 + maxKg;
-  p->rec_doubles = kRecHeader + 2 * maxKg;
-  CBA_TRY(alloc_state(p, p->st[0]));
-  CBA_TRY(alloc_state(p, p->st[1]));
-  CBA_TRY(dev_alloc(&p->itg, 16 * (size_t)L.n_images * L.n_cameras));
-  for (int c = 0; c < L.n_cameras; ++c) CBA_TRY(dev_alloc(&p->tangents[c], 6 * (size_t)p->cams[c].grid_w * p->cams[c].grid_h));
-  {
-    // elimination order (cba_solver_options.elimination)
-    // image sharding: the plan covers the imagesets of all ranks (the border is [rig | points | poses of every rank])
-    const bool sharded = config->allreduce != nullptr;
-    const int n_glob = (sharded && config->n_images_global > 0) ? config->n_images_global : L.n_images;
-    const bool eligible = !L.eliminate_points && !L.localize_only && n_glob > 0 && (sharded || L.n_images > 0);
-    const int want = config->solver.elimination;
-    if (want == 2 && !eligible) { set_error("cba_create: the grid-first elimination order needs eliminate_points = 0 and localize_only = 0"); return CBA_ERR_UNSUPPORTED; }
-    if (want == 2 && sharded && config->distributed_solve) { set_error("cba_create: the grid-first elimination order has no distributed factorisation (distributed_solve = 1)"); return CBA_ERR_UNSUPPORTED; }
-    if (want < 0 || want > 2 || config->solver.grid_strips < 0) { set_error("cba_create: bad solver options"); return CBA_ERR_ARG; }
-    if (want == 2 && sharded && (config->world_size < 1 || config->rank < 0 || config->rank >= config->world_size)) {
-      set_error("cba_create: grid-first sharding needs 0 <= rank < world_size"); return CBA_ERR_ARG;
-    }
-    bool use = want == 2;
-    if (want == 0 && eligible && !sharded) {
-      double pf = 0, gfl = 0;
-      gf_flop_model(p->cams.data(), L.n_cameras, L.n_images, L.n_points, &pf, &gfl);
-      int G = 0;
-      for (int c = 0; c < L.n_cameras; ++c) G += (p->cams[c].model_type == CBA_CENTRAL_GENERIC ? 2 : 5) * p->cams[c].grid_w * p->cams[c].grid_h;
-      use = G >= 2048 && gfl < 0.85 * pf;
-    }
-    if (use) {
-      if (gf_build_plan(p->cams.data(), L.n_cameras, n_glob, L.n_points, config->solver.grid_strips, config->solver.grid_single_tile_tasks, &p->gf) != CBA_OK) { set_error("cba_create: grid-first plan failed"); return CBA_ERR_ARG; }
-      p->gridfirst = true;
-      if (sharded) {
-        // limits of the launches, checked here rather than at the first pass: activity words of k_gf_touch (1024 grid block
-        // rows), its LDS bit sets, the control words of the block-sparse launch, 32-bit offsets inside the sections of k_gf_shared
-        const GfPlan& g = p->gf;
-        const int64_t words = (g.nbg + 63) / 64, touch_lds = 8 * words * ((g.n_pad - g.Gf) / 128);
-        gf_shared_layout(p->cams.data(), L.n_cameras, L.n_points, &p->gfs);
-        int64_t band_max = 0;
-        for (int c = 0; c < L.n_cameras; ++c) band_max = std::max(band_max, p->gfs.band_off[c + 1] - p->gfs.band_off[c]);
-        if (g.nbg > 1024) { set_error("cba_create: grid-first sharding: more than 1024 grid block rows"); return CBA_ERR_UNSUPPORTED; }
-        if (touch_lds > 65536) { set_error("cba_create: grid-first sharding: the activity bit sets of the border need more than 64 KB of LDS"); return CBA_ERR_UNSUPPORTED; }
-        if ((int)g.chains.size() > ldlt_gridfirst_max_chains()) { set_error("cba_create: grid-first sharding: more pivot chains than the block-sparse launch has control words for"); return CBA_ERR_UNSUPPORTED; }
-        if (band_max >= INT32_MAX || (int64_t)p->gfs.n_rp * p->gfs.G >= INT32_MAX) { set_error("cba_create: grid-first sharding: shared blocks too large"); return CBA_ERR_UNSUPPORTED; }
-        p->gf_sharded = true;
-        p->gf_rank = config->rank; p->gf_world = config->world_size;
-      }
-    }
-  }
-  CBA_TRY(build_grid_order(p));
-  CBA_TRY(dev_alloc(&p->cams_dev[0], L.n_cameras));
-  CBA_TRY(dev_alloc(&p->cams_dev[1], L.n_cameras));
-  CBA_TRY(upload_camdevs(p, 0));
-  CBA_TRY(upload_camdevs(p, 1));
-  // pair tables (upper-triangle (row,col) pairs) for the two column-count classes
-  {
-    const size_t stride = (size_t)kMaxCols * (kMaxCols + 1) / 2;
-    std::vector<uint32_t> tab(2 * stride, 0);
-    int counts[2] = {0, 0};
-    for (int slot = 0; slot < 2; ++slot) {
-      int Kg = L.localize_only ? 0 : (slot == 0 ? 32 : 80);
-      int K = 6 + (L.rig_in_state ? 6 : 0) + 3 + Kg;
-      // pairs with both columns in the pose/rig ("hot") range are accumulated in registers by the kernel
-      const int nh = 6 + (L.rig_in_state ? 6 : 0), h0 = L.eliminate_points ? 3 : 0;
-      int e = 0;
-      for (int i = 0; i < K; ++i)
-        for (int k = i; k < K; ++k) {
-          const bool hot = i >= h0 && i < h0 + nh && k >= h0 && k < h0 + nh;
-          const bool grid_grid = i >= K - Kg && k >= K - Kg;   // summed per grid cell by k_accumulate_cells
-          // pose x (point | grid) goes through k_accumulate_strips when the poses are the Schur blocks
-          const bool strip = !L.eliminate_points && i < 6 && k >= nh;
-          // rig pose x grid is summed per grid cell by k_accumulate_cells as well (several cameras, poses eliminated)
-          const bool rig_grid = !L.eliminate_points && L.rig_in_state && i >= 6 && i < 12 && k >= K - Kg;
-          // every pair with a point column is summed per pattern point by k_accumulate_points (poses eliminated)
-          const bool point = !L.eliminate_points && ((i >= nh && i < nh + 3) || (k >= nh && k < nh + 3));
-          if (!hot && !grid_grid && !strip && !rig_grid && !point) tab[slot * stride + e++] = ((uint32_t)i << 16) | (uint32_t)k;
-        }
-      counts[slot] = e;
-    }
-    CBA_TRY(dev_alloc(&p->pair_tables, tab.size()));
-    CBA_TRY(dev_alloc(&p->pair_counts, 2));
-    CBA_HIP(hipMemcpy(p->pair_tables, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    CBA_HIP(hipMemcpy(p->pair_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
-  }
-  {
-    p->cell_base_host.assign(L.n_cameras + 1, 0);
-    for (int c = 0; c < L.n_cameras; ++c) p->cell_base_host[c + 1] = p->cell_base_host[c] + p->cams[c].grid_w * p->cams[c].grid_h;
-    const size_t nk = (size_t)p->cell_base_host.back();
-    CBA_TRY(dev_alloc(&p->cell_base, p->cell_base_host.size()));
-    CBA_HIP(hipMemcpy(p->cell_base, p->cell_base_host.data(), sizeof(int) * p->cell_base_host.size(), hipMemcpyHostToDevice));
-    CBA_TRY(dev_alloc(&p->cell_count, nk + 1)); CBA_TRY(dev_alloc(&p->cell_start, nk + 1)); CBA_TRY(dev_alloc(&p->cell_fill, nk + 1));
-  }
-  CBA_TRY(dev_alloc(&p->det_bits, 2)); CBA_TRY(dev_alloc(&p->det_scale, 2));
-  CBA_TRY(dev_alloc(&p->fd_redo_count, 4));
-  CBA_HIP(hipMemset(p->fd_redo_count, 0, sizeof(int) * 4));
-  CBA_TRY(dev_alloc(&p->red_partials, 256 * 8));
-  CBA_TRY(dev_alloc(&p->red8, 16));
-  // normal equations
-  padded_dims(L.dense_dof, &p->n_pad, &p->n_fact);
-  p->Kpad = round_up(L.block_dof > 0 ? L.block_dof : 1, 48);      // a multiple of the dense K slab (16) and of the block-sparse one (12)
-  const size_t bs = L.block_size, nb = L.n_blocks;
-  CBA_TRY(dev_alloc(&p->Dblk, nb * bs * bs));
-  CBA_TRY(dev_alloc(&p->bblk, nb * bs));
-  CBA_TRY(dev_alloc(&p->Dinv, nb * bs * bs));
-  CBA_TRY(dev_alloc(&p->dinvb, (size_t)p->Kpad));
-  CBA_TRY(dev_alloc(&p->B, (size_t)p->Kpad * p->n_pad));
-  CBA_TRY(dev_alloc(&p->Hdd, (size_t)p->n_pad * p->n_pad));
-  CBA_TRY(dev_alloc(&p->bd, (size_t)p->n_pad));
-  if (p->gridfirst) {
-    const GfPlan& g = p->gf;
-    const size_t nf = (size_t)g.n_pad, wb = (size_t)(g.n_pad - g.Gf);
-    CBA_TRY(dev_alloc(&p->F, nf * nf));
-    CBA_HIP(hipMemset(p->F, 0, sizeof(double) * nf * nf));          // tiles outside the plan's structure stay zero for ever
-    CBA_TRY(dev_alloc(&p->Xb, (size_t)g.Gf * wb));
-    CBA_HIP(hipMemset(p->Xb, 0, sizeof(double) * (size_t)g.Gf * wb));
-    CBA_TRY(dev_alloc(&p->xF, nf));
-    CBA_TRY(dev_alloc(&p->gfd.tasks, g.tasks.size()));
-    CBA_TRY(dev_alloc(&p->gfd.ivals, g.ivals.size()));
-    CBA_TRY(dev_alloc(&p->gfd.chains, g.chains.size()));
-    CBA_TRY(dev_alloc(&p->gfd.rowmask, g.rowmask.size()));
-    CBA_HIP(hipMemcpy(p->gfd.tasks, g.tasks.data(), sizeof(GfTask) * g.tasks.size(), hipMemcpyHostToDevice));
-    CBA_HIP(hipMemcpy(p->gfd.ivals, g.ivals.data(), sizeof(GfIval) * g.ivals.size(), hipMemcpyHostToDevice));
-    CBA_HIP(hipMemcpy(p->gfd.chains, g.chains.data(), sizeof(GfChain) * g.chains.size(), hipMemcpyHostToDevice));
-    CBA_HIP(hipMemcpy(p->gfd.rowmask, g.rowmask.data(), sizeof(uint64_t) * g.rowmask.size(), hipMemcpyHostToDevice));
-    p->gfd.n_tasks0 = g.n_tasks0; p->gfd.n_tasks1 = (int)g.tasks.size() - g.n_tasks0; p->gfd.n_chains = (int)g.chains.size();
-    p->gfd.nbg = g.nbg; p->gfd.nbf = g.nbf; p->gfd.mask_words = g.mask_words; p->gfd.flops_grid = g.flops_grid;
-    // tiles the forming kernel writes per attempt: the structural tiles of the grid x grid part, the row strips of the grid rows
-    // (every border column block + the right-hand side's), the upper triangle of the border
-    // Rule: every tile that any launch of a solve WRITES is formed again for the next attempt (a broken solve -- zero pivot, NaN --
-    // must not leave anything behind: tests/test_gpu_gridfirst.py).  The dense border launch and the border update also write the
-    // padding-only block columns and the block rows behind the factored ones.
-    std::vector<int> tiles(g.grid_tiles);
-    for (int r = 0; r < g.nbg; ++r) {
-      for (int c = g.nbg; c < g.nbf; ++c) { tiles.push_back(r); tiles.push_back(c); }
-      tiles.push_back(r); tiles.push_back(g.ntc - 1);
-    }
-    for (int r = g.nbg; r < g.ntc; ++r)
-      for (int c = r; c < g.ntc; ++c) { tiles.push_back(r); tiles.push_back(c); }
-    p->n_gf_tiles = (int)(tiles.size() / 2);
-    CBA_TRY(dev_alloc(&p->gf_tiles, tiles.size()));
-    CBA_HIP(hipMemcpy(p->gf_tiles, tiles.data(), sizeof(int) * tiles.size(), hipMemcpyHostToDevice));
-    CBA_TRY(dev_alloc(&p->gf_grid_of_f, g.grid_of_f.size()));
-    CBA_HIP(hipMemcpy(p->gf_grid_of_f, g.grid_of_f.data(), sizeof(int) * g.grid_of_f.size(), hipMemcpyHostToDevice));
-    CBA_TRY(dev_alloc(&p->gf_f_of_grid, g.f_of_grid.size()));
-    CBA_HIP(hipMemcpy(p->gf_f_of_grid, g.f_of_grid.data(), sizeof(int) * g.f_of_grid.size(), hipMemcpyHostToDevice));
-    // activity of the row strips (per pass): bit sets over the grid block rows per 128-column border tile, and what is derived
-    {
-      GfDevice& d = p->gfd;
-      d.act_words = (g.nbg + 63) / 64;
-      d.n_act_tiles = (g.n_pad - g.Gf) / 128;
-      d.kmask_words = (g.Gf / 16 + 63) / 64;
-      CBA_TRY(dev_alloc(&d.act, (size_t)d.n_act_tiles * d.act_words));
-      CBA_TRY(dev_alloc(&d.kmask, (size_t)(g.n_pad / 128) * d.kmask_words));
-      CBA_HIP(hipMemset(d.kmask, 0, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words));
-      CBA_TRY(dev_alloc(&d.rowmask_dyn, g.rowmask.size()));
-      CBA_TRY(dev_alloc(&d.gridrow, g.gridrow.size()));
-      CBA_HIP(hipMemcpy(d.gridrow, g.gridrow.data(), sizeof(uint64_t) * g.gridrow.size(), hipMemcpyHostToDevice));
-      {
-        const size_t nt = (size_t)d.n_act_tiles;
-        // entries of four ints (tm, tn, K-slab range), eight interleaved per-XCD lists padded to the longest: 4 x 8 x (tiles in up to three
-        // parts each, dealt evenly) is a quarter of this
-        p->gf_tile_list_capacity = (size_t)32 * nt * (nt + 1) + 4096;
-        CBA_TRY(dev_alloc(&p->gf_tile_list, p->gf_tile_list_capacity));
-        CBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->gf_tile_list_host), sizeof(int) * p->gf_tile_list_capacity));
-      }
-      CBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->gf_kmask_host), sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words));
-      std::memset(p->gf_kmask_host, 0, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words);
-    }
-  } else {
-    CBA_TRY(dev_alloc(&p->W, (size_t)p->Kpad * p->n_pad));
-    CBA_TRY(dev_alloc(&p->S, (size_t)p->n_pad * p->n_pad));
-  }
-  if (config->allreduce) {
-    // the reduced system crosses ranks as its upper 128-row blocks only (half the all-reduce volume); grid-first: the shared blocks
-    int64_t need = p->gf_sharded ? p->gfs.doubles : packed_upper_doubles(p->n_pad);
-    if (config->distributed_solve) {       // staging of the reduce-scatter / all-gathers (send: P, receive: P2)
-      need = (int64_t)ldlt_dist_buffer_doubles(p->n_pad, config->world_size);
-      p->dist_buf_doubles = (size_t)need;
-      CBA_TRY(dev_alloc(&p->P2, (size_t)need));
-    }
-    if (config->reduce_buffer) {
-      if (config->reduce_buffer_doubles < need) { set_error("reduce_buffer too small"); return CBA_ERR_ARG; }
-      p->P = static_cast<double*>(config->reduce_buffer); p->P_owned = false;
-    } else {
-      CBA_TRY(dev_alloc(&p->P, (size_t)need));
-    }
-    p->P_cap = config->reduce_buffer ? config->reduce_buffer_doubles : need;
-  }
-  if (p->gf_sharded) {
-    // imagesets of every rank (the one collective of cba_create; every rank computes the same plan, so all of them get here)
-    const int W = p->gf_world;
-    if (p->P_cap < W) { set_error("reduce_buffer too small"); return CBA_ERR_ARG; }
-    std::vector<double> cnt(W, 0.0);
-    cnt[p->gf_rank] = (double)L.n_images;
-    CBA_HIP(hipMemcpy(p->P, cnt.data(), sizeof(double) * W, hipMemcpyHostToDevice));
-    CBA_TRY(gf_sum(p, W));
-    CBA_HIP(hipMemcpy(cnt.data(), p->P, sizeof(double) * W, hipMemcpyDeviceToHost));
-    p->gf_counts.assign(W, 0); p->gf_offsets.assign(W, 0);
-    int total = 0;
-    for (int r = 0; r < W; ++r) {
-      p->gf_counts[r] = (int)cnt[r]; p->gf_offsets[r] = total; total += p->gf_counts[r];
-      p->gf_max_local = std::max(p->gf_max_local, p->gf_counts[r]);
-    }
-    if (total != p->gf.n_images || p->gf_counts[p->gf_rank] != L.n_images) {
-      set_error("cba_create: grid-first sharding: the imagesets of the ranks do not add up to n_images_global"); return CBA_ERR_ARG;
-    }
-    p->gf_img0 = p->gf_offsets[p->gf_rank];
-    const size_t Ng = (size_t)total, ld = (size_t)p->n_pad;
-    CBA_TRY(dev_alloc(&p->gDblk, 36 * Ng));
-    CBA_TRY(dev_alloc(&p->gbblk, 6 * Ng));
-    CBA_TRY(dev_alloc(&p->gB, 6 * Ng * ld));
-    const GfDevice& d = p->gfd;
-    p->gblk = 2 * (int64_t)d.n_act_tiles * d.act_words + (int64_t)p->gf_max_local * (42 + 6 * (int64_t)ld);
-    CBA_TRY(dev_alloc(&p->gsend, (size_t)p->gblk));
-    CBA_HIP(hipMemset(p->gsend, 0, sizeof(double) * (size_t)p->gblk));
-    CBA_TRY(dev_alloc(&p->grecv, (size_t)p->gblk * W));
-    // band position -> engine dense column (the engine's grid order is the plan's elimination order, build_grid_order)
-    std::vector<int> col(p->gfs.ref_col.size());
-    for (size_t k = 0; k < col.size(); ++k) col[k] = p->dense_perm_host[p->gfs.ref_col[k]];
-    CBA_TRY(dev_alloc(&p->gfs_col, col.size()));
-    CBA_HIP(hipMemcpy(p->gfs_col, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
-  }
-  if (p->S) CBA_HIP(hipMemset(p->S, 0, sizeof(double) * (size_t)p->n_pad * p->n_pad));
-  if (p->W) CBA_HIP(hipMemset(p->W, 0, sizeof(double) * (size_t)p->Kpad * p->n_pad));
-  CBA_HIP(hipMemset(p->dinvb, 0, sizeof(double) * (size_t)p->Kpad));
-  CBA_TRY(dev_alloc(&p->x, (size_t)L.block_dof + p->n_pad));
-  CBA_HIP(hipMemset(p->x, 0, sizeof(double) * ((size_t)L.block_dof + p->n_pad)));
-  CBA_TRY(dev_alloc(&p->scal, 16));
-  CBA_TRY(dev_alloc(&p->kmask, (size_t)(p->n_pad / 128) * schur_mask_words(p->Kpad)));
-  if (schur_chunk_count(p->n_pad) > 0) {
-    CBA_TRY(dev_alloc(&p->chunk_order, (size_t)schur_chunk_count(p->n_pad)));
-    CBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->chunk_order_host), sizeof(int) * (size_t)schur_chunk_count(p->n_pad)));
-  }
-  CBA_TRY(dev_alloc(&p->gemv_ws, (size_t)gemv_t_workspace_doubles(p->n_pad)));
-  CBA_TRY(dev_alloc(&p->status, 2));      // [0] block-inverse status, [1] guard word of the solve (k_solve_status)
-  if (p->gridfirst) CBA_TRY(ldlt_workspace_alloc(p->ldlt, p->gf.n_pad, p->gf.nbg));
-  else CBA_TRY(ldlt_workspace_alloc(p->ldlt, p->n_pad));
-  apply_solver_options(p->ldlt, &config->solver);
-  guard.q = nullptr;
-  *out = p;
+  CBA_TRY(choose_elimination_order(p.get(), config));
+  CBA_TRY(alloc_pass_buffers(p.get()));
+  CBA_TRY(alloc_system(p.get()));
+  CBA_TRY(alloc_reduce_buffer(p.get(), config));
+  CBA_TRY(setup_gf_sharding(p.get()));
+  CBA_TRY(alloc_ldlt_workspace(p.get()));
+  *out = p.release();
   return CBA_OK;
 }
 
 void cba_destroy(cba_problem* p) {
   if (!p) return;
-  hipSetDevice(p->device);
+  hipSetDevice(p->device);          // current while the members free their device memory and events
   if (p->stream) hipStreamSynchronize(p->stream);
-  auto F = [](void* q) { if (q) hipFree(q); };
-  F(p->obs_xy); F(p->obs_point); F(p->obs_image); F(p->obs_camera); F(p->last_projection);
-  for (int s = 0; s < 2; ++s) {
-    F(p->st[s].rig_tr_global); F(p->st[s].camera_tr_rig); F(p->st[s].points);
-    for (int c = 0; c < kMaxCameras; ++c) F(p->st[s].grids[c]);
-    F(p->cams_dev[s]);
-  }
-  F(p->itg);
-  for (int c = 0; c < kMaxCameras; ++c) { F(p->tangents[c]); F(p->gperm[c]); }
-  F(p->cost_ref); F(p->cost_test); F(p->pixels); F(p->flags); F(p->fd_out); F(p->fd_ok); F(p->jrec); F(p->cells);
-  F(p->pair_tables); F(p->pair_counts); F(p->pt_start); F(p->pt_obs); F(p->red_partials); F(p->red8);
-  F(p->cell_base); F(p->cell_count); F(p->cell_start); F(p->cell_fill); F(p->cell_order); F(p->pose_slot);
-  F(p->Dblk); F(p->bblk); F(p->B); F(p->Hdd); F(p->bd); F(p->Dinv); F(p->dinvb); F(p->W);
-  if (p->S_owned) F(p->S);
-  if (p->P_owned) F(p->P);
-  F(p->P2);
-  F(p->x); F(p->scal); F(p->status); F(p->gemv_ws); F(p->kmask);
-  F(p->F); F(p->Xb); F(p->xF); F(p->gf_tiles); F(p->gf_grid_of_f); F(p->gf_f_of_grid);
-  F(p->gfs_col); F(p->gDblk); F(p->gbblk); F(p->gB); F(p->gsend); F(p->grecv);
-  F(p->gfd.tasks); F(p->gfd.ivals); F(p->gfd.chains); F(p->gfd.rowmask);
-  F(p->gfd.act); F(p->gfd.gridrow); F(p->gfd.kmask); F(p->gfd.rowmask_dyn);
-  if (p->gf_kmask_host) hipHostFree(p->gf_kmask_host);
-  F(p->gf_tile_list);
-  if (p->gf_tile_list_host) hipHostFree(p->gf_tile_list_host);
-  ldlt_workspace_free(p->ldlt);
-  for (auto& t : p->timers) for (auto& sp : t.spans) { hipEventDestroy(sp.e0); hipEventDestroy(sp.e1); }
-  if (p->kmask_host) hipHostFree(p->kmask_host);
-  if (p->chunk_order_host) hipHostFree(p->chunk_order_host);
-  if (p->chunk_order) hipFree(p->chunk_order);
-  F(p->slow_skip); F(p->fd_slow); F(p->slow_list); F(p->slow_count); F(p->img_start); F(p->band_mask); F(p->det_bits); F(p->det_scale); F(p->fd_redo[0]); F(p->fd_redo[1]); F(p->fd_redo_count);
-  if (p->ev_aux0) hipEventDestroy(p->ev_aux0);
-  if (p->ev_aux1) hipEventDestroy(p->ev_aux1);
-  if (p->ev_aux2) hipEventDestroy(p->ev_aux2);
-  if (p->ev_clear) hipEventDestroy(p->ev_clear);
-  if (p->ev_mask) hipEventDestroy(p->ev_mask);
-  if (p->pin_status) hipHostFree(p->pin_status);
-  if (p->pin_cost) hipHostFree(p->pin_cost);
   delete p;
 }
 
@@ -1234,38 +1352,35 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
     prev = key;
   }
   CBA_HIP(hipSetDevice(p->device));
-  auto F = [](void* q) { if (q) hipFree(q); };
-  F(p->obs_xy); F(p->obs_point); F(p->obs_image); F(p->obs_camera); F(p->last_projection);
-  F(p->cost_ref); F(p->cost_test); F(p->pixels); F(p->flags); F(p->fd_out); F(p->fd_ok); F(p->jrec); F(p->cells); F(p->cell_order);
+  // no observations until the upload below is complete: after a failed re-upload cba_step returns CBA_ERR_STATE
+  p->have_obs = false; p->have_system = false;
   p->n_obs = n;
-  CBA_TRY(dev_alloc(&p->obs_xy, 2 * (size_t)n)); CBA_TRY(dev_alloc(&p->obs_point, (size_t)n));
-  CBA_TRY(dev_alloc(&p->obs_image, (size_t)n)); CBA_TRY(dev_alloc(&p->obs_camera, (size_t)n));
-  CBA_TRY(dev_alloc(&p->last_projection, 2 * (size_t)n));
-  CBA_TRY(dev_alloc(&p->cost_ref, (size_t)n)); CBA_TRY(dev_alloc(&p->cost_test, (size_t)n));
-  CBA_TRY(dev_alloc(&p->pixels, 2 * (size_t)n)); CBA_TRY(dev_alloc(&p->flags, (size_t)n));
-  CBA_TRY(dev_alloc(&p->fd_out, 2 * (size_t)n * p->tasks_per_obs)); CBA_TRY(dev_alloc(&p->fd_ok, (size_t)n * p->tasks_per_obs));
-  CBA_TRY(dev_alloc(&p->jrec, (size_t)n * p->rec_doubles)); CBA_TRY(dev_alloc(&p->cells, 2 * (size_t)n));
+  CBA_TRY(p->obs_xy.alloc(2 * (size_t)n)); CBA_TRY(p->obs_point.alloc((size_t)n));
+  CBA_TRY(p->obs_image.alloc((size_t)n)); CBA_TRY(p->obs_camera.alloc((size_t)n));
+  CBA_TRY(p->last_projection.alloc(2 * (size_t)n));
+  CBA_TRY(p->cost_ref.alloc((size_t)n)); CBA_TRY(p->cost_test.alloc((size_t)n));
+  CBA_TRY(p->pixels.alloc(2 * (size_t)n)); CBA_TRY(p->flags.alloc((size_t)n));
+  CBA_TRY(p->fd_out.alloc(2 * (size_t)n * p->tasks_per_obs)); CBA_TRY(p->fd_ok.alloc((size_t)n * p->tasks_per_obs));
+  CBA_TRY(p->jrec.alloc((size_t)n * p->rec_doubles)); CBA_TRY(p->cells.alloc(2 * (size_t)n));
   {
     // gather-path follow-up lists of the finite-difference kernel: a quarter of all tasks (the share of tasks whose iterate
     // crosses a cell boundary is a few per cent) + 65 536
     const size_t cap = (size_t)n * p->tasks_per_obs / 4 + 65536;
     p->fd_redo_cap = (int)(cap > 0x7fffff00u ? 0x7fffff00u : cap);
-    for (int i = 0; i < 2; ++i) { if (p->fd_redo[i]) hipFree(p->fd_redo[i]); p->fd_redo[i] = nullptr; CBA_TRY(dev_alloc(&p->fd_redo[i], (size_t)p->fd_redo_cap)); }
+    for (int i = 0; i < 2; ++i) CBA_TRY(p->fd_redo[i].alloc((size_t)p->fd_redo_cap));
   }
   CBA_HIP(hipMemset(p->jrec, 0, sizeof(double) * (size_t)(n > 0 ? n : 1) * p->rec_doubles));   // records of mixed-model problems have unused tails
-  CBA_TRY(dev_alloc(&p->cell_order, (size_t)n));
-  F(p->img_start); p->img_start = nullptr;
-  F(p->band_mask); p->band_mask = nullptr;
-  CBA_TRY(dev_alloc(&p->band_mask, (size_t)(n > 0 ? n : 1)));
+  CBA_TRY(p->cell_order.alloc((size_t)n));
+  CBA_TRY(p->band_mask.alloc((size_t)(n > 0 ? n : 1)));
   {
     std::vector<int64_t> is((size_t)L.n_images + 1, 0);
     for (int64_t i = 0; i < n; ++i) is[image_index[i] + 1] += 1;
     for (int i = 0; i < L.n_images; ++i) is[i + 1] += is[i];
-    CBA_TRY(dev_alloc(&p->img_start, is.size()));
+    CBA_TRY(p->img_start.alloc(is.size()));
     CBA_HIP(hipMemcpy(p->img_start, is.data(), sizeof(int64_t) * is.size(), hipMemcpyHostToDevice));
   }
   // observations of each (camera, pattern point), for the per-point accumulation (static: the point of an observation is data)
-  F(p->pt_start); p->pt_start = nullptr; F(p->pt_obs); p->pt_obs = nullptr;
+  p->pt_start.reset(); p->pt_obs.reset();
   if (!L.eliminate_points && n > 0 && n < 0x7fffffff && (int64_t)L.n_cameras * L.n_points < 0x7fffffff) {
     const size_t nk = (size_t)L.n_cameras * L.n_points;
     std::vector<int> ks(nk + 1, 0), ko((size_t)n);
@@ -1273,18 +1388,15 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
     for (size_t k = 0; k < nk; ++k) ks[k + 1] += ks[k];
     std::vector<int> fill(ks.begin(), ks.end() - 1);
     for (int64_t i = 0; i < n; ++i) ko[(size_t)fill[(size_t)camera_index[i] * L.n_points + point_index[i]]++] = (int)i;
-    CBA_TRY(dev_alloc(&p->pt_start, ks.size())); CBA_TRY(dev_alloc(&p->pt_obs, ko.size()));
+    CBA_TRY(p->pt_start.alloc(ks.size())); CBA_TRY(p->pt_obs.alloc(ko.size()));
     CBA_HIP(hipMemcpy(p->pt_start, ks.data(), sizeof(int) * ks.size(), hipMemcpyHostToDevice));
     CBA_HIP(hipMemcpy(p->pt_obs, ko.data(), sizeof(int) * ko.size(), hipMemcpyHostToDevice));
   }
-  F(p->slow_list); p->slow_list = nullptr;
   p->slow_cap = (int)std::min<int64_t>(std::max<int64_t>(kSlowCapMin, n / 8), 1 << 24);
-  CBA_TRY(dev_alloc(&p->slow_list, (size_t)p->slow_cap));
-  F(p->slow_skip); p->slow_skip = nullptr;
-  CBA_TRY(dev_alloc(&p->slow_skip, (size_t)(n > 0 ? n : 1)));
+  CBA_TRY(p->slow_list.alloc((size_t)p->slow_cap));
+  CBA_TRY(p->slow_skip.alloc((size_t)(n > 0 ? n : 1)));
   CBA_HIP(hipMemset(p->slow_skip, 0, (size_t)(n > 0 ? n : 1)));
-  F(p->fd_slow); p->fd_slow = nullptr;
-  CBA_TRY(dev_alloc(&p->fd_slow, (size_t)(n > 0 ? n : 1)));
+  CBA_TRY(p->fd_slow.alloc((size_t)(n > 0 ? n : 1)));
   CBA_HIP(hipMemset(p->fd_slow, 0, (size_t)(n > 0 ? n : 1)));
   CBA_HIP(hipMemset(p->slow_count, 0, sizeof(int)));
   if (n > 0) {
@@ -1297,7 +1409,7 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
     CBA_HIP(hipMemset(p->flags, 0, (size_t)n));
   }
   // block order of the imagesets (eliminate_points = 0 only: the pose blocks are the Schur blocks)
-  if (p->pose_slot) { hipFree(p->pose_slot); p->pose_slot = nullptr; }
+  p->pose_slot.reset();
   p->pose_slot_host.clear();
   if (!L.eliminate_points && L.n_images > 0 && n > 0) {
     // sort key: Z-order (Morton) index of the centre of the imageset's observations on an 8x8 raster of
@@ -1318,130 +1430,18 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
       key[i] = k;
     }
     std::stable_sort(order.begin(), order.end(), [&](int u, int v) { return key[u] != key[v] ? key[u] < key[v] : sy[u] < sy[v]; });
-    // Round 5: refine that order into a nearest-neighbour chain on the imagesets' FOOTPRINTS in the Schur product's own units.  What the
-    // block-sparse K loop of the product executes is, per pair of 128-column tiles, the 16-row slabs (2.7 imagesets) whose rows are
-    // non-zero in both tiles -- so the cost of an order is how much the tile sets of neighbouring imagesets differ, and the Z-order of the
-    // footprint CENTRES only approximates that (footprints differ in size and shape).  Tile set of an imageset = the tiles of its points'
-    // columns and of the 4 x 4 control patches under its measured pixels (the engine's tiled grid order, build_grid_order); chain: start
-    // at the head of the Z-order, always append the unplaced imageset whose tile set has the smallest Hamming distance to the last one.
-    // Executed slabs of the product, modelled from the observation lists: x 0.86 (cfg 2), 0.85 (cfg 4), 0.83 (cfg 3) against the
-    // Z-order; measured: profiles/r05_schur_row_order.txt.  The order is internal (x and the dumps are un-permuted); the sum over the
-    // pose blocks is taken in another order, which moves S by rounding only.  O(N^2 T / 64): skipped above 8192 imagesets.
-    if (p->gridfirst) {
-      // Grid-first order: the pose columns of F are empty in the grid block rows the imageset does not reach (per-pass activity,
-      // k_gf_touch), per 128-column tile = ~21 imagesets.  Imagesets are ordered by the first row of F their control patches touch
-      // (under the MEASURED pixels: a heuristic, the activity itself comes from the projected ones), so that the imagesets of a tile
-      // start at about the same place of the elimination order and their union stays small.
-      const GfPlan& g = p->gf;
-      const int W = g.grid_words;
-      std::vector<uint64_t> touched((size_t)L.n_images * W, 0ull);
-      for (int64_t i = 0; i < n; ++i) {
-        const int img = image_index[i], cam = camera_index[i];
-        const cba_camera& cm = p->cams[cam];
-        if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1])) continue;
-        const int per = cm.model_type == CBA_CENTRAL_GENERIC ? 2 : 5;
-        const double gx = 1.0 + (cm.grid_w - 3.0) * (xy[2 * i] - cm.calib_min_x) / (cm.calib_max_x + 1.0 - cm.calib_min_x);      // central_grid.h:150-154
-        const double gy = 1.0 + (cm.grid_h - 3.0) * (xy[2 * i + 1] - cm.calib_min_y) / (cm.calib_max_y + 1.0 - cm.calib_min_y);
-        const int fx = (int)std::floor(gx + 2) - 3, fy = (int)std::floor(gy + 2) - 3;
-        for (int r = 0; r < 4; ++r)
-          for (int q = 0; q < 4; ++q) {
-            const int cx = fx + q, cy = fy + r;
-            if (cx < 0 || cy < 0 || cx >= cm.grid_w || cy >= cm.grid_h) continue;
-            const int e = L.intr_offset[cam] - g.n_rp + per * g.gperm[cam][cx + (size_t)cy * cm.grid_w];
-            const int r0 = g.f_of_grid[e] >> 6, r1 = g.f_of_grid[e + per - 1] >> 6;
-            touched[(size_t)img * W + (r0 >> 6)] |= 1ull << (r0 & 63);
-            touched[(size_t)img * W + (r1 >> 6)] |= 1ull << (r1 & 63);
-          }
-      }
-      std::vector<int> slot_of;
-      gf_order_imagesets(g, touched, L.n_images, g.n_rp + 6 * p->gf_img0, &slot_of);      // (sharding: this rank's slots of the border)
-      for (int i = 0; i < L.n_images; ++i) order[slot_of[i]] = i;
-      // First tile order of the border update, predicted from the same rows (the first solve would otherwise run its tiles in
-      // row-major order: 4.7 instead of 3.5 ms at BASELINE configs[1]): per 128-column tile of the border the union of its imagesets'
-      // rows, closed under the fill of the grid factor; rig / point tiles and the right-hand side's tile reach every row.
-      if (p->gf_tile_list_host) {
-        const int nt = (g.n_pad - g.Gf) / 128;
-        std::vector<uint64_t> tact((size_t)nt * W, 0ull);
-        auto all_rows = [&](int t) { for (int w = 0; w < W; ++w) tact[(size_t)t * W + w] = ~0ull; };
-        for (int t = 0; t < nt && 128 * t < g.n_rp; ++t) all_rows(t);
-        all_rows(nt - 1);
-        if (p->gf_sharded) for (int t = 0; t < nt; ++t) all_rows(t);        // (the other ranks' rows are not known here: dense)
-        for (int i = 0; i < L.n_images; ++i)
-          for (int t : {(g.n_rp + 6 * slot_of[i]) >> 7, (g.n_rp + 6 * slot_of[i] + 5) >> 7})
-            for (int w = 0; w < W; ++w) tact[(size_t)t * W + w] |= touched[(size_t)i * W + w];
-        for (int t = 0; t < nt; ++t) {
-          uint64_t* a = &tact[(size_t)t * W];
-          for (int r = 0; r < g.nbg; ++r)
-            if ((a[r >> 6] >> (r & 63)) & 1ull)
-              for (int w = r >> 6; w < W; ++w) a[w] |= g.gridrow[(size_t)r * W + w];
-          for (int w = 0; w < W; ++w)
-            if (64 * w + 64 > g.nbg) a[w] &= (64 * w >= g.nbg) ? 0ull : (~0ull >> (64 - (g.nbg - 64 * w)));
-        }
-        gf_build_tile_list(p, nt, g.Gf / 16, [&](int tm, int tn) {
-          int rows = 0;
-          for (int w = 0; w < W; ++w) rows += __builtin_popcountll(tact[(size_t)tm * W + w] & tact[(size_t)tn * W + w]);
-          return 4 * rows;                                   // K slabs of 16 rows: four per block row
-        }, [&](int tm, int tn, int target) {
-          int seen = 0;
-          for (int r = 0; r < g.nbg; ++r)
-            if (((tact[(size_t)tm * W + (r >> 6)] & tact[(size_t)tn * W + (r >> 6)]) >> (r & 63)) & 1ull) {
-              if (seen + 4 > target) return 4 * r;
-              seen += 4;
-            }
-          return 0;
-        });
-        p->gf_tile_list_age = 0;
-      }
-    } else
-    if (!L.localize_only && L.n_images >= 4 && L.n_images <= 8192 && !p->dense_perm_host.empty()) {
-      const int T = (L.dense_dof + 127) / 128, W = (T + 63) / 64;
-      std::vector<unsigned long long> mask((size_t)L.n_images * W, 0ull);
-      auto set_col = [&](int img, int col) { if (col >= 0 && col < L.dense_dof) { const int t = col >> 7; mask[(size_t)img * W + (t >> 6)] |= 1ull << (t & 63); } };
-      for (int64_t i = 0; i < n; ++i) {
-        const int img = image_index[i], cam = camera_index[i];
-        const int pc = L.first_points - L.block_dof + 3 * point_index[i];
-        set_col(img, pc); set_col(img, pc + 2);
-        if (!std::isfinite(xy[2 * i]) || !std::isfinite(xy[2 * i + 1])) continue;      // (the cast below is undefined for a non-finite pixel)
-        const cba_camera& cm = p->cams[cam];
-        const int per = cm.model_type == CBA_CENTRAL_GENERIC ? 2 : 5;
-        const double gx = 1.0 + (cm.grid_w - 3.0) * (xy[2 * i] - cm.calib_min_x) / (cm.calib_max_x + 1.0 - cm.calib_min_x);      // central_grid.h:150-154
-        const double gy = 1.0 + (cm.grid_h - 3.0) * (xy[2 * i + 1] - cm.calib_min_y) / (cm.calib_max_y + 1.0 - cm.calib_min_y);
-        const int fx = (int)std::floor(gx + 2) - 3, fy = (int)std::floor(gy + 2) - 3;
-        for (int r = 0; r < 4; ++r)
-          for (int q = 0; q < 4; ++q) {
-            const int cx = fx + q, cy = fy + r;
-            if (cx < 0 || cy < 0 || cx >= cm.grid_w || cy >= cm.grid_h) continue;
-            const int first = L.intr_offset[cam] + per * (cx + cy * cm.grid_w);
-            set_col(img, p->dense_perm_host[first]); set_col(img, p->dense_perm_host[first + per - 1]);
-          }
-      }
-      std::vector<int> chain; chain.reserve(L.n_images);
-      std::vector<char> placed(L.n_images, 0);
-      int cur = order[0];
-      chain.push_back(cur); placed[cur] = 1;
-      for (int step = 1; step < L.n_images; ++step) {
-        const unsigned long long* mc = &mask[(size_t)cur * W];
-        int best = -1, best_d = 0x7fffffff;
-        for (int r = 0; r < L.n_images; ++r) {                 // candidates in Z-order: ties go to the Z-order neighbour
-          const int v = order[r];
-          if (placed[v]) continue;
-          const unsigned long long* mv = &mask[(size_t)v * W];
-          int d = 0;
-          for (int w = 0; w < W; ++w) d += __builtin_popcountll(mc[w] ^ mv[w]);
-          if (d < best_d) { best_d = d; best = v; }
-        }
-        cur = best; chain.push_back(cur); placed[cur] = 1;
-      }
-      order.swap(chain);
-    }
+    if (p->gridfirst) order_imagesets_gridfirst(p, n, xy, image_index, camera_index, order);
+    else if (!L.localize_only && L.n_images >= 4 && L.n_images <= 8192 && !p->dense_perm_host.empty())
+      order_imagesets_chain(p, n, xy, point_index, image_index, camera_index, order);
     p->pose_slot_host.assign(L.n_images, 0);
     for (int r = 0; r < L.n_images; ++r) p->pose_slot_host[order[r]] = r;
-    CBA_TRY(dev_alloc(&p->pose_slot, (size_t)L.n_images));
+    CBA_TRY(p->pose_slot.alloc((size_t)L.n_images));
     CBA_HIP(hipMemcpy(p->pose_slot, p->pose_slot_host.data(), sizeof(int) * L.n_images, hipMemcpyHostToDevice));
   }
-  p->have_obs = true; p->have_system = false;
+  p->have_obs = true;
   return CBA_OK;
 }
+
 
 int cba_set_state(cba_problem* p, const double* rig_tr_global, const double* camera_tr_rig, const double* points,
                   const double* const* grids) {
@@ -1542,7 +1542,7 @@ int cba_debug_apply_update(cba_problem* p, const double* x) {
     for (int i = 0; i < p->L.dense_dof; ++i) xp[p->L.block_dof + p->dense_perm_host[i]] = x[p->L.block_dof + i];
     CBA_HIP(hipMemcpy(p->x, xp.data(), sizeof(double) * p->L.total_dof, hipMemcpyHostToDevice));
   }
-  CBA_TRY(launch_apply_update(p->L, p->cams, p->st[p->cur], p->x, p->st[p->cur ^ 1], p->pose_slot, p->gperm, p->stream));
+  CBA_TRY(launch_apply_update(p->L, p->cams, p->st[p->cur], p->x, p->st[p->cur ^ 1], p->pose_slot, gperm_view(p).v, p->stream));
   CBA_HIP(hipStreamSynchronize(p->stream));
   p->cur ^= 1;
   p->have_system = false;
@@ -1580,7 +1580,6 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
     report->final_cost = last_cost;
   };
   if (defer_cost_read) {
-    if (!p->pin_cost) CBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->pin_cost), 16 * sizeof(double)));
     CBA_HIP(hipMemcpyAsync(p->pin_cost, p->red8, 8 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   } else {
     CBA_TRY(allreduce(p, p->red8, 8));
@@ -1616,7 +1615,6 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
   // nothing behind a broken solve (PassArgs::guard), so a NaN / zero-pivot attempt leaves no trace, as in the reference, which
   // skips the cost pass for a NaN update (lm_optimizer.h:905-913).  Decisions are unchanged: the same numbers reach the same tests.
   const bool fused = !multi;
-  if (fused && !p->pin_cost) CBA_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->pin_cost), 16 * sizeof(double)));
   for (int lm = 0; lm < max_lm_attempts; ++lm) {
     report->lm_attempts += 1;
     t0 = now_s();
@@ -1626,7 +1624,7 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
       rc = solve_enqueue(p, lambda, report);
       if (rc == CBA_OK) {
         CBA_TRY(timer_begin(p, 7));
-        CBA_TRY(launch_apply_update(L, p->cams, p->st[p->cur], p->x, p->st[cand], p->pose_slot, p->gperm, p->stream));
+        CBA_TRY(launch_apply_update(L, p->cams, p->st[p->cur], p->x, p->st[cand], p->pose_slot, gperm_view(p).v, p->stream));
         CBA_TRY(residual_pass(p, cand, p->cost_test, p->status + 1));
         CBA_TRY(launch_reduce_costs(p->cost_ref, p->cost_test, nullptr, p->n_obs, p->red_partials, p->red8, p->stream));
         CBA_HIP(hipMemcpyAsync(p->pin_cost + 8, p->red8, 8 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
@@ -1671,7 +1669,7 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
       for (int i = 0; i < 8; ++i) h[i] = p->pin_cost[8 + i];
     } else {
       t0 = now_s();
-      CBA_TRY(launch_apply_update(L, p->cams, p->st[p->cur], p->x, p->st[cand], p->pose_slot, p->gperm, p->stream));
+      CBA_TRY(launch_apply_update(L, p->cams, p->st[p->cur], p->x, p->st[cand], p->pose_slot, gperm_view(p).v, p->stream));
       CBA_TRY(residual_pass(p, cand, p->cost_test));
       CBA_TRY(launch_reduce_costs(p->cost_ref, p->cost_test, nullptr, p->n_obs, p->red_partials, p->red8, p->stream));
       CBA_TRY(allreduce(p, p->red8, 8));
@@ -1797,30 +1795,26 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
 struct cba_model {
   cba_camera cam{};
   int device = 0;
-  double* d_grid = nullptr; CamDev* d_cam = nullptr;
+  DevBuf<double> d_grid; DevBuf<CamDev> d_cam;
   // scratch, grown on demand
   int64_t cap = 0;
-  double *d_a = nullptr, *d_b = nullptr, *d_c = nullptr, *d_j = nullptr; uint8_t* d_ok = nullptr;
+  DevBuf<double> d_a, d_b, d_c, d_j; DevBuf<uint8_t> d_ok;
 };
 static int model_reserve(cba_model* m, int64_t n) {
   if (n <= m->cap) return CBA_OK;
-  auto F = [](void* q) { if (q) hipFree(q); };
-  F(m->d_a); F(m->d_b); F(m->d_c); F(m->d_j); F(m->d_ok);
-  m->d_a = m->d_b = m->d_c = m->d_j = nullptr; m->d_ok = nullptr; m->cap = 0;
+  m->cap = 0;
   const int64_t cap = n < 256 ? 256 : n;
-  CBA_TRY(dev_alloc(&m->d_a, 3 * (size_t)cap));     // local points / pixels (in)
-  CBA_TRY(dev_alloc(&m->d_b, 6 * (size_t)cap));     // pixels / lines (out)
-  CBA_TRY(dev_alloc(&m->d_c, 2 * (size_t)cap));     // initial pixels
-  CBA_TRY(dev_alloc(&m->d_j, 12 * (size_t)cap));    // un-projection Jacobians
-  CBA_TRY(dev_alloc(&m->d_ok, (size_t)cap));
+  CBA_TRY(m->d_a.alloc(3 * (size_t)cap));     // local points / pixels (in)
+  CBA_TRY(m->d_b.alloc(6 * (size_t)cap));     // pixels / lines (out)
+  CBA_TRY(m->d_c.alloc(2 * (size_t)cap));     // initial pixels
+  CBA_TRY(m->d_j.alloc(12 * (size_t)cap));    // un-projection Jacobians
+  CBA_TRY(m->d_ok.alloc((size_t)cap));
   m->cap = cap;
   return CBA_OK;
 }
 void cba_model_destroy(cba_model* m) {
   if (!m) return;
-  hipSetDevice(m->device);
-  auto F = [](void* q) { if (q) hipFree(q); };
-  F(m->d_grid); F(m->d_cam); F(m->d_a); F(m->d_b); F(m->d_c); F(m->d_j); F(m->d_ok);
+  hipSetDevice(m->device);      // current while the members free their memory
   delete m;
 }
 int64_t cba_fd_redo_overflow(cba_problem* p) {
@@ -1853,17 +1847,15 @@ int cba_model_create(const cba_camera* camera, const double* grid, int32_t devic
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available (the engine has no CPU fallback)"); return CBA_ERR_HIP; }
   if (device < 0 || device >= ndev) { set_error("bad device ordinal"); return CBA_ERR_ARG; }
   CBA_HIP(hipSetDevice(device));
-  cba_model* m = new cba_model();
-  struct Guard { cba_model* q; ~Guard() { if (q) cba_model_destroy(q); } } guard{m};
+  std::unique_ptr<cba_model, decltype(&cba_model_destroy)> m(new cba_model(), &cba_model_destroy);
   m->cam = *camera; m->device = device;
   const size_t G = (size_t)camera->grid_w * camera->grid_h;
-  CBA_TRY(dev_alloc(&m->d_grid, (camera->model_type == CBA_CENTRAL_GENERIC ? 3 : 6) * G));
-  CBA_TRY(cba_model_set_grid(m, grid));
+  CBA_TRY(m->d_grid.alloc((camera->model_type == CBA_CENTRAL_GENERIC ? 3 : 6) * G));
+  CBA_TRY(cba_model_set_grid(m.get(), grid));
   CamDev h = make_camdev(*camera, m->d_grid, nullptr, 0);
-  CBA_TRY(dev_alloc(&m->d_cam, 1));
+  CBA_TRY(m->d_cam.alloc(1));
   CBA_HIP(hipMemcpy(m->d_cam, &h, sizeof(CamDev), hipMemcpyHostToDevice));
-  guard.q = nullptr;
-  *out = m;
+  *out = m.release();
   return CBA_OK;
 }
 int cba_model_project(cba_model* m, int64_t n, const double* local_points, const double* init_pixels, double* pixels, uint8_t* ok) {
@@ -1873,7 +1865,7 @@ int cba_model_project(cba_model* m, int64_t n, const double* local_points, const
   CBA_TRY(model_reserve(m, n));
   CBA_HIP(hipMemcpy(m->d_a, local_points, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
   if (init_pixels) CBA_HIP(hipMemcpy(m->d_c, init_pixels, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-  CBA_TRY(launch_project_points(m->d_cam, m->cam.model_type, n, m->d_a, init_pixels ? m->d_c : nullptr, m->d_b, m->d_ok, nullptr));
+  CBA_TRY(launch_project_points(m->d_cam, m->cam.model_type, n, m->d_a, init_pixels ? (const double*)m->d_c : nullptr, m->d_b, m->d_ok, nullptr));
   CBA_HIP(hipMemcpy(pixels, m->d_b, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
   CBA_HIP(hipMemcpy(ok, m->d_ok, (size_t)n, hipMemcpyDeviceToHost));
   return CBA_OK;
@@ -1884,7 +1876,7 @@ int cba_model_unproject(cba_model* m, int64_t n, const double* pixels, double* l
   CBA_HIP(hipSetDevice(m->device));
   CBA_TRY(model_reserve(m, n));
   CBA_HIP(hipMemcpy(m->d_a, pixels, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-  CBA_TRY(launch_unproject(m->d_cam, m->cam.model_type, n, m->d_a, m->d_b, jacobians ? m->d_j : nullptr, m->d_ok, nullptr));
+  CBA_TRY(launch_unproject(m->d_cam, m->cam.model_type, n, m->d_a, m->d_b, jacobians ? (double*)m->d_j : nullptr, m->d_ok, nullptr));
   CBA_HIP(hipMemcpy(lines, m->d_b, sizeof(double) * 6 * n, hipMemcpyDeviceToHost));
   CBA_HIP(hipMemcpy(ok, m->d_ok, (size_t)n, hipMemcpyDeviceToHost));
   if (jacobians) CBA_HIP(hipMemcpy(jacobians, m->d_j, sizeof(double) * 12 * n, hipMemcpyDeviceToHost));
@@ -1929,13 +1921,12 @@ int cba_schur_solve_opt(int32_t block_size, int32_t n_blocks, int32_t dense_dof,
   const int bs = block_size, nb = n_blocks, dd = dense_dof, bdof = bs * nb;
   int n_pad, n_fact; padded_dims(dd, &n_pad, &n_fact);
   const int ld = n_pad, Kpad = round_up(bdof, 16);
-  double *Dblk, *bblk, *Dinv, *dinvb, *B, *W, *Hdd, *bd, *S, *xd, *gws; int* status;
-  DevPool pool;
-  CBA_TRY(pool.alloc(&gws, (size_t)gemv_t_workspace_doubles(dd)));
-  CBA_TRY(pool.alloc(&Dblk, (size_t)nb * bs * bs)); CBA_TRY(pool.alloc(&bblk, (size_t)bdof)); CBA_TRY(pool.alloc(&Dinv, (size_t)nb * bs * bs));
-  CBA_TRY(pool.alloc(&dinvb, (size_t)Kpad)); CBA_TRY(pool.alloc(&B, (size_t)Kpad * ld)); CBA_TRY(pool.alloc(&W, (size_t)Kpad * ld));
-  CBA_TRY(pool.alloc(&Hdd, (size_t)ld * ld)); CBA_TRY(pool.alloc(&bd, (size_t)ld)); CBA_TRY(pool.alloc(&S, (size_t)ld * ld));
-  CBA_TRY(pool.alloc(&xd, (size_t)bdof + ld)); CBA_TRY(pool.alloc(&status, 1));
+  DevBuf<double> Dblk, bblk, Dinv, dinvb, B, W, Hdd, bd, S, xd, gws; DevBuf<int> status;
+  CBA_TRY(gws.alloc((size_t)gemv_t_workspace_doubles(dd)));
+  CBA_TRY(Dblk.alloc((size_t)nb * bs * bs)); CBA_TRY(bblk.alloc((size_t)bdof)); CBA_TRY(Dinv.alloc((size_t)nb * bs * bs));
+  CBA_TRY(dinvb.alloc((size_t)Kpad)); CBA_TRY(B.alloc((size_t)Kpad * ld)); CBA_TRY(W.alloc((size_t)Kpad * ld));
+  CBA_TRY(Hdd.alloc((size_t)ld * ld)); CBA_TRY(bd.alloc((size_t)ld)); CBA_TRY(S.alloc((size_t)ld * ld));
+  CBA_TRY(xd.alloc((size_t)bdof + ld)); CBA_TRY(status.alloc(1));
   CBA_HIP(hipMemset(B, 0, sizeof(double) * (size_t)Kpad * ld)); CBA_HIP(hipMemset(W, 0, sizeof(double) * (size_t)Kpad * ld));
   CBA_HIP(hipMemset(Hdd, 0, sizeof(double) * (size_t)ld * ld)); CBA_HIP(hipMemset(S, 0, sizeof(double) * (size_t)ld * ld));
   CBA_HIP(hipMemset(bd, 0, sizeof(double) * ld)); CBA_HIP(hipMemset(status, 0, sizeof(int))); CBA_HIP(hipMemset(dinvb, 0, sizeof(double) * Kpad));
@@ -1953,7 +1944,6 @@ int cba_schur_solve_opt(int32_t block_size, int32_t n_blocks, int32_t dense_dof,
   CBA_HIP(hipMemcpy2D(Hdd, ld * sizeof(double), hH.data(), dd * sizeof(double), dd * sizeof(double), dd, hipMemcpyHostToDevice));
   CBA_HIP(hipMemcpy(bd, dense_b, sizeof(double) * dd, hipMemcpyHostToDevice));
   LdltWorkspace w;
-  LdltGuard wguard{&w};
   CBA_TRY(ldlt_workspace_alloc(w, n_pad));
   apply_solver_options(w, options);
   CBA_HIP(hipMemset(w.status, 0, sizeof(int)));
@@ -2022,16 +2012,15 @@ int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n
   int n_pad, n_fact; padded_dims(dof, &n_pad, &n_fact);
   const int ld = n_pad;
   cba_fit_report rep{};
-  double *g[2] = {nullptr, nullptr}, *tang, *gp, *dirs, *cost_ref, *cost_test, *rec, *H, *b, *S, *x, *partials, *red8, *scal;
-  int *keys, *count, *start, *fill, *order, *status;
+  DevBuf<double> g[2], tang, gp, dirs, cost_ref, cost_test, rec, H, b, S, x, partials, red8, scal;
+  DevBuf<int> keys, count, start, fill, order, status;
   const size_t nn = (size_t)(n > 0 ? n : 1);
-  DevPool pool;
-  CBA_TRY(pool.alloc(&g[0], 3 * (size_t)G)); CBA_TRY(pool.alloc(&g[1], 3 * (size_t)G)); CBA_TRY(pool.alloc(&tang, 6 * (size_t)G));
-  CBA_TRY(pool.alloc(&gp, 2 * nn)); CBA_TRY(pool.alloc(&dirs, 3 * nn)); CBA_TRY(pool.alloc(&cost_ref, 3 * nn)); CBA_TRY(pool.alloc(&cost_test, 3 * nn));
-  CBA_TRY(pool.alloc(&rec, nn * 99)); CBA_TRY(pool.alloc(&keys, nn)); CBA_TRY(pool.alloc(&order, nn));
-  CBA_TRY(pool.alloc(&count, (size_t)G + 1)); CBA_TRY(pool.alloc(&start, (size_t)G + 1)); CBA_TRY(pool.alloc(&fill, (size_t)G + 1));
-  CBA_TRY(pool.alloc(&H, (size_t)ld * ld)); CBA_TRY(pool.alloc(&b, (size_t)ld)); CBA_TRY(pool.alloc(&S, (size_t)ld * ld)); CBA_TRY(pool.alloc(&x, (size_t)ld));
-  CBA_TRY(pool.alloc(&partials, 256 * 8)); CBA_TRY(pool.alloc(&red8, 8)); CBA_TRY(pool.alloc(&scal, 8)); CBA_TRY(pool.alloc(&status, 1));
+  CBA_TRY(g[0].alloc(3 * (size_t)G)); CBA_TRY(g[1].alloc(3 * (size_t)G)); CBA_TRY(tang.alloc(6 * (size_t)G));
+  CBA_TRY(gp.alloc(2 * nn)); CBA_TRY(dirs.alloc(3 * nn)); CBA_TRY(cost_ref.alloc(3 * nn)); CBA_TRY(cost_test.alloc(3 * nn));
+  CBA_TRY(rec.alloc(nn * 99)); CBA_TRY(keys.alloc(nn)); CBA_TRY(order.alloc(nn));
+  CBA_TRY(count.alloc((size_t)G + 1)); CBA_TRY(start.alloc((size_t)G + 1)); CBA_TRY(fill.alloc((size_t)G + 1));
+  CBA_TRY(H.alloc((size_t)ld * ld)); CBA_TRY(b.alloc((size_t)ld)); CBA_TRY(S.alloc((size_t)ld * ld)); CBA_TRY(x.alloc((size_t)ld));
+  CBA_TRY(partials.alloc(256 * 8)); CBA_TRY(red8.alloc(8)); CBA_TRY(scal.alloc(8)); CBA_TRY(status.alloc(1));
   CBA_HIP(hipMemcpy(g[0], grid, sizeof(double) * 3 * G, hipMemcpyHostToDevice));
   if (n) {
     CBA_HIP(hipMemcpy(gp, grid_points, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
@@ -2039,7 +2028,6 @@ int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n
   }
   CBA_HIP(hipMemset(status, 0, sizeof(int)));
   LdltWorkspace w;
-  LdltGuard wguard{&w};
   CBA_TRY(ldlt_workspace_alloc(w, n_pad));
   hipStream_t s = nullptr;
   CBA_TRY(make_main_stream(&s));

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cba.h"
@@ -20,6 +21,68 @@ void set_error(const std::string& msg);
       return CBA_ERR_HIP;                                                                      \
     }                                                                                          \
   } while (0)
+#define CBA_TRY(expr) do { int _rc = (expr); if (_rc != CBA_OK) return _rc; } while (0)
+
+// Owning handles of device memory (DevBuf), pinned host memory (PinnedBuf) and events (Event); host only, move-only.
+// alloc(n) / create() first release what the handle holds, then allocate (n = 0 allocates one element); on failure the
+// handle stays empty and the error is set as by CBA_HIP.  The read-only conversion keeps launch sites as they are (p->Dblk).
+template <typename T, bool kPinned>
+class HipBuf {
+ public:
+  HipBuf() = default;
+  HipBuf(HipBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  HipBuf& operator=(HipBuf&& o) noexcept {
+    if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+    return *this;
+  }
+  ~HipBuf() { reset(); }
+  int alloc(size_t n) {
+    reset();
+    void* q = nullptr;
+    if (kPinned) CBA_HIP(hipHostMalloc(&q, (n ? n : 1) * sizeof(T)));
+    else CBA_HIP(hipMalloc(&q, (n ? n : 1) * sizeof(T)));
+    p_ = static_cast<T*>(q);
+    return CBA_OK;
+  }
+  void reset() {
+    if (p_) { if (kPinned) hipHostFree(p_); else hipFree(p_); }
+    p_ = nullptr;
+  }
+  operator T*() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+};
+template <typename T> using DevBuf = HipBuf<T, false>;
+template <typename T> using PinnedBuf = HipBuf<T, true>;
+
+class Event {
+ public:
+  Event() = default;
+  Event(Event&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+  Event& operator=(Event&& o) noexcept {
+    if (this != &o) { reset(); e_ = o.e_; o.e_ = nullptr; }
+    return *this;
+  }
+  ~Event() { reset(); }
+  int create(unsigned flags = hipEventDefault) {
+    reset();
+    hipEvent_t e = nullptr;
+    CBA_HIP(hipEventCreateWithFlags(&e, flags));
+    e_ = e;
+    return CBA_OK;
+  }
+  void reset() {
+    if (e_) hipEventDestroy(e_);
+    e_ = nullptr;
+  }
+  operator hipEvent_t() const { return e_; }
+
+ private:
+  hipEvent_t e_ = nullptr;
+};
+
+static_assert(std::is_trivially_copyable_v<CamDev>);
 
 // Variable ordering of JointOptimizationState (joint_optimization.cc:49-59, 142-170).
 struct Layout {
@@ -38,10 +101,10 @@ constexpr int kMaxCols = 6 + 6 + 3 + kMaxGridCols;     // pose + rig + point + g
 constexpr int kRecHeader = 3 + 12 + 12 + 6;
 
 struct DevState {
-  double* rig_tr_global = nullptr;   // 7N
-  double* camera_tr_rig = nullptr;   // 7C
-  double* points = nullptr;          // 3P
-  double* grids[kMaxCameras] = {};   // per camera
+  DevBuf<double> rig_tr_global;      // 7N
+  DevBuf<double> camera_tr_rig;      // 7C
+  DevBuf<double> points;             // 3P
+  DevBuf<double> grids[kMaxCameras]; // per camera
 };
 
 // Device-visible description of a pass over the observations.
@@ -74,6 +137,7 @@ struct PassArgs {
   // attempt touches nothing, exactly as the reference, which skips the cost pass for a NaN update (LV/lm_optimizer.h:905-913)
   const int* guard;
 };
+static_assert(std::is_trivially_copyable_v<PassArgs>);
 
 // ---- kernels_obs.hip ----
 int launch_compose_poses(const DevState& st, int N, int C, double* itg, hipStream_t s);
@@ -97,6 +161,7 @@ int launch_assemble(const PassArgs& a, const Layout& L, const DevState& st, int 
 struct AccumTargets {
   double* Dblk; double* bblk; double* B; double* Hdd; double* bd;
 };
+static_assert(std::is_trivially_copyable_v<AccumTargets>);
 int launch_accumulate(const PassArgs& a, const Layout& L, int rec_doubles, const uint8_t* flags, const double* jrec,
                       const int* cells, const uint32_t* pair_tables, const int* pair_counts, AccumTargets t,
                       const double* det_scale, int points_separate, hipStream_t s);
@@ -144,40 +209,39 @@ int launch_gemv_n(const double* M, int K, int n, int ld, const double* v, const 
 struct GemmStats { double seconds = 0, flops = 0, bytes = 0; int launches = 0; };
 // In-place blocked LDL^T of a symmetric matrix stored "upper in row-major" (= lower in column-major).
 struct LdltWorkspace {
-  double* X = nullptr;       // X = D L of a super-panel's row strip [x_rows][ld]
+  DevBuf<double> X;          // X = D L of a super-panel's row strip [x_rows][ld]
   int x_rows = 0;
-  double* invLt = nullptr;   // per 64-block: transposed inverse of the unit factor [kInner][kInner]
+  DevBuf<double> invLt;      // per 64-block: transposed inverse of the unit factor [kInner][kInner]
   // scheduling options (cba_solver_options): rows left to the final dataflow launch; back substitution as one dataflow launch
   int tail_rows = 0;         // rows left to the final dataflow launch; 0 = the schedule's default (ldlt_tail_rows)
   bool back_dataflow = true;
-  double* dvec = nullptr;    // n
-  int* status = nullptr;
+  DevBuf<double> dvec;       // n
+  DevBuf<int> status;
   // the device's side streams (shared, not owned): high-priority / two plain ones.  The factorisation itself runs on the caller's
   // stream; users: the exchanges of the distributed variant, the Jacobian pass' side work (cba_api.hip)
   hipStream_t panel_stream = nullptr, mid_stream = nullptr, far_stream = nullptr;
-  hipEvent_t ev_strip = nullptr, ev_mid = nullptr;
+  Event ev_strip, ev_mid;
   size_t n_alloc = 0;
   // kernel-only timing of the 128 x 128 GEMM launches of the factorisation (bulk and row-strip updates): event pairs
   // on the stream of each launch, read back by the caller after the step (ldlt_collect_spans)
-  struct Span { hipEvent_t e0 = nullptr, e1 = nullptr; double flops = 0; bool masked_update = false; };
+  struct Span { Event e0, e1; double flops = 0; bool masked_update = false; };
   std::vector<Span> spans;
   int spans_used = 0;
   // persistent tail launch (ldlt_tail): flags hold the number of the call that set them, nothing is cleared between calls
-  unsigned* tail_flags = nullptr;    // tile flags [tail_rows_cap / 64][n / 64], then diag / upre / part flags [n / 64] each
-  unsigned* tail_ctrl = nullptr;     // tickets, abort flag, role tickets, chain CU
+  DevBuf<unsigned> tail_flags;       // tile flags [tail_rows_cap / 64][n / 64], then diag / upre / part flags [n / 64] each
+  DevBuf<unsigned> tail_ctrl;        // tickets, abort flag, role tickets, chain CU
   bool tail_ctrl_clean = false;      // the control words are already zero for the next dataflow launch (ldlt_clear_ctrl)
   unsigned tail_epoch = 0;
   int tail_rows_cap = 0;             // largest tail this workspace has flags for
-  double* back_xe = nullptr;         // back substitution (k_back_dataflow): {value, tag} pairs, 2 * n doubles
+  DevBuf<double> back_xe;            // back substitution (k_back_dataflow): {value, tag} pairs, 2 * n doubles
   unsigned long long back_epoch = 0;
-  hipEvent_t tail_e0 = nullptr, tail_e1 = nullptr;   // span of the last tail launch (statistics only)
+  Event tail_e0, tail_e1;            // span of the last tail launch (statistics only)
   bool tail_timed = false;
 };
 // flag_rows_blocks: block rows a dataflow launch may cover (0 = the dense schedule's own maximum)
 int ldlt_workspace_alloc(LdltWorkspace& w, int n, int flag_rows_blocks = 0);
 // adds the GEMM launches timed since the last call to `st` (waits for them)
 int ldlt_collect_spans(LdltWorkspace& w, GemmStats* st);
-void ldlt_workspace_free(LdltWorkspace& w);
 // k_begin: rows above it are factored already and their update is applied (the border of the grid-first order)
 int ldlt_factor(double* S, int n, int ld, LdltWorkspace& w, hipStream_t s, GemmStats* trailing_stats, int k_begin = 0);
 // x of L^T x = z (z = column zcol of S, forward-substituted by the factorisation); rowmask: optional block-sparsity of the factor's rows
@@ -186,16 +250,16 @@ int ldlt_back_solve(const double* S, int n_fact, int ld, int zcol, const LdltWor
 // Grid-first elimination (gridfirst_plan.h): device copies of the plan's arrays
 struct GfTask; struct GfIval; struct GfChain;
 struct GfDevice {
-  GfTask* tasks = nullptr; GfIval* ivals = nullptr; GfChain* chains = nullptr;
+  DevBuf<GfTask> tasks; DevBuf<GfIval> ivals; DevBuf<GfChain> chains;
   int n_tasks0 = 0, n_tasks1 = 0, n_chains = 0;
   int nbg = 0, nbf = 0;
-  unsigned long long* rowmask = nullptr; int mask_words = 0;      // static structure of every factored block row (the plan's)
+  DevBuf<unsigned long long> rowmask; int mask_words = 0;      // static structure of every factored block row (the plan's)
   double flops_grid = 0;
   // per Jacobian pass (launch_gf_activity): activity of the grid x border tiles and what is derived from it
-  unsigned long long* act = nullptr; int act_words = 0; int n_act_tiles = 0;
-  unsigned long long* gridrow = nullptr;          // [nbg][act_words]: structure of the grid x grid factor's rows (closure of the activity)
-  unsigned long long* kmask = nullptr; int kmask_words = 0;      // border update: [absolute 128-column tile][words], bit = 16-row K slab
-  unsigned long long* rowmask_dyn = nullptr;      // back substitution: rowmask with the border bits of the grid rows from `act`
+  DevBuf<unsigned long long> act; int act_words = 0; int n_act_tiles = 0;
+  DevBuf<unsigned long long> gridrow;          // [nbg][act_words]: structure of the grid x grid factor's rows (closure of the activity)
+  DevBuf<unsigned long long> kmask; int kmask_words = 0;      // border update: [absolute 128-column tile][words], bit = 16-row K slab
+  DevBuf<unsigned long long> rowmask_dyn;      // back substitution: rowmask with the border bits of the grid rows from `act`
 };
 // F = [grid | border] in the plan's order, ld = its n_pad; Xb: (rows of the grid part) x (ld - Gf) panel buffer (zero outside the
 // tiles the launch writes); kmask: optional block-sparsity of the border update (null = dense); tile_list: optional order of its

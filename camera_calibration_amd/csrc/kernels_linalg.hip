@@ -268,6 +268,7 @@ struct GemmArgs {
                                 // the tile are entries of their own and run whenever: a tile with all slabs is a third of the launch's
                                 // makespan, two halves are not); s1 = 0: the whole tile, plain read-modify-write
 };
+static_assert(std::is_trivially_copyable_v<GemmArgs>);
 
 // Developer switches are compiled only into the bench harness (tools/bench_tail.hip, tools/bench_diag.hip define CBA_DEV_SWITCHES): the
 // product library has no epilogue modes and reads no CBA_* environment variables.
@@ -778,6 +779,7 @@ struct TailArgs {
   const unsigned long long* act;    // optional activity of the border tiles: [(c - x_c0) / 2][act_words], bit r = block row r of the 128-column
   int act_words;                    // tile can be non-zero (kernels_gridfirst.hip: k_gf_touch / k_gf_close); inactive tiles are neither computed nor read
 };
+static_assert(std::is_trivially_copyable_v<TailArgs>);
 // first block row >= k (< kend) whose bit is set / clear in `bits`; kend if there is none
 __device__ __forceinline__ int bits_next(const unsigned long long* bits, int k, int kend, bool want_set) {
   while (k < kend) {
@@ -2101,7 +2103,7 @@ int make_main_stream(hipStream_t* s) {
 
 static int super_width();
 int ldlt_workspace_alloc(LdltWorkspace& w, int n_pad, int flag_rows_blocks) {
-  ldlt_workspace_free(w);
+  w = LdltWorkspace();
   // X = D L of a super-panel's row strip: the K-major B operand of the bulk update.  A super-panel is at most super_width() + 512
   // rows wide (super_width_at), never wider than the matrix
   {
@@ -2110,61 +2112,46 @@ int ldlt_workspace_alloc(LdltWorkspace& w, int n_pad, int flag_rows_blocks) {
     int x_rows = std::max(super_width(), (super_width() % 512) ? 2048 : 0) + 512;
     if (x_rows > kSuperMax) x_rows = kSuperMax;
     if (x_rows > n_pad) x_rows = n_pad;
-    CBA_HIP(hipMalloc(&w.X, sizeof(double) * (size_t)x_rows * n_pad));
+    CBA_TRY(w.X.alloc((size_t)x_rows * n_pad));
     w.x_rows = x_rows;
   }
-  CBA_HIP(hipMalloc(&w.invLt, sizeof(double) * (size_t)(n_pad / kInner) * kInner * kInner));
-  CBA_HIP(hipMalloc(&w.dvec, sizeof(double) * (size_t)n_pad));
-  CBA_HIP(hipMalloc(&w.status, sizeof(int)));
+  CBA_TRY(w.invLt.alloc((size_t)(n_pad / kInner) * kInner * kInner));
+  CBA_TRY(w.dvec.alloc((size_t)n_pad));
+  CBA_TRY(w.status.alloc(1));
   {
     DeviceStreams d;
     int rc = device_streams(&d);
     if (rc != CBA_OK) return rc;
     w.panel_stream = d.chain; w.mid_stream = d.mid; w.far_stream = d.far;     // shared, not owned
   }
-  CBA_HIP(hipEventCreateWithFlags(&w.ev_strip, hipEventDisableTiming | hipEventDisableSystemFence));
-  CBA_HIP(hipEventCreateWithFlags(&w.ev_mid, hipEventDisableTiming | hipEventDisableSystemFence));
+  CBA_TRY(w.ev_strip.create(hipEventDisableTiming | hipEventDisableSystemFence));
+  CBA_TRY(w.ev_mid.create(hipEventDisableTiming | hipEventDisableSystemFence));
   {
     const int ntc = n_pad / kInner;
     int rows = ntc < kTailMaxBlockRows ? ntc : kTailMaxBlockRows;
     if (flag_rows_blocks > rows) rows = flag_rows_blocks < ntc ? flag_rows_blocks : ntc;      // block-sparse launch: every grid block row has its flags
     const size_t words = (size_t)rows * ntc + 3 * (size_t)ntc;
-    CBA_HIP(hipMalloc(&w.tail_flags, sizeof(unsigned) * words));
+    CBA_TRY(w.tail_flags.alloc(words));
     CBA_HIP(hipMemset(w.tail_flags, 0, sizeof(unsigned) * words));
-    CBA_HIP(hipMalloc(&w.tail_ctrl, sizeof(unsigned) * kCtrlWords));
+    CBA_TRY(w.tail_ctrl.alloc(kCtrlWords));
     CBA_HIP(hipMemset(w.tail_ctrl, 0, sizeof(unsigned) * kCtrlWords));
     w.tail_rows_cap = rows * kInner;
     w.tail_epoch = 0;
-    CBA_HIP(hipEventCreate(&w.tail_e0));
-    CBA_HIP(hipEventCreate(&w.tail_e1));
-    CBA_HIP(hipMalloc(&w.back_xe, sizeof(double) * 2 * (size_t)n_pad));
+    CBA_TRY(w.tail_e0.create());
+    CBA_TRY(w.tail_e1.create());
+    CBA_TRY(w.back_xe.alloc(2 * (size_t)n_pad));
     CBA_HIP(hipMemset(w.back_xe, 0, sizeof(double) * 2 * (size_t)n_pad));
     w.back_epoch = 0;
   }
   w.n_alloc = n_pad;
   return CBA_OK;
 }
-void ldlt_workspace_free(LdltWorkspace& w) {
-  if (w.X) hipFree(w.X);
-  if (w.invLt) hipFree(w.invLt);
-  if (w.dvec) hipFree(w.dvec);
-  if (w.status) hipFree(w.status);
-  if (w.ev_strip) hipEventDestroy(w.ev_strip);
-  if (w.ev_mid) hipEventDestroy(w.ev_mid);
-  for (auto& sp : w.spans) { hipEventDestroy(sp.e0); hipEventDestroy(sp.e1); }
-  if (w.tail_flags) hipFree(w.tail_flags);
-  if (w.tail_ctrl) hipFree(w.tail_ctrl);
-  if (w.back_xe) hipFree(w.back_xe);
-  if (w.tail_e0) hipEventDestroy(w.tail_e0);
-  if (w.tail_e1) hipEventDestroy(w.tail_e1);
-  w = LdltWorkspace();
-}
 
 static int span_begin(LdltWorkspace& w, hipStream_t s) {
   if (w.spans_used == (int)w.spans.size()) {
     LdltWorkspace::Span sp;
-    CBA_HIP(hipEventCreate(&sp.e0)); CBA_HIP(hipEventCreate(&sp.e1));
-    w.spans.push_back(sp);
+    CBA_TRY(sp.e0.create()); CBA_TRY(sp.e1.create());
+    w.spans.push_back(std::move(sp));
   }
   CBA_HIP(hipEventRecord(w.spans[w.spans_used].e0, s));
   return CBA_OK;
@@ -2455,6 +2442,7 @@ struct RectArgs {
   int R0;               // first row
   int nrows;            // > 0: every group sends rows [R0, R0 + nrows) (a band); 0: rows [R0, end of the group) (the triangle)
 };
+static_assert(std::is_trivially_copyable_v<RectArgs>);
 // i-th column group of rank q in this transfer: first column, width, number of rows, offset in q's block of the buffer
 __host__ __device__ inline bool dist_rect(const RectArgs& a, int q, int i, int* col0, int* width, int* height, long long* off) {
   const int gq0 = a.g_begin + ((q - a.g_begin % a.world) % a.world + a.world) % a.world;
@@ -2741,6 +2729,7 @@ struct BackArgs {
   const unsigned long long* rowmask;   // optional [block row][mask_words]: bit c = tile (r, c) can be non-zero (grid-first order: the
   int mask_words;                      // grid x grid part of the factor is block-sparse); null = every tile
 };
+static_assert(std::is_trivially_copyable_v<BackArgs>);
 // Round 4: (1) a lane's 16 columns of a 64-column block are 8 jj + 2 q4 + {0, 1}, jj = 0 ... 7 -- one 16-byte load per jj, the four
 // lanes of a row read 64 contiguous bytes per instruction; with 16 consecutive columns per lane a wavefront-load touched 64 cache
 // lines and the strip loop, not the chain, set the pace: 0.56 -> 0.34 ms at BASELINE configs[1].  (2) x_c is double-buffered in

@@ -922,6 +922,7 @@ struct AccumLayout {
   int first_rig_tr_global, first_camera_tr_rig, first_points;
   int block_dof, block_size, dense_dof;
 };
+static_assert(std::is_trivially_copyable_v<AccumLayout>);
 
 // One wavefront walks kAccChunk consecutive observations.  Entries whose row AND column belong to the
 // imageset pose / rig pose ("hot": every observation of the same image and camera hits the same few

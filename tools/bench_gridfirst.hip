@@ -58,10 +58,10 @@ int main(int argc, char** argv) {
   hipMalloc(&x, sizeof(double) * n);
   hipMemcpy(F0, hF.data(), sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice);
   GfDevice g;
-  hipMalloc(&g.tasks, sizeof(GfTask) * pl.tasks.size()); hipMemcpy(g.tasks, pl.tasks.data(), sizeof(GfTask) * pl.tasks.size(), hipMemcpyHostToDevice);
-  hipMalloc(&g.ivals, sizeof(GfIval) * pl.ivals.size()); hipMemcpy(g.ivals, pl.ivals.data(), sizeof(GfIval) * pl.ivals.size(), hipMemcpyHostToDevice);
-  hipMalloc(&g.chains, sizeof(GfChain) * pl.chains.size()); hipMemcpy(g.chains, pl.chains.data(), sizeof(GfChain) * pl.chains.size(), hipMemcpyHostToDevice);
-  hipMalloc(&g.rowmask, sizeof(uint64_t) * pl.rowmask.size()); hipMemcpy(g.rowmask, pl.rowmask.data(), sizeof(uint64_t) * pl.rowmask.size(), hipMemcpyHostToDevice);
+  g.tasks.alloc(pl.tasks.size()); hipMemcpy(g.tasks, pl.tasks.data(), sizeof(GfTask) * pl.tasks.size(), hipMemcpyHostToDevice);
+  g.ivals.alloc(pl.ivals.size()); hipMemcpy(g.ivals, pl.ivals.data(), sizeof(GfIval) * pl.ivals.size(), hipMemcpyHostToDevice);
+  g.chains.alloc(pl.chains.size()); hipMemcpy(g.chains, pl.chains.data(), sizeof(GfChain) * pl.chains.size(), hipMemcpyHostToDevice);
+  g.rowmask.alloc(pl.rowmask.size()); hipMemcpy(g.rowmask, pl.rowmask.data(), sizeof(uint64_t) * pl.rowmask.size(), hipMemcpyHostToDevice);
   g.n_tasks0 = pl.n_tasks0; g.n_tasks1 = (int)pl.tasks.size() - pl.n_tasks0; g.n_chains = (int)pl.chains.size(); g.nbg = pl.nbg; g.nbf = pl.nbf;
   g.mask_words = pl.mask_words; g.flops_grid = pl.flops_grid;
   prepare_device_streams();

@@ -160,7 +160,7 @@ int main(int argc, char** argv) {
       if (rep == 1) hipMemcpyToSymbol(HIP_SYMBOL(g_helplog), &hl, sizeof(hl));
       GemmStats gs;
       hipEventRecord(e0, ms);
-      ldlt_tail(S, W > 0 ? k0 + W : n_fact, n, k0, w, ms, &gs, W > 0 ? w.X : nullptr);
+      ldlt_tail(S, W > 0 ? k0 + W : n_fact, n, k0, w, ms, &gs, W > 0 ? (double*)w.X : nullptr);
       hipEventRecord(e1, ms);
       printf("dataflow launch rows [%d, %d): %.3f ms\n", k0, W > 0 ? k0 + W : n_fact, timeit(e0, e1));
     }
@@ -346,7 +346,6 @@ int main(int argc, char** argv) {
              tail, t0, n_fact - t0, ms_t, tms, st, dx / xmax, dd / dmax, smax > 0 ? dS / smax : 0.0, nan ? "  NaN!" : "", g_launches, g_rate);
     }
     // residual of the solution with the last setting on small cases (host, O(n^2))
-    ldlt_workspace_free(w);
     hipFree(A); hipFree(S0); hipFree(S); hipFree(H); hipFree(x);
   }
   return 0;

@@ -9,8 +9,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcalib_ba_hip.so")
-SOURCES = ["cba_api.hip", "kernels_obs.hip", "kernels_linalg.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip"]
-HEADERS = ["cba_internal.h", "model.hip.h", "gridfirst_plan.h", os.path.join("..", "..", "include", "cba.h")]
+SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip",
+           "kernels_obs.hip", "kernels_linalg.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip"]
+HEADERS = ["cba_internal.h", "cba_problem.h", "model.hip.h", "gridfirst_plan.h", os.path.join("..", "..", "include", "cba.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]  # keep MFMA accumulators in VGPRs: no AGPR<->VGPR copies in the K loop
 

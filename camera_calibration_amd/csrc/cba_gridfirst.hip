@@ -1,0 +1,407 @@
+// Grid-first elimination order (gridfirst_plan.h) and its image sharding (section 6a): the system F and
+// the per-pass activity masks, the exchange between ranks, the tile order of the border update, the solve.
+#include <algorithm>
+#include <cstring>
+
+#include "cba_problem.h"
+
+namespace cba {
+
+// grid-first system: F and the plan's arrays, the tiles the forming kernel writes, the activity masks, the tile-list buffers
+int alloc_gridfirst_system(cba_problem* p) {
+  const GfPlan& g = p->gf.plan;
+  const size_t nf = (size_t)g.n_pad, wb = (size_t)(g.n_pad - g.Gf);
+  CBA_TRY(p->gf.F.alloc(nf * nf));
+  CBA_HIP(hipMemset(p->gf.F, 0, sizeof(double) * nf * nf));          // tiles outside the plan's structure stay zero for ever
+  CBA_TRY(p->gf.Xb.alloc((size_t)g.Gf * wb));
+  CBA_HIP(hipMemset(p->gf.Xb, 0, sizeof(double) * (size_t)g.Gf * wb));
+  CBA_TRY(p->gf.xF.alloc(nf));
+  CBA_TRY(p->gf.dev.tasks.alloc(g.tasks.size()));
+  CBA_TRY(p->gf.dev.ivals.alloc(g.ivals.size()));
+  CBA_TRY(p->gf.dev.chains.alloc(g.chains.size()));
+  CBA_TRY(p->gf.dev.rowmask.alloc(g.rowmask.size()));
+  CBA_HIP(hipMemcpy(p->gf.dev.tasks, g.tasks.data(), sizeof(GfTask) * g.tasks.size(), hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(p->gf.dev.ivals, g.ivals.data(), sizeof(GfIval) * g.ivals.size(), hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(p->gf.dev.chains, g.chains.data(), sizeof(GfChain) * g.chains.size(), hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(p->gf.dev.rowmask, g.rowmask.data(), sizeof(uint64_t) * g.rowmask.size(), hipMemcpyHostToDevice));
+  p->gf.dev.n_tasks0 = g.n_tasks0; p->gf.dev.n_tasks1 = (int)g.tasks.size() - g.n_tasks0; p->gf.dev.n_chains = (int)g.chains.size();
+  p->gf.dev.nbg = g.nbg; p->gf.dev.nbf = g.nbf; p->gf.dev.mask_words = g.mask_words; p->gf.dev.flops_grid = g.flops_grid;
+  // tiles the forming kernel writes per attempt: the structural tiles of the grid x grid part, the row strips of the grid rows
+  // (every border column block + the right-hand side's), the upper triangle of the border
+  // Rule: every tile that any launch of a solve WRITES is formed again for the next attempt (a broken solve -- zero pivot, NaN --
+  // must not leave anything behind: tests/test_gpu_gridfirst.py).  The dense border launch and the border update also write the
+  // padding-only block columns and the block rows behind the factored ones.
+  std::vector<int> tiles(g.grid_tiles);
+  for (int r = 0; r < g.nbg; ++r) {
+    for (int c = g.nbg; c < g.nbf; ++c) { tiles.push_back(r); tiles.push_back(c); }
+    tiles.push_back(r); tiles.push_back(g.ntc - 1);
+  }
+  for (int r = g.nbg; r < g.ntc; ++r)
+    for (int c = r; c < g.ntc; ++c) { tiles.push_back(r); tiles.push_back(c); }
+  p->gf.n_tiles = (int)(tiles.size() / 2);
+  CBA_TRY(p->gf.tiles.alloc(tiles.size()));
+  CBA_HIP(hipMemcpy(p->gf.tiles, tiles.data(), sizeof(int) * tiles.size(), hipMemcpyHostToDevice));
+  CBA_TRY(p->gf.grid_of_f.alloc(g.grid_of_f.size()));
+  CBA_HIP(hipMemcpy(p->gf.grid_of_f, g.grid_of_f.data(), sizeof(int) * g.grid_of_f.size(), hipMemcpyHostToDevice));
+  CBA_TRY(p->gf.f_of_grid.alloc(g.f_of_grid.size()));
+  CBA_HIP(hipMemcpy(p->gf.f_of_grid, g.f_of_grid.data(), sizeof(int) * g.f_of_grid.size(), hipMemcpyHostToDevice));
+  // activity of the row strips (per pass): bit sets over the grid block rows per 128-column border tile, and what is derived
+  {
+    GfDevice& d = p->gf.dev;
+    d.act_words = (g.nbg + 63) / 64;
+    d.n_act_tiles = (g.n_pad - g.Gf) / 128;
+    d.kmask_words = (g.Gf / 16 + 63) / 64;
+    CBA_TRY(d.act.alloc((size_t)d.n_act_tiles * d.act_words));
+    CBA_TRY(d.kmask.alloc((size_t)(g.n_pad / 128) * d.kmask_words));
+    CBA_HIP(hipMemset(d.kmask, 0, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words));
+    CBA_TRY(d.rowmask_dyn.alloc(g.rowmask.size()));
+    CBA_TRY(d.gridrow.alloc(g.gridrow.size()));
+    CBA_HIP(hipMemcpy(d.gridrow, g.gridrow.data(), sizeof(uint64_t) * g.gridrow.size(), hipMemcpyHostToDevice));
+    {
+      const size_t nt = (size_t)d.n_act_tiles;
+      // entries of four ints (tm, tn, K-slab range), eight interleaved per-XCD lists padded to the longest: 4 x 8 x (tiles in up to three
+      // parts each, dealt evenly) is a quarter of this
+      p->gf.tile_list_capacity = (size_t)32 * nt * (nt + 1) + 4096;
+      CBA_TRY(p->gf.tile_list.alloc(p->gf.tile_list_capacity));
+      CBA_TRY(p->gf.tile_list_host.alloc(p->gf.tile_list_capacity));
+    }
+    CBA_TRY(p->gf.kmask_host.alloc((size_t)(g.n_pad / 128) * d.kmask_words));
+    std::memset(p->gf.kmask_host, 0, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words);
+  }
+  return CBA_OK;
+}
+
+// Grid-first sharding: sum of the reduce buffer P over the ranks (cba_config.collective if set, else the all-reduce callback)
+static int gf_sum(cba_problem* p, int64_t count) {
+  CBA_HIP(hipStreamSynchronize(p->stream));
+  const int rc = p->cfg.collective ? p->cfg.collective(CBA_COLL_ALLREDUCE_SUM, p->P, p->P, count, p->cfg.collective_user)
+                                   : p->cfg.allreduce(p->P, count, p->cfg.allreduce_user);
+  if (rc != 0) { set_error("grid-first sharding: a collective callback failed"); return CBA_ERR_STATE; }
+  return CBA_OK;
+}
+// gsend (gblk doubles) of every rank into block r of grecv.  Without a collective callback: sums through P with zeros in the other
+// ranks' blocks, in chunks of P's size (exact: finite values and integer-valued mask halves)
+static int gf_allgather(cba_problem* p) {
+  const int64_t n = p->sh.gblk, total = n * p->sh.world, own0 = n * p->sh.rank;
+  if (p->cfg.collective) {
+    CBA_HIP(hipStreamSynchronize(p->stream));
+    if (p->cfg.collective(CBA_COLL_ALLGATHER, p->sh.gsend, p->sh.grecv, n, p->cfg.collective_user) != 0) {
+      set_error("grid-first sharding: a collective callback failed"); return CBA_ERR_STATE;
+    }
+    return CBA_OK;
+  }
+  for (int64_t c0 = 0; c0 < total; c0 += p->P_cap) {
+    const int64_t len = std::min<int64_t>(p->P_cap, total - c0);
+    CBA_HIP(hipMemsetAsync(p->P, 0, sizeof(double) * (size_t)len, p->stream));
+    const int64_t a = std::max(c0, own0), b = std::min(c0 + len, own0 + n);
+    if (a < b) CBA_HIP(hipMemcpyAsync(p->P + (a - c0), p->sh.gsend + (a - own0), sizeof(double) * (size_t)(b - a), hipMemcpyDeviceToDevice, p->stream));
+    CBA_TRY(gf_sum(p, len));
+    CBA_HIP(hipMemcpyAsync(p->sh.grecv + c0, p->P, sizeof(double) * (size_t)len, hipMemcpyDeviceToDevice, p->stream));
+  }
+  return CBA_OK;
+}
+// The exchange of one Gauss-Newton step (after the accumulation; the activity words of this rank's observations are in gfd.act):
+//   1. shared blocks: H_dd / b_d packed (k_gf_shared), summed over the ranks, unpacked into H_dd / b_d -- launch_gf_form reads them as
+//      it reads a single process's accumulator;
+//   2. pose rows and activity words: gathered, the pose rows placed rank-major into gDblk / gbblk / gB, the words OR-ed;
+//   3. closure and masks of the union (the single-process masks up to the order of the pose columns), their host copy.
+static int gf_exchange(cba_problem* p) {
+  const Layout& L = p->L;
+  const GfPlan& g = p->gf.plan;
+  GfDevice& d = p->gf.dev;
+  hipStream_t s = p->stream;
+  const int ld = p->n_pad;
+  CBA_TRY(launch_gf_shared(p->sh.shared, p->sh.shared_col, p->Hdd, ld, p->bd, p->P, 0, s));
+  CBA_TRY(gf_sum(p, p->sh.shared.doubles));
+  CBA_TRY(launch_gf_shared(p->sh.shared, p->sh.shared_col, p->Hdd, ld, p->bd, p->P, 1, s));
+  const int nw = d.n_act_tiles * d.act_words, M = p->sh.max_local, nloc = L.n_images;
+  const int64_t oD = 2 * (int64_t)nw, ob = oD + 36 * (int64_t)M, oB = ob + 6 * (int64_t)M;
+  CBA_TRY(launch_gf_words_to_doubles(d.act, nw, p->sh.gsend, s));
+  if (nloc > 0) {
+    CBA_HIP(hipMemcpyAsync(p->sh.gsend + oD, p->Dblk, sizeof(double) * 36 * (size_t)nloc, hipMemcpyDeviceToDevice, s));
+    CBA_HIP(hipMemcpyAsync(p->sh.gsend + ob, p->bblk, sizeof(double) * 6 * (size_t)nloc, hipMemcpyDeviceToDevice, s));
+    CBA_HIP(hipMemcpyAsync(p->sh.gsend + oB, p->B, sizeof(double) * 6 * (size_t)nloc * ld, hipMemcpyDeviceToDevice, s));
+  }
+  CBA_TRY(gf_allgather(p));
+  for (int r = 0; r < p->sh.world; ++r) {
+    const size_t cnt = (size_t)p->sh.counts[r], off = (size_t)p->sh.offsets[r];
+    if (!cnt) continue;
+    const double* src = p->sh.grecv + (size_t)r * p->sh.gblk;
+    CBA_HIP(hipMemcpyAsync(p->sh.gDblk + 36 * off, src + oD, sizeof(double) * 36 * cnt, hipMemcpyDeviceToDevice, s));
+    CBA_HIP(hipMemcpyAsync(p->sh.gbblk + 6 * off, src + ob, sizeof(double) * 6 * cnt, hipMemcpyDeviceToDevice, s));
+    CBA_HIP(hipMemcpyAsync(p->sh.gB + 6 * off * ld, src + oB, sizeof(double) * 6 * cnt * ld, hipMemcpyDeviceToDevice, s));
+  }
+  CBA_TRY(launch_gf_or_words(p->sh.grecv, p->sh.world, p->sh.gblk, nw, d.act, s));
+  CBA_TRY(launch_gf_close_masks(d.n_act_tiles, d.act_words, g.nbg, g.nbf, d.gridrow, d.act, d.kmask, d.kmask_words, g.Gf / 128, d.rowmask,
+                                d.rowmask_dyn, d.mask_words, s));
+  CBA_HIP(hipMemcpyAsync(p->gf.kmask_host, d.kmask, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words, hipMemcpyDeviceToHost, s));
+  return CBA_OK;
+}
+
+// image sharding with the grid-first order: the imagesets of every rank (the one collective of cba_create; every rank computes
+// the same plan, so all of them get here), the pose rows of all ranks, the all-gather staging, the band columns of the shared blocks
+int setup_gf_sharding(cba_problem* p) {
+  if (!p->gf_sharded) return CBA_OK;
+  const Layout& L = p->L;
+  const int W = p->sh.world;
+  if (p->P_cap < W) { set_error("reduce_buffer too small"); return CBA_ERR_ARG; }
+  std::vector<double> cnt(W, 0.0);
+  cnt[p->sh.rank] = (double)L.n_images;
+  CBA_HIP(hipMemcpy(p->P, cnt.data(), sizeof(double) * W, hipMemcpyHostToDevice));
+  CBA_TRY(gf_sum(p, W));
+  CBA_HIP(hipMemcpy(cnt.data(), p->P, sizeof(double) * W, hipMemcpyDeviceToHost));
+  p->sh.counts.assign(W, 0); p->sh.offsets.assign(W, 0);
+  int total = 0;
+  for (int r = 0; r < W; ++r) {
+    p->sh.counts[r] = (int)cnt[r]; p->sh.offsets[r] = total; total += p->sh.counts[r];
+    p->sh.max_local = std::max(p->sh.max_local, p->sh.counts[r]);
+  }
+  if (total != p->gf.plan.n_images || p->sh.counts[p->sh.rank] != L.n_images) {
+    set_error("cba_create: grid-first sharding: the imagesets of the ranks do not add up to n_images_global"); return CBA_ERR_ARG;
+  }
+  p->sh.img0 = p->sh.offsets[p->sh.rank];
+  const size_t Ng = (size_t)total, ld = (size_t)p->n_pad;
+  CBA_TRY(p->sh.gDblk.alloc(36 * Ng));
+  CBA_TRY(p->sh.gbblk.alloc(6 * Ng));
+  CBA_TRY(p->sh.gB.alloc(6 * Ng * ld));
+  const GfDevice& d = p->gf.dev;
+  p->sh.gblk = 2 * (int64_t)d.n_act_tiles * d.act_words + (int64_t)p->sh.max_local * (42 + 6 * (int64_t)ld);
+  CBA_TRY(p->sh.gsend.alloc((size_t)p->sh.gblk));
+  CBA_HIP(hipMemset(p->sh.gsend, 0, sizeof(double) * (size_t)p->sh.gblk));
+  CBA_TRY(p->sh.grecv.alloc((size_t)p->sh.gblk * W));
+  // band position -> engine dense column (the engine's grid order is the plan's elimination order, build_grid_order)
+  std::vector<int> col(p->sh.shared.ref_col.size());
+  for (size_t k = 0; k < col.size(); ++k) col[k] = p->dense_perm_host[p->sh.shared.ref_col[k]];
+  CBA_TRY(p->sh.shared_col.alloc(col.size()));
+  CBA_HIP(hipMemcpy(p->sh.shared_col, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
+  return CBA_OK;
+}
+
+// Jacobian pass, side stream: which grid block rows each 128-column tile of the border can reach in THIS pass (the control patch of an
+// observation sits under its projected pixel), closed under the fill of the grid factor, and the masks derived from it -- on
+// the side stream behind the per-cell accumulation, underneath the strips kernel of the main stream (waited for at the end of the pass)
+int gridfirst_pass_activity(cba_problem* p, const PassArgs& a, hipStream_t aux) {
+  const Layout& L = p->L;
+  const GfPlan& g = p->gf.plan;
+  GfDevice& d = p->gf.dev;
+  if (p->gf_sharded) {        // this rank's rows only (pose columns at their global tiles): the union and the masks follow the exchange
+    CBA_TRY(launch_gf_touch(a, p->flags, p->cells, p->img_start, L.n_images, p->gf.f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
+                            d.n_act_tiles, d.act_words, p->sh.img0, d.act, aux));
+  } else {
+    CBA_TRY(launch_gf_activity(a, p->flags, p->cells, p->img_start, L.n_images, p->gf.f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
+                               d.n_act_tiles, d.act_words, g.nbg, g.nbf, d.gridrow, d.act, d.kmask, d.kmask_words, g.Gf / 128, d.rowmask, d.rowmask_dyn,
+                               d.mask_words, aux));
+    CBA_HIP(hipMemcpyAsync(p->gf.kmask_host, d.kmask, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words, hipMemcpyDeviceToHost, aux));
+  }
+  return CBA_OK;
+}
+// End of a Jacobian pass: image sharding exchanges the accumulated system and the activity words
+int gridfirst_pass_end(cba_problem* p) { return p->gf_sharded ? gf_exchange(p) : CBA_OK; }
+
+// Order in which the border update hands out its 128 x 128 tiles (GemmArgs::tile_list): workgroup b of the launch runs on XCD b % 8 and
+// the dispatcher hands workgroups out strictly in order, so (a) the list as a whole is sorted by executed K slabs, heaviest first --
+// list scheduling: the light tiles fill the gaps behind the heavy ones, and every XCD (every eighth entry) sees the same sequence of
+// weights, which keeps the in-order dispatcher from waiting for one XCD -- and (b) inside a run of tiles of about the same weight (7 %
+// buckets) the tiles are dealt so that one XCD walks a CONTIGUOUS piece of the run in row-major order: its tiles in flight share an A
+// panel and neighbouring B panels in that XCD's L2 instead of 64 unrelated pairs (FETCH_SIZE of the launch:
+// profiles/r06_update_tile_order.txt).  Short lists are padded with (-1, -1) (the workgroup leaves).  weight(tm, tn): executed K slabs
+// (or anything proportional) of upper tile (tm, tn), tm <= tn < nt.  Host work; the list is uploaded by the next solve.
+// A tile with all K slabs runs for most of the launch (2.7 of 3.5 ms at BASELINE configs[1]); tiles heavier than a third of the heaviest
+// are therefore handed out in PARTS (K ranges with equal shares of the executed slabs, GemmArgs::tile_list) that add to C atomically --
+// not in the deterministic mode, where the additions must keep one order.  split(tm, tn, target): the K slab in front of which
+// `target` units of the tile's weight lie; n_slabs: K slabs of the launch.
+template <class Weight, class Split>
+static void gf_build_tile_list(cba_problem* p, int nt, int n_slabs, Weight weight, Split split) {
+  struct Tile { int w, tm, tn, s0, s1; };
+  std::vector<Tile> all;
+  all.reserve((size_t)nt * (nt + 1));
+  int w_max = 0;
+  for (int tm = 0; tm < nt; ++tm)
+    for (int tn = tm; tn < nt; ++tn) { const int w = weight(tm, tn); all.push_back(Tile{w, tm, tn, 0, 0}); w_max = std::max(w_max, w); }
+  // (image sharding: not either -- every rank must factor F bit for bit alike, or the replicas' LM decisions and collectives part)
+  if (!p->cfg.deterministic && !p->gf_sharded) {
+    // unit: a third of the heaviest tile (measured at BASELINE configs[1] / [2] / [3], launch ms with units of 1/2, 1/3, 1/4, 1/6:
+    // 3.31 / 3.31 / 3.26 / 3.26, 12.17 / 12.03 / 12.09 / 12.18, 5.40 / 5.27 / 5.37 / 5.41; whole tiles: 3.50 / 12.34 / 5.53)
+    const int unit = std::max(8, w_max / 3);
+    const size_t n0 = all.size();
+    for (size_t i = 0; i < n0; ++i) {
+      const int w = all[i].w, parts = (w + unit - 1) / unit;
+      if (parts < 2) continue;
+      int prev = 0, done = 0;
+      bool ok = true;
+      std::vector<Tile> add;
+      for (int q = 1; q < parts && ok; ++q) {
+        const int target = (int)((long long)w * q / parts);
+        const int sq = split(all[i].tm, all[i].tn, target);
+        if (sq <= prev || sq >= n_slabs) { ok = false; break; }
+        add.push_back(Tile{target - done, all[i].tm, all[i].tn, prev, sq});
+        prev = sq; done = target;
+      }
+      if (!ok) continue;
+      add.push_back(Tile{w - done, all[i].tm, all[i].tn, prev, n_slabs});
+      all[i] = add[0];
+      for (size_t q = 1; q < add.size(); ++q) all.push_back(add[q]);
+    }
+  }
+  std::stable_sort(all.begin(), all.end(), [](const Tile& u, const Tile& v) { return u.w > v.w; });      // row-major among equals
+  std::vector<Tile> lists[8];
+  size_t i0 = 0;
+  while (i0 < all.size()) {
+    size_t i1 = i0 + 1;
+    while (i1 < all.size() && (double)all[i1].w >= 0.93 * all[i0].w) ++i1;                               // one bucket
+    std::stable_sort(all.begin() + i0, all.begin() + i1, [](const Tile& u, const Tile& v) { return u.tm != v.tm ? u.tm < v.tm : (u.tn != v.tn ? u.tn < v.tn : u.s0 < v.s0); });
+    const size_t L = i1 - i0;
+    int start = 0;
+    for (int x = 1; x < 8; ++x) if (lists[x].size() < lists[start].size()) start = x;
+    size_t pos = i0;
+    for (int k = 0; k < 8; ++k) {
+      const size_t len = L / 8 + ((size_t)k < L % 8 ? 1 : 0);
+      std::vector<Tile>& dst = lists[(start + k) % 8];
+      dst.insert(dst.end(), all.begin() + pos, all.begin() + pos + len);
+      pos += len;
+    }
+    i0 = i1;
+  }
+  size_t longest = 0;
+  for (int x = 0; x < 8; ++x) longest = std::max(longest, lists[x].size());
+  if (4 * 8 * longest > p->gf.tile_list_capacity) return;      // (cannot happen with the sizing of cba_create; the previous list stays)
+  p->gf.tile_list_entries = (int)(8 * longest);
+  for (size_t i = 0; i < longest; ++i)
+    for (int x = 0; x < 8; ++x) {
+      const bool have = i < lists[x].size();
+      int* e = p->gf.tile_list_host + 4 * (8 * i + x);
+      e[0] = have ? lists[x][i].tm : -1; e[1] = have ? lists[x][i].tn : -1;
+      e[2] = have ? lists[x][i].s0 : 0; e[3] = have ? lists[x][i].s1 : 0;
+    }
+  p->gf.tile_list_valid = true;
+  p->gf.tile_list_dirty = true;
+}
+
+// Grid-first order: F formed from the accumulated parts, block-sparse launch of the grid rows, border update, dense border,
+// masked back substitution, x back in the engine's layout -- between the status words and the status launch of solve_enqueue.
+// Timers: kTimerProduct = the border update (the K = Gf product), kTimerFactor = the whole factorisation.
+int gridfirst_enqueue(cba_problem* p, double lambda) {
+  const Layout& L = p->L;
+  const GfPlan& g = p->gf.plan;
+  const int ld = g.n_pad;
+  CBA_TRY(ldlt_clear_ctrl(p->ldlt, p->stream));
+  const GfDevice& d = p->gf.dev;
+  // (image sharding: H_dd / b_d hold the sums over the ranks, the pose rows of all ranks are in gDblk / gbblk / gB -- gf_exchange)
+  const bool sh = p->gf_sharded;
+  CBA_TRY(launch_gf_form(p->gf.F, ld, g.Gf, g.n_rp, g.n_border, p->gf.grid_of_f, p->Hdd, p->n_pad, p->bd, sh ? p->sh.gB : p->B, sh ? p->sh.gDblk : p->Dblk,
+                         sh ? p->sh.gbblk : p->bblk, lambda, p->gf.tiles, p->gf.n_tiles, d.act, d.act_words, p->stream));
+  GemmStats gs;
+  CBA_TRY(timer_begin(p, kTimerFactor));
+  const int* tile_list = nullptr;
+  if (p->gf.tile_list_valid) {
+    if (p->gf.tile_list_dirty) {      // (rebuilt by gridfirst_finish behind a stream wait: nothing in flight reads the device copy)
+      CBA_HIP(hipMemcpyAsync(p->gf.tile_list, p->gf.tile_list_host, sizeof(int) * 4 * (size_t)p->gf.tile_list_entries, hipMemcpyHostToDevice, p->stream));
+      p->gf.tile_list_dirty = false;
+    }
+    tile_list = p->gf.tile_list;
+  }
+  CBA_TRY(ldlt_factor_gridfirst(p->gf.F, g.n_fact, ld, d, p->gf.Xb, ld - g.Gf, p->ldlt, p->stream, &gs, d.kmask, d.kmask_words, tile_list,
+                                tile_list ? p->gf.tile_list_entries : 0));
+  CBA_TRY(timer_end(p, kTimerFactor, gs.flops, 0, gs.launches));
+  CBA_TRY(ldlt_back_solve(p->gf.F, g.n_fact, ld, ld - 1, p->ldlt, p->gf.xF, p->stream, d.rowmask_dyn, d.mask_words));
+  CBA_TRY(launch_gf_scatter(p->gf.xF, g.Gf, g.n_rp, L.block_dof, g.G, p->gf.f_of_grid, sh ? 6 * p->sh.img0 : 0, p->x, p->stream));
+  return CBA_OK;
+}
+
+// Behind the host's wait for the solve: the executed flops of the border update, the tile order of the next ones
+void gridfirst_finish(cba_problem* p) {
+  // executed K slabs of the border update (masks of this pass, copied on the side stream during the pass): the launch's flops
+  const GfPlan& g = p->gf.plan;
+  const int kw = p->gf.dev.kmask_words, t0 = g.Gf / 128, nt = (g.n_pad - g.Gf) / 128;
+  auto row = [&](int t) { return p->gf.kmask_host + (size_t)(t0 + t) * kw; };      // K-slab mask of border tile t
+  double slabs = 0;
+  for (int tm = 0; tm < nt; ++tm)
+    for (int tn = tm; tn < nt; ++tn) slabs += common_slabs(row(tm), row(tn), kw);
+  p->gf.update_flops = slabs * 2.0 * 128 * 128 * 16;
+  {
+    LdltWorkspace& w = p->ldlt;
+    for (int i = 0; i < w.spans_used; ++i)
+      if (w.spans[i].masked_update) { w.spans[i].flops = p->gf.update_flops; w.spans[i].masked_update = false; }
+  }
+  // Tile order of the NEXT border updates (gf_build_tile_list; host work while the device idles)
+  // (cba_set_observations leaves a first list predicted from the measured pixels; the first solve's masks replace it, then every 8th)
+  ++p->gf.tile_list_age;
+  if (!p->gf.tile_list_valid || p->gf.tile_list_age == 1 || (p->gf.tile_list_age & 7) == 0)
+    gf_build_tile_list(p, nt, g.Gf / 16, [&](int tm, int tn) { return common_slabs(row(tm), row(tn), kw); }, [&](int tm, int tn, int target) {
+      int seen = 0;
+      for (int w = 0; w < kw; ++w) {
+        const unsigned long long bits = row(tm)[w] & row(tn)[w];
+        const int c = __builtin_popcountll(bits);
+        if (seen + c < target) { seen += c; continue; }
+        for (int b = 0; b < 64; ++b)
+          if ((bits >> b) & 1ull) { if (seen == target) return 64 * w + b; ++seen; }
+        return 64 * (w + 1);
+      }
+      return 0;
+    });
+}
+
+// ---- block order of the imagesets (cba_set_observations): refinement of the Z-order `order` (order_imagesets) ----
+// Grid-first order: the pose columns of F are empty in the grid block rows the imageset does not reach (per-pass activity,
+// k_gf_touch), per 128-column tile = ~21 imagesets.  Imagesets are ordered by the first row of F their control patches touch
+// (under the MEASURED pixels: a heuristic, the activity itself comes from the projected ones), so that the imagesets of a tile
+// start at about the same place of the elimination order and their union stays small.
+void order_imagesets_gridfirst(cba_problem* p, int64_t n, const float* xy, const int32_t* image_index, const int32_t* camera_index,
+                                      std::vector<int>& order) {
+  const Layout& L = p->L;
+  const GfPlan& g = p->gf.plan;
+  const int W = g.grid_words;
+  std::vector<uint64_t> touched((size_t)L.n_images * W, 0ull);
+  for (int64_t i = 0; i < n; ++i) {
+    const int img = image_index[i], cam = camera_index[i];
+    const cba_camera& cm = p->cams[cam];
+    const int per = unknowns_per_point(cm.model_type);
+    for_each_control_point(cm, xy[2 * i], xy[2 * i + 1], [&](int cx, int cy) {
+      const int e = L.intr_offset[cam] - g.n_rp + per * g.gperm[cam][cx + (size_t)cy * cm.grid_w];
+      const int r0 = g.f_of_grid[e] >> 6, r1 = g.f_of_grid[e + per - 1] >> 6;
+      touched[(size_t)img * W + (r0 >> 6)] |= 1ull << (r0 & 63);
+      touched[(size_t)img * W + (r1 >> 6)] |= 1ull << (r1 & 63);
+    });
+  }
+  std::vector<int> slot_of;
+  gf_order_imagesets(g, touched, L.n_images, g.n_rp + 6 * p->sh.img0, &slot_of);      // (sharding: this rank's slots of the border)
+  for (int i = 0; i < L.n_images; ++i) order[slot_of[i]] = i;
+  // First tile order of the border update, predicted from the same rows (the first solve would otherwise run its tiles in
+  // row-major order: 4.7 instead of 3.5 ms at BASELINE configs[1]): per 128-column tile of the border the union of its imagesets'
+  // rows, closed under the fill of the grid factor; rig / point tiles and the right-hand side's tile reach every row.
+  if (p->gf.tile_list_host) {
+    const int nt = (g.n_pad - g.Gf) / 128;
+    std::vector<uint64_t> tact((size_t)nt * W, 0ull);
+    auto all_rows = [&](int t) { for (int w = 0; w < W; ++w) tact[(size_t)t * W + w] = ~0ull; };
+    for (int t = 0; t < nt && 128 * t < g.n_rp; ++t) all_rows(t);
+    all_rows(nt - 1);
+    if (p->gf_sharded) for (int t = 0; t < nt; ++t) all_rows(t);        // (the other ranks' rows are not known here: dense)
+    for (int i = 0; i < L.n_images; ++i)
+      for (int t : {(g.n_rp + 6 * slot_of[i]) >> 7, (g.n_rp + 6 * slot_of[i] + 5) >> 7})
+        for (int w = 0; w < W; ++w) tact[(size_t)t * W + w] |= touched[(size_t)i * W + w];
+    for (int t = 0; t < nt; ++t) {
+      uint64_t* a = &tact[(size_t)t * W];
+      for (int r = 0; r < g.nbg; ++r)
+        if ((a[r >> 6] >> (r & 63)) & 1ull)
+          for (int w = r >> 6; w < W; ++w) a[w] |= g.gridrow[(size_t)r * W + w];
+      for (int w = 0; w < W; ++w)
+        if (64 * w + 64 > g.nbg) a[w] &= (64 * w >= g.nbg) ? 0ull : (~0ull >> (64 - (g.nbg - 64 * w)));
+    }
+    gf_build_tile_list(p, nt, g.Gf / 16, [&](int tm, int tn) {
+      int rows = 0;
+      for (int w = 0; w < W; ++w) rows += __builtin_popcountll(tact[(size_t)tm * W + w] & tact[(size_t)tn * W + w]);
+      return 4 * rows;                                   // K slabs of 16 rows: four per block row
+    }, [&](int tm, int tn, int target) {
+      int seen = 0;
+      for (int r = 0; r < g.nbg; ++r)
+        if (((tact[(size_t)tm * W + (r >> 6)] & tact[(size_t)tn * W + (r >> 6)]) >> (r & 63)) & 1ull) {
+          if (seen + 4 > target) return 4 * r;
+          seen += 4;
+        }
+      return 0;
+    });
+    p->gf.tile_list_age = 0;
+  }
+}
+
+}  // namespace cba

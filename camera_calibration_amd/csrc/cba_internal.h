@@ -3,11 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <chrono>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/cba.h"
+#include "gridfirst_plan.h"
 #include "model.hip.h"
 
 namespace cba {
@@ -139,6 +141,29 @@ struct PassArgs {
 };
 static_assert(std::is_trivially_copyable_v<PassArgs>);
 
+// ---- small host helpers ----
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+inline double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+inline bool camera_ok(const cba_camera& c) {
+  return (c.model_type == CBA_CENTRAL_GENERIC || c.model_type == CBA_NONCENTRAL_GENERIC) && c.grid_w >= 4 && c.grid_h >= 4 &&
+         c.calib_max_x >= c.calib_min_x && c.calib_max_y >= c.calib_min_y;
+}
+// per control point of a camera's grid: unknowns of the optimisation / doubles of the stored grid
+inline int unknowns_per_point(int model_type) { return model_type == CBA_CENTRAL_GENERIC ? 2 : 5; }
+inline int doubles_per_point(int model_type) { return model_type == CBA_CENTRAL_GENERIC ? 3 : 6; }
+
+// ---- cba_setup.hip ----
+struct LdltWorkspace;
+#pragma GCC visibility push(hidden)      // (shared by the cba_* units only: not in the library's dynamic symbol table)
+void padded_dims(int dd, int* n_pad, int* n_fact);
+CamDev make_camdev(const cba_camera& c, const double* grid, const double* tangents, int intr_offset, const int* gperm = nullptr);
+// makes `device` current; error messages start with `prefix`
+int select_device(int device, const char* prefix);
+void apply_solver_options(LdltWorkspace& w, const cba_solver_options* o);
+#pragma GCC visibility pop
+
 // ---- kernels_obs.hip ----
 int launch_compose_poses(const DevState& st, int N, int C, double* itg, hipStream_t s);
 int launch_tangents(const double* dir_grid, double* tang, int G, hipStream_t s);
@@ -218,7 +243,7 @@ struct LdltWorkspace {
   DevBuf<double> dvec;       // n
   DevBuf<int> status;
   // the device's side streams (shared, not owned): high-priority / two plain ones.  The factorisation itself runs on the caller's
-  // stream; users: the exchanges of the distributed variant, the Jacobian pass' side work (cba_api.hip)
+  // stream; users: the exchanges of the distributed variant, the Jacobian pass' side work (cba_passes.hip)
   hipStream_t panel_stream = nullptr, mid_stream = nullptr, far_stream = nullptr;
   Event ev_strip, ev_mid;
   size_t n_alloc = 0;
@@ -248,7 +273,6 @@ int ldlt_factor(double* S, int n, int ld, LdltWorkspace& w, hipStream_t s, GemmS
 int ldlt_back_solve(const double* S, int n_fact, int ld, int zcol, const LdltWorkspace& w, double* x, hipStream_t s,
                     const unsigned long long* rowmask = nullptr, int mask_words = 0);
 // Grid-first elimination (gridfirst_plan.h): device copies of the plan's arrays
-struct GfTask; struct GfIval; struct GfChain;
 struct GfDevice {
   DevBuf<GfTask> tasks; DevBuf<GfIval> ivals; DevBuf<GfChain> chains;
   int n_tasks0 = 0, n_tasks1 = 0, n_chains = 0;
@@ -284,5 +308,44 @@ struct DistComm {
 };
 size_t ldlt_dist_buffer_doubles(int n_pad, int world);
 int ldlt_factor_distributed(double* S, int n, int ld, LdltWorkspace& w, hipStream_t s, const DistComm& c, GemmStats* trailing_stats);
+int launch_dinv_times_B_ld(const double* Dinv, const double* B, int bs, int nb, int dd, int ld, double* W, hipStream_t s);
+int launch_gemv_t_partial(const double* M, int K, int n, int ld, const double* v, double* partial_ws, hipStream_t s);
+int launch_gemv_t_final(int n, const double* base, double* y, int ystride, const double* partial_ws, int n_zero, hipStream_t s);
+int launch_gemv_t_strided(const double* M, int K, int n, int ld, const double* v, const double* base, double* y,
+                          int ystride, double* partial_ws, hipStream_t s);
+int gemv_t_workspace_doubles(int n);
+// (the definition carries the defaults chunk_order = nullptr, keep_col = -1; callers in other units pass both)
+int schur_gemm(const double* A, const double* B, int Kpad, int ldab, const double* Cin, double* C, int n_pad, int ld,
+               int n_real, int add_diag, double lambda, const unsigned long long* kmask, hipStream_t s, const int* chunk_order,
+               int keep_col);
+int schur_chunk_count(int n_pad);
+void schur_chunk_order(const unsigned long long* mask_host, int n_pad, int Kpad, int* order);
+int schur_mask_words(int Kpad);
+int schur_slab_rows();
+int launch_touch_mask(const double* B, int Kpad, int n_pad, int ld, unsigned long long* mask, hipStream_t s);
+int launch_finish_diag(double* S, int ld, int n_real, int n_pad, double lambda, hipStream_t s);
+int launch_diag_sum(const double* Dblk, int bs, int nb, const double* Hdd, int ld, int dd, double* out, hipStream_t s);
+int make_main_stream(hipStream_t* s);
+int prepare_device_streams();
+int64_t packed_upper_doubles(int n_pad);
+int launch_pack_upper(const double* S, int n_pad, double* P, int unpack, hipStream_t s);
+
+// ---- kernels_gridfirst.hip ----
+int launch_gf_form(double* F, int ldf, int Gf, int n_rp, int n_border, const int* grid_of_f, const double* Hdd, int ldh, const double* bd,
+                   const double* B, const double* Dblk, const double* bblk, double lambda, const int* tiles, int n_tiles,
+                   const unsigned long long* act, int act_words, hipStream_t s);
+int launch_gf_activity(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
+                       int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
+                       unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
+                       int mask_words, hipStream_t s);
+int launch_gf_touch(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
+                    int n_rp, int rig_dof, int n_tiles, int words, int slot0, unsigned long long* act, hipStream_t s);
+int launch_gf_close_masks(int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
+                          unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
+                          int mask_words, hipStream_t s);
+int launch_gf_scatter(const double* xF, int Gf, int n_rp, int block_dof, int G, const int* f_of_grid, int pose0, double* x, hipStream_t s);
+int launch_gf_shared(const GfShared& L, const int* col, double* Hdd, int ld, double* bd, double* buf, int unpack, hipStream_t s);
+int launch_gf_words_to_doubles(const unsigned long long* w, int n, double* out, hipStream_t s);
+int launch_gf_or_words(const double* blocks, int world, long long block_stride, int n, unsigned long long* w, hipStream_t s);
 
 }  // namespace cba

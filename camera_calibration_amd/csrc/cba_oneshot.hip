@@ -1,0 +1,292 @@
+// Entry points of the C ABI (include/cba.h) that need no cba_problem: the device-resident camera model, the one-shot
+// projection / un-projection wrappers, the stand-alone Schur solve, the grid-first plan query and the grid-only fit.
+#include <cstring>
+#include <memory>
+
+#include "cba_internal.h"
+
+using namespace cba;
+
+extern "C" {
+
+// ---- model-level entry points: device-resident camera model -----------------------------------------
+struct cba_model {
+  cba_camera cam{};
+  int device = 0;
+  DevBuf<double> d_grid; DevBuf<CamDev> d_cam;
+  // scratch, grown on demand
+  int64_t cap = 0;
+  DevBuf<double> d_a, d_b, d_c, d_j; DevBuf<uint8_t> d_ok;
+};
+static int model_reserve(cba_model* m, int64_t n) {
+  if (n <= m->cap) return CBA_OK;
+  m->cap = 0;
+  const int64_t cap = n < 256 ? 256 : n;
+  CBA_TRY(m->d_a.alloc(3 * (size_t)cap));     // local points / pixels (in)
+  CBA_TRY(m->d_b.alloc(6 * (size_t)cap));     // pixels / lines (out)
+  CBA_TRY(m->d_c.alloc(2 * (size_t)cap));     // initial pixels
+  CBA_TRY(m->d_j.alloc(12 * (size_t)cap));    // un-projection Jacobians
+  CBA_TRY(m->d_ok.alloc((size_t)cap));
+  m->cap = cap;
+  return CBA_OK;
+}
+void cba_model_destroy(cba_model* m) {
+  if (!m) return;
+  hipSetDevice(m->device);      // current while the members free their memory
+  delete m;
+}
+
+int cba_model_set_grid(cba_model* m, const double* grid) {
+  if (!m || !grid) { set_error("cba_model_set_grid: bad argument"); return CBA_ERR_ARG; }
+  CBA_HIP(hipSetDevice(m->device));
+  const size_t G = (size_t)m->cam.grid_w * m->cam.grid_h;
+  CBA_HIP(hipMemcpy(m->d_grid, grid, doubles_per_point(m->cam.model_type) * G * sizeof(double), hipMemcpyHostToDevice));
+  return CBA_OK;
+}
+int cba_model_create(const cba_camera* camera, const double* grid, int32_t device, cba_model** out) {
+  if (!camera || !grid || !out || !camera_ok(*camera)) { set_error("bad camera / grid"); return CBA_ERR_ARG; }
+  CBA_TRY(select_device(device, ""));
+  std::unique_ptr<cba_model, decltype(&cba_model_destroy)> m(new cba_model(), &cba_model_destroy);
+  m->cam = *camera; m->device = device;
+  const size_t G = (size_t)camera->grid_w * camera->grid_h;
+  CBA_TRY(m->d_grid.alloc(doubles_per_point(camera->model_type) * G));
+  CBA_TRY(cba_model_set_grid(m.get(), grid));
+  CamDev h = make_camdev(*camera, m->d_grid, nullptr, 0);
+  CBA_TRY(m->d_cam.alloc(1));
+  CBA_HIP(hipMemcpy(m->d_cam, &h, sizeof(CamDev), hipMemcpyHostToDevice));
+  *out = m.release();
+  return CBA_OK;
+}
+int cba_model_project(cba_model* m, int64_t n, const double* local_points, const double* init_pixels, double* pixels, uint8_t* ok) {
+  if (!m || n < 0 || (n > 0 && (!local_points || !pixels || !ok))) { set_error("cba_model_project: bad argument"); return CBA_ERR_ARG; }
+  if (n == 0) return CBA_OK;
+  CBA_HIP(hipSetDevice(m->device));
+  CBA_TRY(model_reserve(m, n));
+  CBA_HIP(hipMemcpy(m->d_a, local_points, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+  if (init_pixels) CBA_HIP(hipMemcpy(m->d_c, init_pixels, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+  CBA_TRY(launch_project_points(m->d_cam, m->cam.model_type, n, m->d_a, init_pixels ? (const double*)m->d_c : nullptr, m->d_b, m->d_ok, nullptr));
+  CBA_HIP(hipMemcpy(pixels, m->d_b, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
+  CBA_HIP(hipMemcpy(ok, m->d_ok, (size_t)n, hipMemcpyDeviceToHost));
+  return CBA_OK;
+}
+int cba_model_unproject(cba_model* m, int64_t n, const double* pixels, double* lines, double* jacobians, uint8_t* ok) {
+  if (!m || n < 0 || (n > 0 && (!pixels || !lines || !ok))) { set_error("cba_model_unproject: bad argument"); return CBA_ERR_ARG; }
+  if (n == 0) return CBA_OK;
+  CBA_HIP(hipSetDevice(m->device));
+  CBA_TRY(model_reserve(m, n));
+  CBA_HIP(hipMemcpy(m->d_a, pixels, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+  CBA_TRY(launch_unproject(m->d_cam, m->cam.model_type, n, m->d_a, m->d_b, jacobians ? (double*)m->d_j : nullptr, m->d_ok, nullptr));
+  CBA_HIP(hipMemcpy(lines, m->d_b, sizeof(double) * 6 * n, hipMemcpyDeviceToHost));
+  CBA_HIP(hipMemcpy(ok, m->d_ok, (size_t)n, hipMemcpyDeviceToHost));
+  if (jacobians) CBA_HIP(hipMemcpy(jacobians, m->d_j, sizeof(double) * 12 * n, hipMemcpyDeviceToHost));
+  return CBA_OK;
+}
+
+// ---- stateless entry points (one-shot wrappers) ------------------------------------------------------
+int cba_project(const cba_camera* camera, const double* grid, int64_t n, const double* local_points,
+                const double* init_pixels, double* pixels, uint8_t* ok, int32_t device) {
+  if (n < 0 || (n > 0 && (!local_points || !pixels || !ok))) { set_error("cba_project: bad argument"); return CBA_ERR_ARG; }
+  cba_model* m = nullptr;
+  CBA_TRY(cba_model_create(camera, grid, device, &m));
+  const int rc = cba_model_project(m, n, local_points, init_pixels, pixels, ok);
+  cba_model_destroy(m);
+  return rc;
+}
+
+int cba_unproject(const cba_camera* camera, const double* grid, int64_t n, const double* pixels, double* lines,
+                  double* jacobians, uint8_t* ok, int32_t device) {
+  if (n < 0 || (n > 0 && (!pixels || !lines || !ok))) { set_error("cba_unproject: bad argument"); return CBA_ERR_ARG; }
+  cba_model* m = nullptr;
+  CBA_TRY(cba_model_create(camera, grid, device, &m));
+  const int rc = cba_model_unproject(m, n, pixels, lines, jacobians, ok);
+  cba_model_destroy(m);
+  return rc;
+}
+
+int cba_schur_solve(int32_t block_size, int32_t n_blocks, int32_t dense_dof, const double* block_diag_H,
+                    const double* off_diag_H, const double* dense_H, const double* block_diag_b,
+                    const double* dense_b, double* x, int32_t device) {
+  return cba_schur_solve_opt(block_size, n_blocks, dense_dof, block_diag_H, off_diag_H, dense_H, block_diag_b, dense_b, x, nullptr, device);
+}
+int cba_schur_solve_opt(int32_t block_size, int32_t n_blocks, int32_t dense_dof, const double* block_diag_H,
+                        const double* off_diag_H, const double* dense_H, const double* block_diag_b,
+                        const double* dense_b, double* x, const cba_solver_options* options, int32_t device) {
+  if (block_size < 1 || block_size > 6 || n_blocks < 1 || dense_dof < 1 || !block_diag_H || !off_diag_H || !dense_H ||
+      !block_diag_b || !dense_b || !x) { set_error("cba_schur_solve: bad argument"); return CBA_ERR_ARG; }
+  CBA_TRY(select_device(device, ""));
+  const int bs = block_size, nb = n_blocks, dd = dense_dof, bdof = bs * nb;
+  int n_pad, n_fact; padded_dims(dd, &n_pad, &n_fact);
+  const int ld = n_pad, Kpad = round_up(bdof, 16);
+  DevBuf<double> Dblk, bblk, Dinv, dinvb, B, W, Hdd, bd, S, xd, gws; DevBuf<int> status;
+  CBA_TRY(gws.alloc((size_t)gemv_t_workspace_doubles(dd)));
+  CBA_TRY(Dblk.alloc((size_t)nb * bs * bs)); CBA_TRY(bblk.alloc((size_t)bdof)); CBA_TRY(Dinv.alloc((size_t)nb * bs * bs));
+  CBA_TRY(dinvb.alloc((size_t)Kpad)); CBA_TRY(B.alloc((size_t)Kpad * ld)); CBA_TRY(W.alloc((size_t)Kpad * ld));
+  CBA_TRY(Hdd.alloc((size_t)ld * ld)); CBA_TRY(bd.alloc((size_t)ld)); CBA_TRY(S.alloc((size_t)ld * ld));
+  CBA_TRY(xd.alloc((size_t)bdof + ld)); CBA_TRY(status.alloc(1));
+  CBA_HIP(hipMemset(B, 0, sizeof(double) * (size_t)Kpad * ld)); CBA_HIP(hipMemset(W, 0, sizeof(double) * (size_t)Kpad * ld));
+  CBA_HIP(hipMemset(Hdd, 0, sizeof(double) * (size_t)ld * ld)); CBA_HIP(hipMemset(S, 0, sizeof(double) * (size_t)ld * ld));
+  CBA_HIP(hipMemset(bd, 0, sizeof(double) * ld)); CBA_HIP(hipMemset(status, 0, sizeof(int))); CBA_HIP(hipMemset(dinvb, 0, sizeof(double) * Kpad));
+  CBA_HIP(hipMemset(xd, 0, sizeof(double) * ((size_t)bdof + ld)));
+  // upper triangles only: the reference fills lower triangles with NaN in its golden test, so copy and scrub
+  std::vector<double> hD(block_diag_H, block_diag_H + (size_t)nb * bs * bs), hH((size_t)dd * dd);
+  for (int b = 0; b < nb; ++b)
+    for (int r = 0; r < bs; ++r)
+      for (int c = 0; c < r; ++c) hD[(size_t)b * bs * bs + r * bs + c] = 0.0;
+  for (int r = 0; r < dd; ++r)
+    for (int c = 0; c < dd; ++c) hH[(size_t)r * dd + c] = (c >= r) ? dense_H[(size_t)r * dd + c] : 0.0;
+  CBA_HIP(hipMemcpy(Dblk, hD.data(), sizeof(double) * hD.size(), hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(bblk, block_diag_b, sizeof(double) * bdof, hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy2D(B, ld * sizeof(double), off_diag_H, dd * sizeof(double), dd * sizeof(double), bdof, hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy2D(Hdd, ld * sizeof(double), hH.data(), dd * sizeof(double), dd * sizeof(double), dd, hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(bd, dense_b, sizeof(double) * dd, hipMemcpyHostToDevice));
+  LdltWorkspace w;
+  CBA_TRY(ldlt_workspace_alloc(w, n_pad));
+  apply_solver_options(w, options);
+  CBA_HIP(hipMemset(w.status, 0, sizeof(int)));
+  hipStream_t s = nullptr;
+  CBA_TRY(launch_block_inverse(Dblk, bblk, 0.0, bs, nb, Dinv, dinvb, status, s));
+  CBA_TRY(launch_dinv_times_B_ld(Dinv, B, bs, nb, dd, ld, W, s));
+  CBA_TRY(schur_gemm(B, W, Kpad, ld, Hdd, S, n_pad, ld, dd, 1, 0.0, nullptr, s, nullptr, -1));
+  CBA_TRY(launch_gemv_t_strided(B, bdof, dd, ld, dinvb, bd, S + (ld - 1), ld, gws, s));
+  CBA_TRY(ldlt_factor(S, n_fact, ld, w, s, nullptr));
+  CBA_TRY(ldlt_back_solve(S, n_fact, ld, ld - 1, w, xd + bdof, s));
+  CBA_TRY(launch_gemv_n(W, bdof, dd, ld, xd + bdof, dinvb, xd, s));
+  CBA_HIP(hipDeviceSynchronize());
+  int st[2];
+  CBA_HIP(hipMemcpy(&st[0], status, sizeof(int), hipMemcpyDeviceToHost));
+  CBA_HIP(hipMemcpy(&st[1], w.status, sizeof(int), hipMemcpyDeviceToHost));
+  CBA_HIP(hipMemcpy(x, xd, sizeof(double) * (bdof + dd), hipMemcpyDeviceToHost));
+  if (st[1] == 3) { set_error("cba_schur_solve: a dataflow launch of the factorisation timed out"); return CBA_ERR_TIMEOUT; }
+  if (st[0] || st[1]) { set_error("cba_schur_solve: zero pivot"); return CBA_ERR_NUMERIC; }
+  return CBA_OK;
+}
+
+int64_t cba_gridfirst_plan_query(const cba_camera* cameras, int32_t n_cameras, int32_t n_images, int32_t n_points, int32_t strips,
+                                 int32_t single_tile_tasks, int32_t what, void* out, int64_t capacity_bytes) {
+  GfPlan pl;
+  int rc = gf_build_plan(cameras, n_cameras, n_images, n_points, strips, single_tile_tasks, &pl);
+  if (rc != CBA_OK) { set_error("cba_gridfirst_plan_query: bad argument"); return rc; }
+  auto give = [&](const void* src, size_t bytes) -> int64_t {
+    if (out && capacity_bytes >= (int64_t)bytes && bytes) std::memcpy(out, src, bytes);
+    return (int64_t)bytes;
+  };
+  switch (what) {
+    case 0: {
+      const int32_t h[16] = {pl.G, pl.Gf, pl.n_rp, pl.n_border, pl.n_fact, pl.n_pad, pl.nbg, pl.nbf, pl.ntc, (int32_t)pl.chains.size(),
+                             (int32_t)pl.tasks.size(), pl.n_tasks0, (int32_t)pl.ivals.size(), pl.mask_words, pl.half_bandwidth, pl.strips[0]};
+      return give(h, sizeof(h));
+    }
+    case 1: return give(pl.f_of_grid.data(), pl.f_of_grid.size() * sizeof(int));
+    case 2: return give(pl.chains.data(), pl.chains.size() * sizeof(GfChain));
+    case 3: return give(pl.tasks.data(), pl.tasks.size() * sizeof(GfTask));
+    case 4: return give(pl.ivals.data(), pl.ivals.size() * sizeof(GfIval));
+    case 5: return give(pl.rowmask.data(), pl.rowmask.size() * sizeof(uint64_t));
+    case 6: { const double f[3] = {pl.flops_grid, pl.flops_update, pl.flops_border}; return give(f, sizeof(f)); }
+    case 7: case 8: {
+      GfShared sl;
+      gf_shared_layout(cameras, n_cameras, n_points, &sl);
+      if (what == 8) return give(sl.ref_col.data(), sl.ref_col.size() * sizeof(int));
+      const int64_t h[6] = {sl.doubles, sl.off_rp_grid, sl.off_rig, sl.off_pp, sl.off_b, sl.G};
+      return give(h, sizeof(h));
+    }
+    default:
+      if (what >= 16 && what < 16 + n_cameras) return give(pl.gperm[what - 16].data(), pl.gperm[what - 16].size() * sizeof(int));
+      set_error("cba_gridfirst_plan_query: unknown item");
+      return CBA_ERR_ARG;
+  }
+}
+
+int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n, const double* grid_points,
+                               const double* directions, int32_t max_iteration_count, cba_fit_report* report, int32_t device) {
+  if (!camera || !grid || n < 0 || (n > 0 && (!grid_points || !directions)) || max_iteration_count < 0 || !camera_ok(*camera) ||
+      camera->model_type != CBA_CENTRAL_GENERIC) { set_error("cba_fit_grid_to_directions: bad argument"); return CBA_ERR_ARG; }
+  CBA_TRY(select_device(device, ""));
+  const int gw = camera->grid_w, gh = camera->grid_h, G = gw * gh, dof = 2 * G;
+  int n_pad, n_fact; padded_dims(dof, &n_pad, &n_fact);
+  const int ld = n_pad;
+  cba_fit_report rep{};
+  DevBuf<double> g[2], tang, gp, dirs, cost_ref, cost_test, rec, H, b, S, x, partials, red8, scal;
+  DevBuf<int> keys, count, start, fill, order, status;
+  const size_t nn = (size_t)(n > 0 ? n : 1);
+  CBA_TRY(g[0].alloc(3 * (size_t)G)); CBA_TRY(g[1].alloc(3 * (size_t)G)); CBA_TRY(tang.alloc(6 * (size_t)G));
+  CBA_TRY(gp.alloc(2 * nn)); CBA_TRY(dirs.alloc(3 * nn)); CBA_TRY(cost_ref.alloc(3 * nn)); CBA_TRY(cost_test.alloc(3 * nn));
+  CBA_TRY(rec.alloc(nn * 99)); CBA_TRY(keys.alloc(nn)); CBA_TRY(order.alloc(nn));
+  CBA_TRY(count.alloc((size_t)G + 1)); CBA_TRY(start.alloc((size_t)G + 1)); CBA_TRY(fill.alloc((size_t)G + 1));
+  CBA_TRY(H.alloc((size_t)ld * ld)); CBA_TRY(b.alloc((size_t)ld)); CBA_TRY(S.alloc((size_t)ld * ld)); CBA_TRY(x.alloc((size_t)ld));
+  CBA_TRY(partials.alloc(256 * 8)); CBA_TRY(red8.alloc(8)); CBA_TRY(scal.alloc(8)); CBA_TRY(status.alloc(1));
+  CBA_HIP(hipMemcpy(g[0], grid, sizeof(double) * 3 * G, hipMemcpyHostToDevice));
+  if (n) {
+    CBA_HIP(hipMemcpy(gp, grid_points, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+    CBA_HIP(hipMemcpy(dirs, directions, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+  }
+  CBA_HIP(hipMemset(status, 0, sizeof(int)));
+  LdltWorkspace w;
+  CBA_TRY(ldlt_workspace_alloc(w, n_pad));
+  hipStream_t s = nullptr;
+  CBA_TRY(make_main_stream(&s));
+  auto read = [&](const double* dev, double* host, int k) -> int {
+    CBA_HIP(hipMemcpyAsync(host, dev, sizeof(double) * k, hipMemcpyDeviceToHost, s));
+    CBA_HIP(hipStreamSynchronize(s));
+    return CBA_OK;
+  };
+  int cur = 0, rc = CBA_OK;
+  double lambda = -1.0, last_cost = 0.0;
+  const double init_lambda_factor = (double)0.001f;
+  for (int iteration = 0; iteration < max_iteration_count && rc == CBA_OK; ++iteration) {
+    double t0 = now_s();
+    if ((rc = launch_tangents(g[cur], tang, G, s))) break;
+    if ((rc = launch_fit_pass(true, gw, gh, g[cur], tang, n, gp, dirs, cost_ref, rec, keys, status, s))) break;
+    CBA_HIP(hipMemsetAsync(H, 0, sizeof(double) * (size_t)ld * ld, s));
+    CBA_HIP(hipMemsetAsync(b, 0, sizeof(double) * (size_t)ld, s));
+    if ((rc = launch_fit_accumulate(gw, gh, n, rec, keys, count, start, fill, order, H, ld, b, s))) break;
+    if ((rc = launch_reduce_costs(cost_ref, nullptr, nullptr, 3 * n, partials, red8, s))) break;
+    if ((rc = launch_fit_diag_sum(H, ld, dof, scal, s))) break;
+    double h8[8], hsum = 0; int st = 0;
+    if ((rc = read(red8, h8, 8)) || (rc = read(scal, &hsum, 1))) break;
+    CBA_HIP(hipMemcpy(&st, status, sizeof(int), hipMemcpyDeviceToHost));
+    rep.t_pass += now_s() - t0;
+    if (st == 3) { set_error("cba_fit_grid_to_directions: a grid point lies outside the grid's 4x4 patches"); rc = CBA_ERR_ARG; break; }
+    last_cost = h8[0];
+    if (iteration == 0) { rep.initial_cost = last_cost; lambda = init_lambda_factor * hsum / dof; }
+    if (last_cost == 0) break;
+    bool applied = false;
+    for (int lm = 0; lm < 10 && rc == CBA_OK; ++lm) {
+      rep.lm_attempts += 1;
+      t0 = now_s();
+      CBA_HIP(hipMemcpyAsync(S, H, sizeof(double) * (size_t)ld * ld, hipMemcpyDeviceToDevice, s));
+      if ((rc = launch_finish_diag(S, ld, dof, n_pad, lambda, s))) break;
+      if ((rc = launch_fit_set_rhs(S, ld, b, dof, s))) break;
+      CBA_HIP(hipMemsetAsync(w.status, 0, sizeof(int), s));
+      if ((rc = ldlt_factor(S, n_fact, ld, w, s, nullptr))) break;
+      if ((rc = ldlt_back_solve(S, n_fact, ld, ld - 1, w, x, s))) break;
+      CBA_HIP(hipMemcpyAsync(&st, w.status, sizeof(int), hipMemcpyDeviceToHost, s));
+      CBA_HIP(hipStreamSynchronize(s));
+      rep.t_solve += now_s() - t0;
+      if (st != 0) { lambda = 2.f * lambda; continue; }     // zero pivot: treated like the reference's NaN update
+      t0 = now_s();
+      if ((rc = launch_update_direction_grid(g[cur], x, G, g[cur ^ 1], s))) break;
+      if ((rc = launch_fit_pass(false, gw, gh, g[cur ^ 1], tang, n, gp, dirs, cost_test, nullptr, nullptr, status, s))) break;
+      if ((rc = launch_reduce_costs(cost_ref, cost_test, nullptr, 3 * n, partials, red8, s))) break;
+      if ((rc = read(red8, h8, 8))) break;
+      rep.t_pass += now_s() - t0;
+      if (h8[4] > 0 && h8[3] < h8[2]) {                       // CostIsSmallerThan
+        cur ^= 1;
+        lambda = 0.5f * lambda;
+        applied = true;
+        rep.iterations_performed += 1;
+        last_cost = h8[1];
+        break;
+      }
+      lambda = 2.f * lambda;
+    }
+    if (!applied || last_cost == 0) break;
+  }
+  if (rc == CBA_OK) {
+    rep.final_cost = last_cost; rep.lambda = lambda;
+    if (hipMemcpy(grid, g[cur], sizeof(double) * 3 * G, hipMemcpyDeviceToHost) != hipSuccess) { set_error("cba_fit_grid_to_directions: copy back failed"); rc = CBA_ERR_HIP; }
+    if (report) *report = rep;
+  }
+  return rc;
+}
+
+}  // extern "C"

@@ -1,0 +1,184 @@
+// Passes over the observations (include/cba.h): stage timers, the residual pass, the Jacobian pass with the accumulation of
+// the normal equations, the scalar reductions across ranks.  The kernels are those of kernels_obs.hip.
+#include "cba_problem.h"
+
+namespace cba {
+
+int timer_begin(cba_problem* p, int which, hipStream_t s) {
+  KernelTimer& t = p->timers[which];
+  if (t.used == (int)t.spans.size()) {
+    KernelTimer::Span sp;
+    CBA_TRY(sp.e0.create()); CBA_TRY(sp.e1.create());
+    t.spans.push_back(std::move(sp));
+  }
+  CBA_HIP(hipEventRecord(t.spans[t.used].e0, s ? s : p->stream));
+  return CBA_OK;
+}
+int timer_end(cba_problem* p, int which, double flops, double bytes, int launches, hipStream_t s) {
+  KernelTimer& t = p->timers[which];
+  CBA_HIP(hipEventRecord(t.spans[t.used].e1, s ? s : p->stream));
+  t.used += 1;
+  t.flops += flops; t.bytes += bytes; t.launches += launches;
+  return CBA_OK;
+}
+// adds the elapsed times of the spans recorded since the last call (waits for them)
+int timers_collect(cba_problem* p) {
+  for (KernelTimer& t : p->timers) {
+    for (int i = 0; i < t.used; ++i) {
+      CBA_HIP(hipEventSynchronize(t.spans[i].e1));
+      float ms = 0;
+      CBA_HIP(hipEventElapsedTime(&ms, t.spans[i].e0, t.spans[i].e1));
+      t.seconds += ms * 1e-3;
+    }
+    t.used = 0;
+  }
+  GemmStats gs;                       // kernel-only spans of the factorisation's 128 x 128 GEMM launches
+  { int rc = ldlt_collect_spans(p->ldlt, &gs); if (rc != CBA_OK) return rc; }
+  p->timers[kTimerFactorGemm].seconds += gs.seconds; p->timers[kTimerFactorGemm].flops += gs.flops; p->timers[kTimerFactorGemm].launches += gs.launches;
+  return CBA_OK;
+}
+
+// -1 (default): pooled wherever the projections of one wavefront differ in length -- the non-central model (83 tasks per observation) and
+// rigs: 9 - 11 % faster in the bench trajectories of BASELINE configs[3] / [2] -- and one task per lane for a single central-generic
+// camera, where after the first iteration every task of an observation takes the same two outer iterations and the pool's bookkeeping
+// costs 4 % (configs[1]; in the FIRST iteration from the perturbed state the pool wins there too, 1.46 -> 1.29 ms).
+// profiles/r05_fd_schedules.txt, r05_fd_schedules_bench.txt
+static int fd_schedule_of(const cba_problem* p) {
+  if (p->fd_schedule >= 0) return p->fd_schedule;
+  return (p->L.n_cameras == 1 && p->model_mask == 1) ? 1 : 0;
+}
+static PassArgs pass_args(cba_problem* p, int which) {
+  PassArgs a;
+  a.n_obs = p->n_obs; a.n_cameras = p->L.n_cameras;
+  a.obs_xy = p->obs_xy; a.obs_point = p->obs_point; a.obs_image = p->obs_image; a.obs_camera = p->obs_camera;
+  a.last_projection = p->last_projection;
+  a.points = p->st[which].points; a.itg = p->itg; a.cams = p->cams_dev[which];
+  a.fd_delta = p->cfg.numerical_diff_delta;
+  a.pose_slot = p->pose_slot;
+  a.obs_list = nullptr; a.obs_count = nullptr; a.obs_list_cap = 0; a.skip = nullptr;
+  a.jrec = p->jrec; a.rec_doubles = p->rec_doubles;
+  a.guard = nullptr;
+  return a;
+}
+
+int read_scalars(cba_problem* p, const double* dev, double* host, int n) {
+  CBA_HIP(hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
+  CBA_HIP(hipStreamSynchronize(p->stream));
+  return CBA_OK;
+}
+
+int allreduce(cba_problem* p, double* dev, int64_t count) {
+  if (!p->cfg.allreduce) return CBA_OK;
+  CBA_HIP(hipStreamSynchronize(p->stream));
+  int rc = p->cfg.allreduce(dev, count, p->cfg.allreduce_user);
+  if (rc != 0) { set_error("allreduce callback failed"); return CBA_ERR_STATE; }
+  return CBA_OK;
+}
+
+// residual pass on state `which`; fills cost vector `cost_vec` and reduces to out8 (host)
+int residual_pass(cba_problem* p, int which, double* cost_vec, const int* guard) {
+  CBA_TRY(launch_compose_poses(p->st[which], p->L.n_images, p->L.n_cameras, p->itg, p->stream));
+  PassArgs a = pass_args(p, which);
+  a.guard = guard;
+  CBA_TRY(launch_base_project(a, p->model_mask, cost_vec, p->pixels, p->flags, p->slow_list, p->slow_count, p->slow_cap, p->slow_skip, p->straggler_threshold, nullptr, p->stream));
+  PassArgs as = a;
+  as.obs_list = p->slow_list; as.obs_count = p->slow_count; as.obs_list_cap = p->slow_cap;
+  CBA_TRY(launch_base_project_slow(as, p->model_mask, cost_vec, p->pixels, p->flags, p->stream));
+  return CBA_OK;
+}
+
+int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
+  const Layout& L = p->L;
+  const int w = p->cur;
+  for (int c = 0; c < L.n_cameras; ++c)
+    CBA_TRY(launch_tangents(p->st[w].grids[c], p->tangents[c], p->cams[c].grid_w * p->cams[c].grid_h, p->stream));
+  CBA_TRY(launch_compose_poses(p->st[w], L.n_images, L.n_cameras, p->itg, p->stream));
+  PassArgs a = pass_args(p, w);
+  PassArgs as = a;
+  as.obs_list = p->slow_list; as.obs_count = p->slow_count; as.obs_list_cap = p->slow_cap;
+  a.skip = p->slow_skip;
+  hipStream_t aux = p->ldlt.far_stream, clr = p->ldlt.mid_stream;
+  if (p->pf.mask_pending) {      // (two passes without a solve in between: the previous pass's mask launch reads the B this one rewrites)
+    CBA_HIP(hipStreamWaitEvent(p->stream, p->pf.ev_mask, 0));
+    p->pf.mask_pending = false;
+  }
+  const size_t bs = L.block_size, nb = L.n_blocks;
+  CBA_HIP(hipMemsetAsync(p->fd_redo_count + 2, 0, sizeof(int), p->stream));      // tasks that found a follow-up list full, this pass
+  CBA_TRY(launch_base_project(a, p->model_mask, p->cost_ref, p->pixels, p->flags, p->slow_list, p->slow_count, p->slow_cap, p->slow_skip, p->straggler_threshold, p->fd_slow, p->stream));
+  // ... and the stragglers of the base projection (long projection chains, see k_base_project_slow) are finished there,
+  // followed by their finite-difference tasks, underneath the main finite-difference launch
+  CBA_HIP(hipEventRecord(p->ev_aux2, p->stream));
+  CBA_HIP(hipStreamWaitEvent(aux, p->ev_aux2, 0));
+  CBA_TRY(launch_base_project_slow(as, p->model_mask, p->cost_ref, p->pixels, p->flags, aux));
+  CBA_TRY(launch_fd_tasks(as, p->model_mask, p->tasks_per_obs, L.localize_only, p->pixels, p->flags, p->fd_out, p->fd_ok, p->fd_redo[1], p->fd_redo_count + 1, p->fd_redo_cap,
+                          p->fd_redo_count + 2, aux, fd_schedule_of(p)));
+  CBA_HIP(hipEventRecord(p->ev_aux1, aux));
+  CBA_TRY(timer_begin(p, kTimerFd));
+  CBA_TRY(launch_fd_tasks(a, p->model_mask, p->tasks_per_obs, L.localize_only, p->pixels, p->flags, p->fd_out, p->fd_ok, p->fd_redo[0], p->fd_redo_count, p->fd_redo_cap,
+                          p->fd_redo_count + 2, p->stream, fd_schedule_of(p)));
+  CBA_TRY(timer_end(p, kTimerFd, 0, 0, 1));
+  // Third stream: the accumulation targets are cleared (1.3 GB for H_dd at cfg 2) underneath the finite-difference launch.  Round 3
+  // issued the memsets first, on the side stream: the 0.2 ms fill of H_dd then held the chip before the base projection of the pass
+  // got a workgroup slot (profiles/r04_v2_step_timeline_cfg2.txt: base projection 0.25 ms after the tangents); queued behind the
+  // VALU-bound FD kernel the fill's workgroups take slots as they come free.
+  CBA_HIP(hipStreamWaitEvent(clr, p->ev_aux2, 0));            // behind the base projection of this pass
+  CBA_HIP(hipMemsetAsync(p->Dblk, 0, sizeof(double) * nb * bs * bs, clr));
+  CBA_HIP(hipMemsetAsync(p->bblk, 0, sizeof(double) * nb * bs, clr));
+  if (L.eliminate_points)
+    CBA_HIP(hipMemsetAsync(p->B, 0, sizeof(double) * (size_t)p->Kpad * p->n_pad, clr));
+  else if (p->Kpad > L.block_dof)     // padding rows of B (the strips below overwrite everything else, zeros included)
+    CBA_HIP(hipMemsetAsync(p->B + (size_t)L.block_dof * p->n_pad, 0, sizeof(double) * (size_t)(p->Kpad - L.block_dof) * p->n_pad, clr));
+  CBA_HIP(hipMemsetAsync(p->Hdd, 0, sizeof(double) * (size_t)p->n_pad * p->n_pad, clr));
+  CBA_HIP(hipMemsetAsync(p->bd, 0, sizeof(double) * (size_t)p->n_pad, clr));
+  CBA_HIP(hipEventRecord(p->ev_clear, clr));
+  CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_aux1, 0));
+  CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_clear, 0));
+  a.skip = nullptr;
+  const bool side = !L.localize_only;      // the per-cell accumulation runs on the side stream
+  // (Running the assembly / accumulation of one chunk of imagesets next to the finite-difference launches of the
+  // next chunk was measured and gained nothing: the two share the same CUs and the sum stayed the same.)
+  CBA_TRY(launch_assemble(a, L, p->st[w], p->tasks_per_obs, p->rec_doubles, p->pixels, p->flags, p->fd_out, p->fd_ok,
+                          p->jrec, p->cells, p->fd_slow, p->stream));
+  double t0 = now_s();
+  CBA_TRY(timer_begin(p, kTimerAccumulate));
+  AccumTargets T{p->Dblk, p->bblk, p->B, p->Hdd, p->bd};
+  Layout Lp = L;
+  Lp.dense_dof = p->n_pad;  // Hdd / B use the padded leading dimension as row stride
+  const double* det = p->cfg.deterministic ? (const double*)p->det_scale : nullptr;
+  if (det) CBA_TRY(launch_det_scale(p->n_obs, p->rec_doubles, p->rec_doubles, p->flags, p->jrec, p->det_bits, p->det_scale, p->stream));
+  const int points_separate = (!L.eliminate_points && p->pt_start) ? 1 : 0;
+  // The four accumulation kernels write disjoint parts of the system (or add atomically).  The per-cell kernel runs on the side
+  // stream next to the others; the per-point kernel (120 KB of LDS per workgroup, one per CU) goes FIRST on the main stream, alone:
+  // next to the strips kernel its workgroups rarely find a CU with that much LDS free and the launch takes 3.9 ms instead of
+  // ~0.6 at cfg 3 (measured, profiles/r03_v4_bench_cfg3_kernel_stats.txt).
+  if (side) {
+    CBA_HIP(hipEventRecord(p->ev_aux0, p->stream));
+    CBA_HIP(hipStreamWaitEvent(aux, p->ev_aux0, 0));
+    CBA_TRY(launch_accumulate_cells(a, p->cams, p->cell_base_host, p->rec_doubles, p->n_pad, p->flags, p->jrec, p->cells, p->cell_base,
+                                    p->cell_count, p->cell_start, p->cell_fill, p->cell_order, p->Hdd,
+                                    (!L.eliminate_points && L.rig_in_state) ? L.first_camera_tr_rig - L.block_dof : -1, det, p->bd, aux));
+    if (p->gridfirst) CBA_TRY(gridfirst_pass_activity(p, a, aux));      // the activity masks of this pass, behind the per-cell accumulation
+    CBA_HIP(hipEventRecord(p->ev_aux1, aux));
+  }
+  if (points_separate)
+    CBA_TRY(launch_accumulate_points(a, Lp, p->cams, p->rec_doubles, p->flags, p->jrec, p->cells, p->pt_start, p->pt_obs, T, det, p->stream));
+  if (!L.eliminate_points)   // B strips (plain stores), the remaining terms are added on top atomically
+    CBA_TRY(launch_accumulate_strips(a, Lp, L.n_images, p->rec_doubles, p->flags, p->jrec, p->cells, p->band_mask, p->img_start, p->B,
+                                     p->n_pad, det, p->stream));
+  CBA_TRY(launch_accumulate(a, Lp, p->rec_doubles, p->flags, p->jrec, p->cells, p->pair_tables, p->pair_counts, T, det, points_separate, p->stream));
+  if (side) CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_aux1, 0));
+  if (det) {   // fixed point -> fp64, in place
+    CBA_TRY(launch_det_convert(p->Dblk, nb * bs * bs, det, p->stream));
+    CBA_TRY(launch_det_convert(p->bblk, nb * bs, det + 1, p->stream));      // J^T r: second scale
+    CBA_TRY(launch_det_convert(p->Hdd, (size_t)L.dense_dof * p->n_pad, det, p->stream));
+    CBA_TRY(launch_det_convert(p->bd, (size_t)p->n_pad, det + 1, p->stream));
+    CBA_TRY(launch_det_convert(p->B, (size_t)L.block_dof * p->n_pad, det, p->stream));   // strips store integers, the pose x rig atomics add to them
+  }
+  CBA_TRY(timer_end(p, kTimerAccumulate, 0, 0, 1));
+  if (t_acc) *t_acc += now_s() - t0;
+  CBA_TRY(p->gridfirst ? gridfirst_pass_end(p) : posefirst_pass_end(p));      // exchange between the ranks / touch masks of B
+  p->have_system = true;
+  return CBA_OK;
+}
+
+}  // namespace cba

@@ -116,7 +116,7 @@ def _packed_worker(rank, world, port, out_dir):
     lam = 0.37
     S, s, _, _ = dist_mod.local_reduced_system(sysm.block_diag_H, sysm.off_diag_H, sysm.dense_H, sysm.block_diag_b, sysm.dense_b, lam)
     D = pb.dense_dof
-    n_pad = -(-(D + 1) // 128) * 128                 # the engine's padding rule (cba_api.hip padded_dims)
+    n_pad = -(-(D + 1) // 128) * 128                 # the engine's padding rule (cba_setup.hip padded_dims)
     if -(-D // 64) * 64 >= n_pad:
         n_pad += 128
     Sp = np.zeros((n_pad, n_pad))

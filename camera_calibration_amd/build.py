@@ -10,8 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcalib_ba_hip.so")
 SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip",
-           "kernels_obs.hip", "kernels_linalg.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip"]
-HEADERS = ["cba_internal.h", "cba_problem.h", "model.hip.h", "gridfirst_plan.h", os.path.join("..", "..", "include", "cba.h")]
+           "kernels_obs.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip"]
+HEADERS = ["cba_internal.h", "cba_problem.h", "model.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]  # keep MFMA accumulators in VGPRs: no AGPR<->VGPR copies in the K loop
 
@@ -65,7 +65,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             print(out)
     if failed:
         raise RuntimeError("hipcc compilation failed")
-    check_tail_m0(os.path.join(CSRC, "kernels_linalg.o"))
+    check_tail_m0(os.path.join(CSRC, "kernels_ldlt.o"))
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
     with open(FLAGS_STAMP, "w") as f:
         f.write(_extra_flags())
@@ -102,7 +102,7 @@ _IMPLICIT_M0 = ("s_sendmsg", "s_movrel", "v_movrel", "ds_gws", "s_ttrace", "v_in
 
 
 def check_tail_m0(obj: str) -> int:
-    """Build-time guard for the inline-asm LDS-DMA of k_ldlt_tail (kernels_linalg.hip: tail_dma16 / tail_dma4).
+    """Build-time guard for the inline-asm LDS-DMA of k_ldlt_tail (ldlt_dataflow.hip.h: tail_dma16 / tail_dma4).
 
     Those helpers write M0 (the LDS base of global_load_lds) from inline asm and cannot declare it clobbered (the compiler rejects
     the clobber).  That is only correct while the compiler itself never keeps a value in M0 inside that kernel.  This check

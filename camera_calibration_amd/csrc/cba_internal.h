@@ -162,7 +162,12 @@ CamDev make_camdev(const cba_camera& c, const double* grid, const double* tangen
 // makes `device` current; error messages start with `prefix`
 int select_device(int device, const char* prefix);
 void apply_solver_options(LdltWorkspace& w, const cba_solver_options* o);
+// the device's three side streams (shared, never destroyed)
+int device_side_streams(hipStream_t* chain, hipStream_t* mid, hipStream_t* far);
 #pragma GCC visibility pop
+// the engine's streams of the current device, created on the first call (cba_prepare_device: as early as possible in the process)
+int prepare_device_streams();
+int make_main_stream(hipStream_t* s);
 
 // ---- kernels_obs.hip ----
 int launch_compose_poses(const DevState& st, int N, int C, double* itg, hipStream_t s);
@@ -224,13 +229,33 @@ int launch_project_points(const CamDev* cam_dev, int model, int64_t n, const dou
 int launch_unproject(const CamDev* cam_dev, int model, int64_t n, const double* pixels, double* lines, double* jac,
                      uint8_t* ok, hipStream_t s);
 
-// ---- kernels_linalg.hip ----
+// ---- kernels_linalg.hip (Schur stage, the fp64 MFMA GEMM, pack / diagonal kernels) ----
 // Inverse of the (bs x bs) diagonal blocks with lambda added, and Dinv*b.
 int launch_block_inverse(const double* Dblk, const double* bblk, double lambda, int bs, int nb, double* Dinv,
                          double* dinvb, int* status, hipStream_t s);
 // y[k] = base[k] - sum_j M[k][j] * v[j]   (row dot products) -- pose back-substitution
 int launch_gemv_n(const double* M, int K, int n, int ld, const double* v, const double* base, double* y,
                   hipStream_t s);
+int launch_dinv_times_B_ld(const double* Dinv, const double* B, int bs, int nb, int dd, int ld, double* W, hipStream_t s);
+int launch_gemv_t_partial(const double* M, int K, int n, int ld, const double* v, double* partial_ws, hipStream_t s);
+int launch_gemv_t_final(int n, const double* base, double* y, int ystride, const double* partial_ws, int n_zero, hipStream_t s);
+int launch_gemv_t_strided(const double* M, int K, int n, int ld, const double* v, const double* base, double* y,
+                          int ystride, double* partial_ws, hipStream_t s);
+int gemv_t_workspace_doubles(int n);
+int schur_gemm(const double* A, const double* B, int Kpad, int ldab, const double* Cin, double* C, int n_pad, int ld,
+               int n_real, int add_diag, double lambda, const unsigned long long* kmask, hipStream_t s, const int* chunk_order = nullptr,
+               int keep_col = -1);
+int schur_chunk_count(int n_pad);
+void schur_chunk_order(const unsigned long long* mask_host, int n_pad, int Kpad, int* order);
+int schur_mask_words(int Kpad);
+int schur_slab_rows();
+int launch_touch_mask(const double* B, int Kpad, int n_pad, int ld, unsigned long long* mask, hipStream_t s);
+int launch_finish_diag(double* S, int ld, int n_real, int n_pad, double lambda, hipStream_t s);
+int launch_diag_sum(const double* Dblk, int bs, int nb, const double* Hdd, int ld, int dd, double* out, hipStream_t s);
+int64_t packed_upper_doubles(int n_pad);
+int launch_pack_upper(const double* S, int n_pad, double* P, int unpack, hipStream_t s);
+
+// ---- kernels_ldlt.hip ----
 struct GemmStats { double seconds = 0, flops = 0, bytes = 0; int launches = 0; };
 // In-place blocked LDL^T of a symmetric matrix stored "upper in row-major" (= lower in column-major).
 struct LdltWorkspace {
@@ -269,9 +294,6 @@ int ldlt_workspace_alloc(LdltWorkspace& w, int n, int flag_rows_blocks = 0);
 int ldlt_collect_spans(LdltWorkspace& w, GemmStats* st);
 // k_begin: rows above it are factored already and their update is applied (the border of the grid-first order)
 int ldlt_factor(double* S, int n, int ld, LdltWorkspace& w, hipStream_t s, GemmStats* trailing_stats, int k_begin = 0);
-// x of L^T x = z (z = column zcol of S, forward-substituted by the factorisation); rowmask: optional block-sparsity of the factor's rows
-int ldlt_back_solve(const double* S, int n_fact, int ld, int zcol, const LdltWorkspace& w, double* x, hipStream_t s,
-                    const unsigned long long* rowmask = nullptr, int mask_words = 0);
 // Grid-first elimination (gridfirst_plan.h): device copies of the plan's arrays
 struct GfDevice {
   DevBuf<GfTask> tasks; DevBuf<GfIval> ivals; DevBuf<GfChain> chains;
@@ -298,6 +320,12 @@ int ldlt_tail_rows(const LdltWorkspace& w, int world = 1);
 int ldlt_clear_ctrl(LdltWorkspace& w, hipStream_t s);
 // milliseconds of the last tail launch (waits for it); 0 when there was none
 double ldlt_tail_last_ms(LdltWorkspace& w);
+// ---- kernels_backsolve.hip ----
+// x of L^T x = z (z = column zcol of S, forward-substituted by the factorisation); rowmask: optional block-sparsity of the factor's rows
+int ldlt_back_solve(const double* S, int n_fact, int ld, int zcol, const LdltWorkspace& w, double* x, hipStream_t s,
+                    const unsigned long long* rowmask = nullptr, int mask_words = 0);
+
+// ---- kernels_ldlt_dist.hip ----
 // Distributed variant (cba_config.distributed_solve): S holds this rank's PARTIAL reduced system on entry; the collectives are
 // blocking host calls.  `send` / `recv`: device staging buffers of at least ldlt_dist_buffer_doubles(n_pad, world) doubles each.
 struct DistComm {
@@ -308,27 +336,6 @@ struct DistComm {
 };
 size_t ldlt_dist_buffer_doubles(int n_pad, int world);
 int ldlt_factor_distributed(double* S, int n, int ld, LdltWorkspace& w, hipStream_t s, const DistComm& c, GemmStats* trailing_stats);
-int launch_dinv_times_B_ld(const double* Dinv, const double* B, int bs, int nb, int dd, int ld, double* W, hipStream_t s);
-int launch_gemv_t_partial(const double* M, int K, int n, int ld, const double* v, double* partial_ws, hipStream_t s);
-int launch_gemv_t_final(int n, const double* base, double* y, int ystride, const double* partial_ws, int n_zero, hipStream_t s);
-int launch_gemv_t_strided(const double* M, int K, int n, int ld, const double* v, const double* base, double* y,
-                          int ystride, double* partial_ws, hipStream_t s);
-int gemv_t_workspace_doubles(int n);
-// (the definition carries the defaults chunk_order = nullptr, keep_col = -1; callers in other units pass both)
-int schur_gemm(const double* A, const double* B, int Kpad, int ldab, const double* Cin, double* C, int n_pad, int ld,
-               int n_real, int add_diag, double lambda, const unsigned long long* kmask, hipStream_t s, const int* chunk_order,
-               int keep_col);
-int schur_chunk_count(int n_pad);
-void schur_chunk_order(const unsigned long long* mask_host, int n_pad, int Kpad, int* order);
-int schur_mask_words(int Kpad);
-int schur_slab_rows();
-int launch_touch_mask(const double* B, int Kpad, int n_pad, int ld, unsigned long long* mask, hipStream_t s);
-int launch_finish_diag(double* S, int ld, int n_real, int n_pad, double lambda, hipStream_t s);
-int launch_diag_sum(const double* Dblk, int bs, int nb, const double* Hdd, int ld, int dd, double* out, hipStream_t s);
-int make_main_stream(hipStream_t* s);
-int prepare_device_streams();
-int64_t packed_upper_doubles(int n_pad);
-int launch_pack_upper(const double* S, int n_pad, double* P, int unpack, hipStream_t s);
 
 // ---- kernels_gridfirst.hip ----
 int launch_gf_form(double* F, int ldf, int Gf, int n_rp, int n_border, const int* grid_of_f, const double* Hdd, int ldh, const double* bd,

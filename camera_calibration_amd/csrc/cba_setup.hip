@@ -1,6 +1,9 @@
 // Problem setup of the C ABI (include/cba.h): variable layout, camera descriptions, device selection, the choice of the
-// elimination order and the allocations of cba_create; the Z-order of the imagesets (cba_set_observations).
+// elimination order and the allocations of cba_create; the process-wide streams of a device; the Z-order of the imagesets
+// (cba_set_observations).
 #include <algorithm>
+#include <map>
+#include <mutex>
 
 #include "cba_problem.h"
 
@@ -55,6 +58,52 @@ int select_device(int device, const char* prefix) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device available (the engine has no CPU fallback)"); return CBA_ERR_HIP; }
   if (device < 0 || device >= ndev) { set_error(std::string(prefix) + "bad device ordinal"); return CBA_ERR_ARG; }
   CBA_HIP(hipSetDevice(device));
+  return CBA_OK;
+}
+
+// The engine's four HIP streams per device are created ONCE, as early as possible in the life of the process, and
+// never destroyed.  Measured on MI355X / ROCm 7.2 (round 2): the same GEMM launch runs at 60 TFLOP/s on a stream that was created
+// before the process launched its first kernel and at 52-53 TFLOP/s on a stream created afterwards (and that late stream also
+// slows the older ones down).  cba_prepare_device() is the hook for hosts to call first thing; cba_create calls it as a fallback.
+//   main  : everything on the critical path of a step, the whole factorisation included
+//   chain / mid / far : side work (the stragglers of the Jacobian pass, memsets, the distributed solve's exchanges)
+// No CU masks: a masked stream costs every launch on it 13-17 % (in-order dispatch, even over the shader engines: DESIGN.md).
+struct DeviceStreams {
+  hipStream_t main = nullptr, chain = nullptr, mid = nullptr, far = nullptr;
+};
+static std::mutex g_streams_mutex;
+static std::map<int, DeviceStreams> g_streams;
+static int device_streams(DeviceStreams* out) {
+  int dev = 0;
+  CBA_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(g_streams_mutex);
+  auto it = g_streams.find(dev);
+  if (it == g_streams.end()) {
+    DeviceStreams d;
+    int lo = 0, hi = 0;
+    CBA_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    CBA_HIP(hipStreamCreateWithFlags(&d.main, hipStreamNonBlocking));
+    CBA_HIP(hipStreamCreateWithPriority(&d.chain, hipStreamNonBlocking, hi));
+    CBA_HIP(hipStreamCreateWithFlags(&d.mid, hipStreamNonBlocking));
+    CBA_HIP(hipStreamCreateWithFlags(&d.far, hipStreamNonBlocking));
+    it = g_streams.emplace(dev, d).first;
+  }
+  *out = it->second;
+  return CBA_OK;
+}
+int prepare_device_streams() { DeviceStreams d; return device_streams(&d); }
+
+int make_main_stream(hipStream_t* s) {
+  DeviceStreams d;
+  int rc = device_streams(&d);
+  if (rc != CBA_OK) return rc;
+  *s = d.main;
+  return CBA_OK;
+}
+int device_side_streams(hipStream_t* chain, hipStream_t* mid, hipStream_t* far) {
+  DeviceStreams d;
+  CBA_TRY(device_streams(&d));
+  *chain = d.chain; *mid = d.mid; *far = d.far;
   return CBA_OK;
 }
 

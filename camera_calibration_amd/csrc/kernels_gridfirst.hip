@@ -222,7 +222,7 @@ __global__ void k_gf_masks(const unsigned long long* __restrict__ act, int n_til
   }
 }
 // the two halves of launch_gf_activity: the touched rows of this process's observations (image sharding: OR-ed over the ranks in
-// between, cba_api.hip gf_exchange), then their closure and the masks derived from it
+// between, cba_gridfirst.hip gf_exchange), then their closure and the masks derived from it
 int launch_gf_touch(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
                     int n_rp, int rig_dof, int n_tiles, int words, int slot0, unsigned long long* act, hipStream_t s) {
   if (words > 16) { set_error("grid-first: more than 1024 grid block rows"); return CBA_ERR_UNSUPPORTED; }

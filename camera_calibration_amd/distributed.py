@@ -375,14 +375,14 @@ def make_collective_host_staged():
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# Host mirror of the distributed factorisation schedule (csrc/kernels_linalg.hip: ldlt_factor_distributed), numpy: same
+# Host mirror of the distributed factorisation schedule (csrc/kernels_ldlt_dist.hip: ldlt_factor_distributed), numpy: same
 # ownership rule, same transfers (dist_rect: which rows of which column groups travel, and where they sit in the
 # buffers), same order of collectives.  `collective(op, send, recv)` works on float64 arrays (recv in place), with
 # the semantics of cba_collective_fn.  Used by the CPU tests of the multi-rank path (gloo, world size 2 and 3) with the
 # schedule scaled down (group / W / tail_rows are parameters) -- the device kernels are covered on the GPU.
 # ---------------------------------------------------------------------------------------------------------------
 def dist_rect(n_pad: int, group: int, g_begin: int, world: int, R0: int, nrows: int, q: int, i: int):
-    """i-th column group of rank q in a transfer: (col0, width, height, offset in q's block) or None (kernels_linalg.hip: dist_rect)."""
+    """i-th column group of rank q in a transfer: (col0, width, height, offset in q's block) or None (kernels_ldlt_dist.hip: dist_rect)."""
     gq0 = g_begin + (q - g_begin % world) % world
     g = gq0 + i * world
     col0 = g * group

@@ -215,7 +215,7 @@ def test_distributed_factorisation_schedule_on_cpu(tmp_path, world, n, group, W,
 
 
 def test_transfer_layout_matches_the_device_kernels():
-    """dist_rect (distributed.py) against the closed forms of kernels_linalg.hip: the blocks of one rank are contiguous, in
+    """dist_rect (distributed.py) against the closed forms of kernels_ldlt_dist.hip: the blocks of one rank are contiguous, in
     group order, and disjoint; every column group at or right of the first row is covered exactly once over the ranks."""
     for n_pad, group, world, R0, nrows in [(12672, 512, 8, 2048, 0), (12672, 512, 3, 4096, 2048), (42880, 512, 8, 2048, 0), (1152, 512, 2, 512, 640)]:
         g_begin = R0 // group

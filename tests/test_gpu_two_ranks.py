@@ -113,7 +113,7 @@ def test_two_ranks_on_one_gpu_match_the_single_process_engine(tmp_path):
 
 @pytest.mark.parametrize("world,use_collective", [(2, False), (3, True)])
 def test_two_ranks_with_the_distributed_factorisation(tmp_path, world, use_collective):
-    """cba_config.distributed_solve (kernels_linalg.hip: ldlt_factor_distributed): the partial reduced systems are
+    """cba_config.distributed_solve (kernels_ldlt_dist.hip: ldlt_factor_distributed): the partial reduced systems are
     reduce-scattered into the block-cyclic owners of the 512-column groups (first band all-reduced), every rank runs the dataflow
     launch of each super-panel on the complete row band, applies the K = 2048 update to its own column groups only (next band
     first) and the next band is all-gathered from its owners; two super-panels at this size (D = 5337, 512 rows left to the

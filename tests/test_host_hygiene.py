@@ -50,13 +50,13 @@ def test_distributed_solve_arguments_are_validated_before_any_device_work():
 
 
 def test_tail_kernel_uses_m0_only_inside_its_own_lds_dma(tmp_path, monkeypatch):
-    # k_ldlt_tail writes M0 from inline asm without a clobber (kernels_linalg.hip: tail_dma16); the build fails unless the ISA shows
+    # k_ldlt_tail writes M0 from inline asm without a clobber (ldlt_dataflow.hip.h: tail_dma16); the build fails unless the ISA shows
     # that nothing else in the kernel touches M0.  Here: the check passes on the compiled object, and it catches a foreign M0 use.
     import shutil
     from camera_calibration_amd import build as hb
-    obj = os.path.join(ROOT, "camera_calibration_amd", "csrc", "kernels_linalg.o")
+    obj = os.path.join(ROOT, "camera_calibration_amd", "csrc", "kernels_ldlt.o")
     if not os.path.exists(obj) or shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("kernels_linalg.o / ROCm llvm tools not present")
+        pytest.skip("kernels_ldlt.o / ROCm llvm tools not present")
     try:
         sites = hb.check_tail_m0(obj)
     except RuntimeError as ex:

@@ -3,14 +3,13 @@
 // long-double LDL^T on the host and timed with the 100 MHz wall clock inside one workgroup, phase by phase.  (The
 // barrier-per-pivot-pair loop of round 3 it replaced measured 17.9 us per block in this harness against 9.9: profiles/r04_diag.txt.)
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -mllvm -amdgpu-mfma-vgpr-form tools/bench_diag.hip -o tools/bin/bench_diag
-#define CBA_DEV_SWITCHES 1
 #define CBA_DIAGLOG 1
-#include "../camera_calibration_amd/csrc/kernels_linalg.hip"
+#include "../camera_calibration_amd/csrc/ldlt_dataflow.hip.h"
+#include "bench_host.h"
 #include <cstdio>
 #include <vector>
 #include <cmath>
 #include <algorithm>
-namespace cba { void set_error(const std::string& m) { fprintf(stderr, "error: %s\n", m.c_str()); } }
 using namespace cba;
 
 __global__ void __launch_bounds__(256) k_diag_test(const double* __restrict__ Tin, double* __restrict__ Lout, double* __restrict__ Iout,

@@ -2,9 +2,9 @@
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -mllvm -amdgpu-mfma-vgpr-form tools/bench_gemm.hip -o tools/bin/bench_gemm
 #define CBA_DEV_SWITCHES 1
 #include "../camera_calibration_amd/csrc/kernels_linalg.hip"
+#include "bench_host.h"
 #include <cstdio>
 #include <vector>
-namespace cba { void set_error(const std::string& m) { fprintf(stderr, "error: %s\n", m.c_str()); } }
 using namespace cba;
 int main() {
   const int n = 12672, K = 2304;
@@ -24,9 +24,9 @@ int main() {
       const int off = n - ms_[c] * 128;
       u.A = A; u.lda = n; u.B = B; u.ldb = n; u.K = ks_[c]; u.C = S; u.ldc = n; u.Cin = S; u.ldcin = n;
       u.m_off = off; u.m_tiles = ms_[c]; u.n_off = off; u.n_tiles = ms_[c]; u.upper = 1; u.diag = 0;
-      launch_gemm<128, 128, 64, 64, true>(u, nullptr);
+      gemm128_update(u, nullptr);
       hipEventRecord(e0);
-      for (int r = 0; r < 4; ++r) launch_gemm<128, 128, 64, 64, true>(u, nullptr);
+      for (int r = 0; r < 4; ++r) gemm128_update(u, nullptr);
       hipEventRecord(e1);
       float t; hipEventSynchronize(e1); hipEventElapsedTime(&t, e0, e1); t /= 4;
       const double tiles = ms_[c] * (ms_[c] + 1) / 2.0;

@@ -7,11 +7,13 @@
 #define CBA_DEV_SWITCHES 1
 #define CBA_TAILLOG 1
 #include "../camera_calibration_amd/csrc/kernels_linalg.hip"
+#include "../camera_calibration_amd/csrc/kernels_ldlt.hip"
+#include "../camera_calibration_amd/csrc/kernels_backsolve.hip"
+#include "bench_host.h"
 #include <cstdio>
 #include <vector>
 #include <cmath>
 #include <algorithm>
-namespace cba { void set_error(const std::string& m) { fprintf(stderr, "error: %s\n", m.c_str()); } }
 using namespace cba;
 
 static float timeit(hipEvent_t e0, hipEvent_t e1) { float ms; hipEventSynchronize(e1); hipEventElapsedTime(&ms, e0, e1); return ms; }
@@ -90,7 +92,7 @@ int main(int argc, char** argv) {
       u.C = F; u.ldc = n; u.Cin = F; u.ldcin = n; u.diag = 0; u.upper = 1;
       const int tlc = (n - Gf) / 128;
       u.m_off = Gf; u.m_tiles = tlc; u.n_off = Gf; u.n_tiles = tlc;
-      launch_gemm<128, 128, 64, 64, true>(u, ms);
+      gemm128_update(u, ms);
     }
     hipEventRecord(e[2], ms);
     ldlt_factor(F, nf, n, w, ms, &gs, Gf);

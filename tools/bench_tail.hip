@@ -5,11 +5,13 @@
 #define CBA_DEV_SWITCHES 1
 #define CBA_TAILLOG 1
 #include "../camera_calibration_amd/csrc/kernels_linalg.hip"
+#include "../camera_calibration_amd/csrc/kernels_ldlt.hip"
+#include "../camera_calibration_amd/csrc/kernels_backsolve.hip"
+#include "bench_host.h"
 #include <cstdio>
 #include <vector>
 #include <cmath>
 #include <algorithm>
-namespace cba { void set_error(const std::string& m) { fprintf(stderr, "error: %s\n", m.c_str()); } }
 // The helpers' K loop of rounds 2-4 (register-staged: buffer loads -> scale by d -> ds_write -> barrier -> MFMA), kept here as the
 // reference of the LDS-DMA loop the product uses now (tail_mma_dma): same sums bit for bit, 48-50 vs 56-60 TFLOP/s.
 namespace cba {
@@ -87,7 +89,7 @@ __device__ __forceinline__ void tail_mma_regstaged(v4f64 (&acc)[2][2], const dou
 }
 
 }  // namespace cba
-// (the 64 x 128 LDS-DMA K loop, tail_mma_dma2, moved into the product in round 5: REG2 tasks of k_ldlt_tail)
+// (the 64 x 128 LDS-DMA K loop, tail_mma_dma2, moved into the product in round 5; since round 6: REG2 tasks of k_ldlt_sparse)
 __global__ void __launch_bounds__(256, 2) k_mma2_only(const double* S, int ld, const double* dvec, int K, int ntc, double* out) {
   __shared__ double smem[2 * cba::kInner * cba::TS];
   const int c = blockIdx.x % ntc, r = (blockIdx.x / ntc) % ntc;
@@ -298,15 +300,11 @@ int main(int argc, char** argv) {
     };
     std::vector<double> xr, Sr, dr;
     double ms_ref, tms;
-    if (getenv("PAIRS")) setenv("CBA_TAIL_PAIR", "0", 1);          // reference = single-tile tasks
     int st = run(tails.back(), &xr, n <= 4096 ? &Sr : nullptr, &dr, &ms_ref, &tms);
     printf("reference (tail %d): %.3f ms  status %d   [128x128 GEMM launches: %d at %.1f TFLOP/s per launch]\n", tails.back(), ms_ref, st, g_launches, g_rate);
     double xmax = 0; for (double v : xr) xmax = std::max(xmax, std::fabs(v));
     { double s1 = 0, s2 = 0; for (size_t i = 0; i < xr.size(); ++i) { s1 += xr[i] * (1.0 + (i % 7)); s2 += xr[i] * xr[i]; } printf("checksum of x (compare across builds): %.17g %.17g\n", s1, s2); }
-    std::vector<int> pair_modes = {-1};
-    if (const char* e = getenv("PAIRS")) { pair_modes.clear(); for (const char* c = e; *c;) { pair_modes.push_back(atoi(c)); while (*c && *c != ',') ++c; if (*c) ++c; } }
-    for (int tail : tails) for (int pm : pair_modes) {
-      if (pm >= 0) { setenv("CBA_TAIL_PAIR", pm ? "1" : "0", 1); printf("-- CBA_TAIL_PAIR=%d\n", pm); }
+    for (int tail : tails) {
       std::vector<double> xt, St, dt;
       double ms_t;
       st = run(tail, &xt, n <= 4096 ? &St : nullptr, &dt, &ms_t, &tms);

@@ -930,9 +930,9 @@ static_assert(std::is_trivially_copyable_v<AccumLayout>);
 // over the chunk and flushed with one atomic per entry when the (image, camera) key changes; all other
 // entries go straight to HBM with hardware fp64 atomics.
 constexpr int kAccChunk = 8;
-// with the point terms gone (k_accumulate_points) an observation costs ~90 products here, and what limits the kernel is the flush:
-// every wavefront adds its rig-pose sums to the SAME 27 entries per camera (2.4 ms at cfg 3 with chunks of 8: 93 k atomics per
-// address); 64 observations per wavefront = 8x fewer flushes
+// k_accumulate_poses (the pose / rig-pose entries alone, where k_accumulate_points takes every term with a point column): an
+// observation costs ~90 products, and what limits the kernel is the flush: every wavefront adds its rig-pose sums to the SAME 27
+// entries per camera (2.4 ms at cfg 3 with chunks of 8: 93 k atomics per address); 64 observations per wavefront = 8x fewer flushes
 constexpr int kAccChunkHot = 64;
 constexpr int kHotMax = 12;                       // pose 6 + rig 6
 constexpr int kHotPairs = kHotMax * (kHotMax + 1) / 2;   // 78
@@ -990,7 +990,7 @@ __global__ void __launch_bounds__(256) k_accumulate(PassArgs a, AccumLayout L, i
                                                     const uint8_t* __restrict__ flags, const double* __restrict__ jrec,
                                                     const int* __restrict__ cells, const uint32_t* __restrict__ pair_tables,
                                                     const int* __restrict__ pair_counts, AccumTargets T,
-                                                    const double* __restrict__ det_scale, int points_separate) {
+                                                    const double* __restrict__ det_scale) {
   typedef typename Acc<DET>::T acc_t;
   const double scale = DET ? det_scale[0] : 1.0;
   const double scale_b = DET ? det_scale[1] : 1.0;     // the J^T r sums have their own (finer) fixed-point scale
@@ -1000,8 +1000,7 @@ __global__ void __launch_bounds__(256) k_accumulate(PassArgs a, AccumLayout L, i
   __shared__ double sW1[4][kMaxCols];
   __shared__ int sIdx[4][kMaxCols];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int chunk = points_separate ? kAccChunkHot : kAccChunk;
-  const int64_t o_begin = ((int64_t)blockIdx.x * 4 + wv) * chunk;
+  const int64_t o_begin = ((int64_t)blockIdx.x * 4 + wv) * kAccChunk;
   const int nrig = L.rig_in_state ? 6 : 0;
   const int nh = 6 + nrig;                       // hot columns
   const int h0 = L.eliminate_points ? 3 : 0;     // their first position in the ascending column list
@@ -1033,7 +1032,7 @@ __global__ void __launch_bounds__(256) k_accumulate(PassArgs a, AccumLayout L, i
       hot[t] = 0;
     }
   };
-  for (int c = 0; c < chunk; ++c) {
+  for (int c = 0; c < kAccChunk; ++c) {
     const int64_t o = o_begin + c;
     if (o >= a.n_obs) break;
     if (flags[o] != 3) continue;  // wave-uniform
@@ -1053,10 +1052,7 @@ __global__ void __launch_bounds__(256) k_accumulate(PassArgs a, AccumLayout L, i
     }
     const int cx0 = cells[2 * o], cy0 = cells[2 * o + 1];
     __builtin_amdgcn_wave_barrier();   // previous iteration's LDS reads are done before overwriting
-    // points_separate (poses eliminated): every term with a point column is summed per pattern point by
-    // k_accumulate_points; only the pose / rig-pose ("hot") columns are left here
-    const int Ks = points_separate ? nh : K;
-    for (int k = lane; k < Ks; k += 64) {
+    for (int k = lane; k < K; k += 64) {
       int idx; double j0, j1;
       int kk = k;
       // ascending index order: [point] pose [rig] [point] grid  (joint_optimization.cc:490-590)
@@ -1096,7 +1092,6 @@ __global__ void __launch_bounds__(256) k_accumulate(PassArgs a, AccumLayout L, i
       if (hs_k[t] == -2) hot[t] += Acc<DET>::from(r0 * sW0[wv][i] + r1 * sW1[wv][i], scale_b);
       else { const int k = h0 + hs_k[t]; hot[t] += Acc<DET>::from(sW0[wv][i] * sJ0[wv][k] + sW1[wv][i] * sJ1[wv][k], scale); }
     }
-    if (points_separate) continue;                 // wave-uniform
     // b += Jw^T r (non-hot positions)
     for (int k = lane; k < K - Kg; k += 64) {      // the grid entries are summed per cell by k_accumulate_cells
       if (k >= h0 && k < h0 + nh) continue;
@@ -1111,6 +1106,98 @@ __global__ void __launch_bounds__(256) k_accumulate(PassArgs a, AccumLayout L, i
       int i = pr >> 16, k = pr & 0xffff;
       double v = sW0[wv][i] * sJ0[wv][k] + sW1[wv][i] * sJ1[wv][k];
       acc_add_H<DET>(L, T, sIdx[wv][i], sIdx[wv][k], Acc<DET>::from(v, scale));
+    }
+  }
+  flush();
+}
+// ------------------------------------------------------------------------------------------------
+// Pose and rig-pose entries where the point terms have their own kernel (points_separate): the 21 (rig: 78) products of the
+// 6 (12) hot columns and their 6 (12) entries of J^T r, summed over the observations of an (image, camera) segment.
+// k_accumulate walks such a chunk observation by observation through a chain of dependent loads (flag -> camera -> record
+// -> LDS); here a wavefront fetches the record headers of kPoseStage consecutive observations and their block positions
+// with coalesced loads into LDS first, and the walk that follows reads LDS only.  Same slots per lane, same order of the
+// sums within a wavefront and the same flush on a change of the (image, camera) key as k_accumulate.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPoseStage = 32;                   // observations staged per wavefront and step: 4 x 32 x 27 doubles = 27 KB of LDS
+static_assert(kAccChunkHot % kPoseStage == 0, "a wavefront's chunk is a whole number of stages");
+template <bool DET, bool RIG>
+__global__ void __launch_bounds__(256) k_accumulate_poses(PassArgs a, AccumLayout L, int rec_doubles, const uint8_t* __restrict__ flags,
+                                                          const double* __restrict__ jrec, AccumTargets T, const double* __restrict__ det_scale) {
+  typedef typename Acc<DET>::T acc_t;
+  constexpr int NH = RIG ? 12 : 6;               // hot columns
+  constexpr int NHP = NH * (NH + 1) / 2;         // their pairs
+  constexpr int ND = RIG ? 27 : 15;              // doubles of the record header in front of the point block: [res 2][weight][pose 2x6][rig 2x6]
+  constexpr int SLOTS = (NHP + NH + 63) / 64;    // per lane: slot s < NHP is pair (i, k), slot NHP + i is b entry i
+  const double scale = DET ? det_scale[0] : 1.0;
+  const double scale_b = DET ? det_scale[1] : 1.0;
+  __shared__ double s_hdr[4][kPoseStage][ND];
+  __shared__ int s_pose[4][kPoseStage], s_rig[4][kPoseStage];      // first row of the pose (-1: no Jacobian) / rig-pose block
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t o_begin = ((int64_t)blockIdx.x * 4 + wv) * kAccChunkHot;
+  // column i of the hot set sits at header offsets 3 + i / 9 + i (pose) or 9 + i / 15 + i (rig pose, i >= 6): pixel row 0 / 1
+  int hs_i[SLOTS], hs_k[SLOTS];
+#pragma unroll
+  for (int t = 0; t < SLOTS; ++t) {
+    const int sidx = lane + 64 * t;
+    hs_i[t] = -1; hs_k[t] = -1;
+    if (sidx < NHP) {
+      int rem = sidx, i = 0;
+      while (rem >= NH - i) { rem -= NH - i; ++i; }
+      hs_i[t] = i; hs_k[t] = i + rem;
+    } else if (sidx < NHP + NH) {
+      hs_i[t] = sidx - NHP; hs_k[t] = -2;        // b entry
+    }
+  }
+  acc_t hot[SLOTS];
+#pragma unroll
+  for (int t = 0; t < SLOTS; ++t) hot[t] = 0;
+  int cur_pose = -1, cur_rig = -1;
+  auto flush = [&]() {
+    if (cur_pose < 0) return;
+#pragma unroll
+    for (int t = 0; t < SLOTS; ++t) {
+      if (hs_i[t] < 0) continue;
+      const int row = hs_i[t] < 6 ? cur_pose + hs_i[t] : cur_rig + hs_i[t] - 6;
+      if (hs_k[t] == -2) acc_add_b<DET>(L, T, row, hot[t]);
+      else acc_add_H<DET>(L, T, row, hs_k[t] < 6 ? cur_pose + hs_k[t] : cur_rig + hs_k[t] - 6, hot[t]);
+      hot[t] = 0;
+    }
+  };
+  for (int st = 0; st < kAccChunkHot; st += kPoseStage) {
+    const int64_t o0 = o_begin + st;
+    if (o0 >= a.n_obs) break;
+    const int nst = (int)(a.n_obs - o0 < kPoseStage ? a.n_obs - o0 : kPoseStage);
+    __builtin_amdgcn_wave_barrier();             // the previous stage's LDS reads are done before it is overwritten
+    if (lane < nst) {
+      const int64_t o = o0 + lane;
+      const int img = a.obs_image[o];
+      s_pose[wv][lane] = flags[o] == 3 ? L.first_rig_tr_global + 6 * (a.pose_slot ? a.pose_slot[img] : img) : -1;
+      s_rig[wv][lane] = L.first_camera_tr_rig + 6 * a.obs_camera[o];
+    }
+    for (int idx = lane; idx < nst * ND; idx += 64) {
+      const int c = idx / ND, k = idx - c * ND;
+      s_hdr[wv][c][k] = jrec[(size_t)(o0 + c) * rec_doubles + k];
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    for (int c = 0; c < nst; ++c) {
+      const int pose_idx = __builtin_amdgcn_readfirstlane(s_pose[wv][c]);
+      if (pose_idx < 0) continue;                // wave-uniform
+      const int rig_idx = __builtin_amdgcn_readfirstlane(s_rig[wv][c]);
+      if (pose_idx != cur_pose || rig_idx != cur_rig) {
+        flush();
+        cur_pose = pose_idx; cur_rig = rig_idx;
+      }
+      const double* h = s_hdr[wv][c];
+      const double r0 = h[0], r1 = h[1], w = h[2];
+#pragma unroll
+      for (int t = 0; t < SLOTS; ++t) {
+        if (hs_i[t] < 0) continue;
+        const int i = hs_i[t], k = hs_k[t];
+        const double w0 = w * h[(i < 6 ? 3 : 9) + i], w1 = w * h[(i < 6 ? 9 : 15) + i];
+        if (k == -2) hot[t] += Acc<DET>::from(r0 * w0 + r1 * w1, scale_b);
+        else hot[t] += Acc<DET>::from(w0 * h[(k < 6 ? 3 : 9) + k] + w1 * h[(k < 6 ? 9 : 15) + k], scale);
+      }
     }
   }
   flush();
@@ -1507,11 +1594,22 @@ int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& ca
 // sums the 6 x (3 + K_cell) products that fall into its band in LDS (ds_add_f64) and writes the band of
 // the six rows with plain coalesced stores -- zeros included, so B needs no memset and receives no
 // global atomics from these terms (210 of the ~350 per observation).
+//
+// The wavefronts are filled per kind of column:
+//   * point columns: one lane per (observation, point column), kStripPointGroup = 21 observations of the imageset per
+//     wavefront trip, whatever band the point falls into (a band that holds no point column skips the scan);
+//   * grid columns: the observations that reach the band (band_mask) are listed per pass of 64 * kStripWaves observations
+//     and their K_slot = 16 x (largest parameters per control point) grid columns are laid end to end; a wavefront trip takes
+//     64 consecutive entries of that sequence (two central observations, or 64 of the 80 columns of non-central ones), the
+//     weight and the twelve pose entries of a record are loaded once per observation and trip and handed to the lanes with
+//     lane broadcasts, and the per-camera constants come from LDS.
+// Both paths issue every level of their dependent loads for kStripUnroll trips before the first use, as
+// k_accumulate_points does.
 // ------------------------------------------------------------------------------------------------
 constexpr int kStripBand = 1024;
-// bit t of band_mask[o]: observation o couples its pose to a dense column of band t (<= 64 bands = 65 536 columns -- the
-// 4-camera rig of BASELINE configs[4] has 42; wider systems fall back to "all bands")
-__global__ void __launch_bounds__(256) k_strip_band_mask(PassArgs a, AccumLayout L, const uint8_t* __restrict__ flags,
+// bit t of band_mask[o]: observation o couples its pose to a GRID column of band t (<= 64 bands = 65 536 columns -- the
+// 4-camera rig of BASELINE configs[4] has 42; wider systems fall back to "all bands").  The point columns need no mask.
+__global__ void __launch_bounds__(256) k_strip_band_mask(PassArgs a, const uint8_t* __restrict__ flags,
                                                          const int* __restrict__ cells, unsigned long long* __restrict__ band_mask, int n_bands) {
   const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= a.n_obs) return;
@@ -1519,78 +1617,160 @@ __global__ void __launch_bounds__(256) k_strip_band_mask(PassArgs a, AccumLayout
   if (n_bands > 64) { band_mask[o] = ~0ull; return; }
   const CamDev cd = a.cams[a.obs_camera[o]];
   unsigned long long m = 0ull;
-  const int pc = L.first_points - L.block_dof + 3 * a.obs_point[o];
-  m |= 1ull << (pc / kStripBand); m |= 1ull << ((pc + 2) / kStripBand);
-  if (!L.localize_only) {
-    const int cx0 = cells[2 * o], cy0 = cells[2 * o + 1];
-    for (int c = 0; c < 16; ++c) {
-      const int col = grid_column(cd, (cx0 + (c & 3)) + (cy0 + (c >> 2)) * cd.gw, 0);
-      m |= 1ull << (col / kStripBand); m |= 1ull << ((col + cd.params_per_point - 1) / kStripBand);
-    }
+  const int cx0 = cells[2 * o], cy0 = cells[2 * o + 1];
+  for (int c = 0; c < 16; ++c) {
+    const int col = grid_column(cd, (cx0 + (c & 3)) + (cy0 + (c >> 2)) * cd.gw, 0);
+    m |= 1ull << (col / kStripBand); m |= 1ull << ((col + cd.params_per_point - 1) / kStripBand);
   }
   band_mask[o] = m;
 }
 constexpr int kStripWaves = 8;
+constexpr int kStripPointGroup = 21;            // observations per wavefront trip of the point path (3 lanes each, lane 63 idle)
+constexpr int kStripUnroll = 2;                 // trips per wavefront whose loads are in flight together
+// A trip of the grid path covers 64 consecutive entries of slots of K_slot = 32 or 80 columns that start at a multiple of 64:
+// two observations at the most, whose headers sit in lanes 0-12 and 16-28.
+constexpr int kStripTripObs = 2;
+static_assert(kMaxGridCols == 80, "k_accumulate_strips: a wavefront trip is assumed to cover at most kStripTripObs observations");
 template <bool DET>
-__global__ void __launch_bounds__(64 * kStripWaves) k_accumulate_strips(PassArgs a, AccumLayout L, int rec_doubles, const uint8_t* __restrict__ flags,
+__global__ void __launch_bounds__(64 * kStripWaves) k_accumulate_strips(PassArgs a, AccumLayout L, int n_points, int rec_doubles,
+                                                            const uint8_t* __restrict__ flags,
                                                             const double* __restrict__ jrec, const int* __restrict__ cells,
                                                             const unsigned long long* __restrict__ band_mask,
                                                             const int64_t* __restrict__ img_start, double* __restrict__ B, int ld,
                                                             const double* __restrict__ det_scale) {
+  constexpr int U = kStripUnroll, G = kStripPointGroup;
   __shared__ double acc[6][kStripBand];      // DET: the same 8-byte slots hold fixed-point integers (zero bits = 0 in both)
+  __shared__ int s_per[kMaxCameras], s_gw[kMaxCameras], s_off[kMaxCameras];      // per camera: parameters per control point, grid width, first column
+  __shared__ const int* s_perm[kMaxCameras];                                     // ... and the order of its control points
   const double scale = DET ? *det_scale : 1.0;
   const int img = blockIdx.x, band = blockIdx.y;
   const int col_lo = band * kStripBand;
   const int col_hi = min(col_lo + kStripBand, ld);
   for (int i = threadIdx.x; i < 6 * kStripBand; i += 64 * kStripWaves) (&acc[0][0])[i] = 0.0;
+  if (threadIdx.x < a.n_cameras) {
+    const CamDev& cd = a.cams[threadIdx.x];
+    s_per[threadIdx.x] = cd.params_per_point; s_gw[threadIdx.x] = cd.gw; s_off[threadIdx.x] = cd.intr_offset; s_perm[threadIdx.x] = cd.gperm;
+  }
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const unsigned long long bit = 1ull << (band & 63);
   const int64_t o_begin = img_start[img], o_end = img_start[img + 1];
+
+  // ---- point columns ----
+  const int pt_lo = L.first_points - L.block_dof, pt_hi = pt_lo + 3 * n_points;
+  if (col_lo < pt_hi && pt_lo < col_hi) {
+    const int j = lane / 3, c = lane - 3 * j;
+    const int64_t ntrips = (o_end - o_begin + G - 1) / G;
+    for (int64_t t0 = wv; t0 < ntrips; t0 += kStripWaves * U) {
+      int64_t o[U]; bool live[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        o[u] = o_begin + (t0 + u * kStripWaves) * G + j;
+        live[u] = j < G && o[u] < o_end;
+        if (!live[u]) o[u] = o_begin;
+      }
+      uint8_t fl[U]; int pt[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) { fl[u] = flags[o[u]]; pt[u] = a.obs_point[o[u]]; }
+      int col[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        col[u] = pt_lo + 3 * pt[u] + c;
+        live[u] = live[u] && fl[u] == 3 && col[u] >= col_lo && col[u] < col_hi;
+      }
+      double w[U], j0[U], j1[U], h0[U][6], h1[U][6];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (!live[u]) continue;
+        const double* rec = jrec + (size_t)o[u] * rec_doubles;
+        w[u] = rec[2]; j0[u] = rec[27 + c]; j1[u] = rec[30 + c];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { h0[u][k] = rec[3 + k]; h1[u][k] = rec[9 + k]; }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (!live[u]) continue;
+        const double w0 = w[u] * j0[u], w1 = w[u] * j1[u];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Acc<DET>::add(&acc[k][col[u] - col_lo], Acc<DET>::from(h0[u][k] * w0 + h1[u][k] * w1, scale));
+      }
+    }
+  }
+
+  // ---- grid columns ----
+  int kslot = 0;
+  if (!L.localize_only)
+    for (int cam = 0; cam < a.n_cameras; ++cam) kslot = max(kslot, 16 * s_per[cam]);
   // kStripWaves wavefronts.  Pass = 64 * kStripWaves consecutive observations: every wavefront loads the band masks of one group of 64
-  // (one coalesced load instead of a chain of dependent L2 round trips) and publishes its ballot; then the matching
-  // observations of the whole pass are dealt round-robin to the wavefronts (the matches of one band are neighbours
-  // in the observation order, so whole groups would leave most wavefronts idle), all 64 lanes on an observation's
-  // columns.
+  // (one coalesced load instead of a chain of dependent L2 round trips) and publishes its ballot; the matching observations of
+  // the whole pass are listed in order and their slots of kslot columns are dealt in trips of 64 entries round-robin to the
+  // wavefronts (the matches of one band are neighbours in the observation order, so whole groups would leave most wavefronts idle).
   __shared__ unsigned long long gmask[kStripWaves];
-  for (int64_t p0 = o_begin; p0 < o_end; p0 += 64 * kStripWaves) {
+  __shared__ unsigned short s_list[64 * kStripWaves];
+  const unsigned long long bit = 1ull << (band & 63);
+  const int hl = lane >> 4, he = lane & 15;      // header element he of the trip's observation hl is loaded by this lane
+  for (int64_t p0 = o_begin; kslot > 0 && p0 < o_end; p0 += 64 * kStripWaves) {
     const int64_t mine = p0 + 64 * wv + lane;
     const bool hit = mine < o_end && (band_mask[mine] & bit);
     const unsigned long long bal = __ballot(hit);
     if (lane == 0) gmask[wv] = bal;
     __syncthreads();
-    int seen = 0;
-    for (int gidx = 0; gidx < kStripWaves; ++gidx) {
-      unsigned long long todo = gmask[gidx];
-      while (todo) {
-        const int idx = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        if (((seen++) % kStripWaves) != wv) continue;
-        const int64_t o = p0 + 64 * gidx + idx;
-        const CamDev cd = a.cams[a.obs_camera[o]];
-        const int per = cd.params_per_point;
-        const int Kg = L.localize_only ? 0 : per * 16;
-        const int nc = 3 + Kg;                              // dense columns of this observation coupled to the pose
-        const double* rec = jrec + (size_t)o * rec_doubles;
-        const int cx0 = cells[2 * o], cy0 = cells[2 * o + 1];
-        const int point_col = L.first_points - L.block_dof + 3 * a.obs_point[o];
-        const double w = rec[2];
-        for (int c = lane; c < nc; c += 64) {
-          int col; double j0, j1;
-          if (c < 3) { col = point_col + c; j0 = rec[27 + c]; j1 = rec[30 + c]; }
-          else {
-            const int g = c - 3, cell = g / per, d = g - cell * per;
-            col = grid_column(cd, (cx0 + (cell & 3)) + (cy0 + (cell >> 2)) * cd.gw, d);
-            j0 = rec[kRecHeader + g]; j1 = rec[kRecHeader + Kg + g];
-          }
-          if (col < col_lo || col >= col_hi) continue;
-          const double w0 = w * j0, w1 = w * j1;
+    int before = 0, total = 0;
+    for (int g = 0; g < kStripWaves; ++g) {
+      const int n = __popcll(gmask[g]);
+      if (g < wv) before += n;
+      total += n;
+    }
+    if (hit) s_list[before + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)(64 * wv + lane);
+    __syncthreads();
+    const int items = total * kslot;
+    for (int f0 = 64 * wv; f0 < items; f0 += 64 * kStripWaves * U) {
+      // level 0: the observation of this lane's entry, and the one whose header this lane fetches
+      int64_t o[U], oh[U]; int g[U], src[U]; bool live[U], hlive[U];
 #pragma unroll
-          for (int k = 0; k < 6; ++k) Acc<DET>::add(&acc[k][col - col_lo], Acc<DET>::from(rec[3 + k] * w0 + rec[9 + k] * w1, scale));
-        }
+      for (int u = 0; u < U; ++u) {
+        const int first = f0 + u * 64 * kStripWaves, f = first + lane;
+        live[u] = f < items;
+        const int m = live[u] ? f / kslot : 0;
+        g[u] = f - m * kslot;
+        o[u] = p0 + s_list[m];
+        const int mh = first / kslot + hl;
+        hlive[u] = first < items && hl < kStripTripObs && he < 13 && mh < total;
+        oh[u] = p0 + s_list[hlive[u] ? mh : 0];
+        src[u] = live[u] ? 16 * (m - first / kslot) : 0;      // first header lane of this entry's observation (the trip's first or second)
+      }
+      // level 1: camera, patch origin and header
+      int cam[U], cx[U], cy[U]; double hv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        cam[u] = a.obs_camera[o[u]]; cx[u] = cells[2 * o[u]]; cy[u] = cells[2 * o[u] + 1];
+        hv[u] = hlive[u] ? jrec[(size_t)oh[u] * rec_doubles + 2 + he] : 0.0;
+      }
+      // level 2: column (through the order of the control points) and the two Jacobian entries
+      int col[U]; double j0[U], j1[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int per = s_per[cam[u]], Kg = 16 * per, gg = g[u];
+        live[u] = live[u] && gg < Kg;              // a camera with fewer columns than the slot
+        const int cell = live[u] ? gg / per : 0, d = live[u] ? gg - cell * per : 0;
+        const int seq = (cx[u] + (cell & 3)) + (cy[u] + (cell >> 2)) * s_gw[cam[u]];
+        const int* perm = s_perm[cam[u]];
+        col[u] = s_off[cam[u]] + per * (perm ? perm[seq] : seq) + d;
+        const double* rec = jrec + (size_t)o[u] * rec_doubles + kRecHeader;
+        j0[u] = live[u] ? rec[gg] : 0.0; j1[u] = live[u] ? rec[Kg + gg] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        // the header from the lanes that loaded it (every lane takes part: wave-uniform control flow)
+        const double w = __shfl(hv[u], src[u], 64);
+        double h0[6], h1[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { h0[k] = __shfl(hv[u], src[u] + 1 + k, 64); h1[k] = __shfl(hv[u], src[u] + 7 + k, 64); }
+        if (!live[u] || col[u] < col_lo || col[u] >= col_hi) continue;
+        const double w0 = w * j0[u], w1 = w * j1[u];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Acc<DET>::add(&acc[k][col[u] - col_lo], Acc<DET>::from(h0[k] * w0 + h1[k] * w1, scale));
       }
     }
-    __syncthreads();
   }
   __syncthreads();
   const int slot = a.pose_slot ? a.pose_slot[img] : img;
@@ -1610,13 +1790,13 @@ int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, i
   al.first_rig_tr_global = L.first_rig_tr_global; al.first_camera_tr_rig = L.first_camera_tr_rig;
   al.first_points = L.first_points; al.block_dof = L.block_dof; al.block_size = L.block_size; al.dense_dof = L.dense_dof;
   const int bands = (ld + kStripBand - 1) / kStripBand;
-  if (a.n_obs > 0)
-    hipLaunchKernelGGL(k_strip_band_mask, dim3((unsigned)((a.n_obs + 255) / 256)), dim3(256), 0, s, a, al, flags, cells, band_mask, bands);
+  if (a.n_obs > 0 && !L.localize_only)      // (localize_only: no grid columns, the mask is not read)
+    hipLaunchKernelGGL(k_strip_band_mask, dim3((unsigned)((a.n_obs + 255) / 256)), dim3(256), 0, s, a, flags, cells, band_mask, bands);
   if (det_scale)
-    hipLaunchKernelGGL(k_accumulate_strips<true>, dim3((unsigned)n_images, (unsigned)bands), dim3(64 * kStripWaves), 0, s, a, al, rec_doubles, flags,
+    hipLaunchKernelGGL(k_accumulate_strips<true>, dim3((unsigned)n_images, (unsigned)bands), dim3(64 * kStripWaves), 0, s, a, al, L.n_points, rec_doubles, flags,
                        jrec, cells, band_mask, img_start, B, ld, det_scale);
   else
-    hipLaunchKernelGGL(k_accumulate_strips<false>, dim3((unsigned)n_images, (unsigned)bands), dim3(64 * kStripWaves), 0, s, a, al, rec_doubles, flags,
+    hipLaunchKernelGGL(k_accumulate_strips<false>, dim3((unsigned)n_images, (unsigned)bands), dim3(64 * kStripWaves), 0, s, a, al, L.n_points, rec_doubles, flags,
                        jrec, cells, band_mask, img_start, B, ld, det_scale);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
@@ -1632,10 +1812,15 @@ int launch_accumulate(const PassArgs& a, const Layout& L, int rec_doubles, const
   al.first_points = L.first_points; al.block_dof = L.block_dof; al.block_size = L.block_size; al.dense_dof = L.dense_dof;
   const int chunk = points_separate ? kAccChunkHot : kAccChunk;
   const dim3 grid((unsigned)((a.n_obs + 4 * chunk - 1) / (4 * chunk)));
-  if (det_scale)
-    hipLaunchKernelGGL(k_accumulate<true>, grid, dim3(256), 0, s, a, al, rec_doubles, flags, jrec, cells, pair_tables, pair_counts, t, det_scale, points_separate);
+#define CBA_POSES(DET_, RIG_) hipLaunchKernelGGL((k_accumulate_poses<DET_, RIG_>), grid, dim3(256), 0, s, a, al, rec_doubles, flags, jrec, t, det_scale)
+  if (points_separate) {      // only the pose / rig-pose entries are left
+    if (det_scale) { if (L.rig_in_state) CBA_POSES(true, true); else CBA_POSES(true, false); }
+    else { if (L.rig_in_state) CBA_POSES(false, true); else CBA_POSES(false, false); }
+  } else if (det_scale)
+    hipLaunchKernelGGL(k_accumulate<true>, grid, dim3(256), 0, s, a, al, rec_doubles, flags, jrec, cells, pair_tables, pair_counts, t, det_scale);
   else
-    hipLaunchKernelGGL(k_accumulate<false>, grid, dim3(256), 0, s, a, al, rec_doubles, flags, jrec, cells, pair_tables, pair_counts, t, det_scale, points_separate);
+    hipLaunchKernelGGL(k_accumulate<false>, grid, dim3(256), 0, s, a, al, rec_doubles, flags, jrec, cells, pair_tables, pair_counts, t, det_scale);
+#undef CBA_POSES
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

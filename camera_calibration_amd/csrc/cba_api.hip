@@ -1,7 +1,8 @@
 // C-ABI implementation (include/cba.h): device-resident problem, LM control flow
 // (LMOptimizer::OptimizeImpl, libvis/src/libvis/lm_optimizer.h:629-991 in the reference tree) and the
 // rest of the stateful entry points (the stateless ones: cba_oneshot.hip).  Everything numerical runs in the HIP kernels of
-// kernels_obs.hip / kernels_linalg.hip / kernels_ldlt*.hip / kernels_backsolve.hip / kernels_gridfirst.hip; there is no CPU fallback.
+// kernels_project.hip / kernels_fd.hip / kernels_obs.hip / kernels_update.hip / kernels_linalg.hip / kernels_ldlt*.hip /
+// kernels_backsolve.hip / kernels_gridfirst.hip; there is no CPU fallback.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>

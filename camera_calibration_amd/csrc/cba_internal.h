@@ -99,8 +99,15 @@ struct Layout {
 constexpr int kMaxCameras = 16;
 constexpr int kMaxGridCols = 80;                       // 5 * 16
 constexpr int kMaxCols = 6 + 6 + 3 + kMaxGridCols;     // pose + rig + point + grid
-// Jacobian record per observation (doubles): [res 2][weight 1][pose 2x6][rig 2x6][point 2x3][grid 2xKg]
-constexpr int kRecHeader = 3 + 12 + 12 + 6;
+// Jacobian record per observation (doubles): [res 2][weight 1][pose 2x6][rig 2x6][point 2x3][grid 2xKg].  Of a 2 x n block
+// row 0 (d pixel x) comes first, row 1 (d pixel y) right behind it; the two rows of the grid block are Kg apart.
+constexpr int kRecRes = 0;                                              // residual x, y
+constexpr int kRecWeight = kRecRes + 2;                                 // Huber weight
+constexpr int kRecPose0 = kRecWeight + 1, kRecPose1 = kRecPose0 + 6;    // d pixel / d imageset pose
+constexpr int kRecRig0 = kRecPose1 + 6, kRecRig1 = kRecRig0 + 6;        // d pixel / d rig pose of the camera
+constexpr int kRecPoint0 = kRecRig1 + 6, kRecPoint1 = kRecPoint0 + 3;   // d pixel / d pattern point
+constexpr int kRecHeader = kRecPoint1 + 3;                              // first double of the grid block
+static_assert(kRecHeader == 33 && kRecRig0 == 15 && kRecPoint0 == 27, "record layout (cba_jacobian_record_doubles, the tests' readers)");
 
 struct DevState {
   DevBuf<double> rig_tr_global;      // 7N
@@ -124,8 +131,8 @@ struct PassArgs {
   double fd_delta;
   const int* pose_slot;     // block position of each imageset (rows of B sorted by image footprint) or null
   // straggler split: observations whose base projection exceeds the iteration cap of the one-lane kernel are listed by
-  // it and finished by the 16-lanes-per-observation kernel (kernels_obs.hip); in the Jacobian pass that launch and the
-  // finite-difference tasks of the listed observations run on a side stream while the main launch skips them
+  // it and finished by the 16-lanes-per-observation kernel (kernels_project.hip: k_base_project_slow); in the Jacobian pass
+  // that launch and the finite-difference tasks of the listed observations run on a side stream while the main launch skips them
   const int* obs_list;      // null = all observations in order
   const int* obs_count;     // device: entries in obs_list (clamped to obs_list_cap)
   int obs_list_cap;
@@ -169,7 +176,7 @@ int device_side_streams(hipStream_t* chain, hipStream_t* mid, hipStream_t* far);
 int prepare_device_streams();
 int make_main_stream(hipStream_t* s);
 
-// ---- kernels_obs.hip ----
+// ---- kernels_project.hip (pose composition, base projection, stateless model-level kernels) ----
 int launch_compose_poses(const DevState& st, int N, int C, double* itg, hipStream_t s);
 int launch_tangents(const double* dir_grid, double* tang, int G, hipStream_t s);
 // base projection of every observation; lanes that exceed the iteration cap are appended to defer_list (and marked in
@@ -177,6 +184,11 @@ int launch_tangents(const double* dir_grid, double* tang, int G, hipStream_t s);
 int launch_base_project(const PassArgs& a, int model_mask, double* cost_vec, double* pixels, uint8_t* flags, int* defer_list,
                         int* defer_count, int defer_cap, uint8_t* defer_skip, int outer_cap, const uint8_t* fd_slow, hipStream_t s);
 int launch_base_project_slow(const PassArgs& a, int model_mask, double* cost_vec, double* pixels, uint8_t* flags, hipStream_t s);
+int launch_project_points(const CamDev* cam_dev, int model, int64_t n, const double* local, const double* init,
+                          double* pixels, uint8_t* ok, hipStream_t s);
+int launch_unproject(const CamDev* cam_dev, int model, int64_t n, const double* pixels, double* lines, double* jac,
+                     uint8_t* ok, hipStream_t s);
+// ---- kernels_fd.hip (finite-difference tasks of the Jacobian pass) ----
 // redo / redo_count: device work list (redo_cap entries / one int) for the tasks that leave their staged patch; tasks that find
 // the list full are counted in *redo_overflow
 // schedule: 0 = pooled (workgroup task pool, one LM attempt per trip), 1 = one task per lane; same expressions in the same order,
@@ -185,31 +197,27 @@ int launch_base_project_slow(const PassArgs& a, int model_mask, double* cost_vec
 int launch_fd_tasks(const PassArgs& a, int model_mask, int tasks_per_obs, int localize_only, const double* pixels,
                     const uint8_t* flags, double* fd_out, uint8_t* fd_ok, int64_t* redo, int* redo_count, int redo_cap, int* redo_overflow,
                     hipStream_t s, int schedule = 0);
-int launch_assemble(const PassArgs& a, const Layout& L, const DevState& st, int tasks_per_obs, int rec_doubles,
-                    const double* pixels, uint8_t* flags, const double* fd_out, const uint8_t* fd_ok, double* jrec,
-                    int* cells, uint8_t* fd_slow, hipStream_t s);
+// ---- kernels_obs.hip (stage B: Jacobian records and their accumulation; the records are a.jrec, a.rec_doubles apart) ----
+int launch_assemble(const PassArgs& a, const Layout& L, const DevState& st, int tasks_per_obs, const double* pixels, uint8_t* flags,
+                    const double* fd_out, const uint8_t* fd_ok, int* cells, uint8_t* fd_slow, hipStream_t s);
 struct AccumTargets {
   double* Dblk; double* bblk; double* B; double* Hdd; double* bd;
 };
 static_assert(std::is_trivially_copyable_v<AccumTargets>);
-int launch_accumulate(const PassArgs& a, const Layout& L, int rec_doubles, const uint8_t* flags, const double* jrec,
-                      const int* cells, const uint32_t* pair_tables, const int* pair_counts, AccumTargets t,
-                      const double* det_scale, int points_separate, hipStream_t s);
+int launch_accumulate(const PassArgs& a, const Layout& L, const uint8_t* flags, const int* cells, const uint32_t* pair_tables,
+                      const int* pair_counts, AccumTargets t, const double* det_scale, int points_separate, hipStream_t s);
 // terms with a pattern-point column, bucketed by (camera, point) (poses eliminated); key lists: cba_set_observations
-int launch_accumulate_points(const PassArgs& a, const Layout& L, const std::vector<cba_camera>& cams, int rec_doubles, const uint8_t* flags,
-                             const double* jrec, const int* cells, const int* key_start, const int* key_obs, AccumTargets t,
-                             const double* det_scale, hipStream_t s);
+int launch_accumulate_points(const PassArgs& a, const Layout& L, const std::vector<cba_camera>& cams, const uint8_t* flags, const int* cells,
+                             const int* key_start, const int* key_obs, AccumTargets t, const double* det_scale, hipStream_t s);
 // deterministic mode (cba_config.deterministic): fixed-point scale of a pass, conversion of an accumulated array
-int launch_det_scale(int64_t n, int rec_doubles, int used_doubles, const uint8_t* flags, const double* jrec, unsigned long long* bits,
-                     double* scale, hipStream_t s);
+int launch_det_scale(const PassArgs& a, const uint8_t* flags, unsigned long long* bits, double* scale, hipStream_t s);
 int launch_det_convert(double* p, size_t n, const double* det_scale, hipStream_t s);
-int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, int rec_doubles, const uint8_t* flags, const double* jrec,
-                             const int* cells, unsigned long long* band_mask, const int64_t* img_start, double* B, int ld, const double* det_scale,
-                             hipStream_t s);
-int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const std::vector<int>& cell_base_host,
-                            int rec_doubles, int ld, const uint8_t* flags, const double* jrec, const int* cells,
-                            const int* cell_base, int* count, int* start, int* fill, int* order, double* Hdd,
-                            int rig_row_first, const double* det_scale, double* bd, hipStream_t s);
+int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, const uint8_t* flags, const int* cells,
+                             unsigned long long* band_mask, const int64_t* img_start, double* B, int ld, const double* det_scale, hipStream_t s);
+int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const std::vector<int>& cell_base_host, int ld,
+                            const uint8_t* flags, const int* cells, const int* cell_base, int* count, int* start, int* fill, int* order,
+                            double* Hdd, int rig_row_first, const double* det_scale, double* bd, hipStream_t s);
+// ---- kernels_update.hip (cost reductions, state update) ----
 // 8 outputs: [0] sum ref (valid), [1] sum test (valid), [2] masked ref, [3] masked test, [4] count both valid,
 // [5] n valid ref, [6] n valid test, [7] n jac dropped (flags)
 int launch_reduce_costs(const double* ref, const double* test, const uint8_t* flags, int64_t n, double* partials,
@@ -224,10 +232,6 @@ int launch_fit_accumulate(int gw, int gh, int64_t n, const double* rec, const in
                           int* order, double* H, int ld, double* b, hipStream_t s);
 int launch_fit_set_rhs(double* S, int ld, const double* b, int n, hipStream_t s);
 int launch_fit_diag_sum(const double* H, int ld, int n, double* out, hipStream_t s);
-int launch_project_points(const CamDev* cam_dev, int model, int64_t n, const double* local, const double* init,
-                          double* pixels, uint8_t* ok, hipStream_t s);
-int launch_unproject(const CamDev* cam_dev, int model, int64_t n, const double* pixels, double* lines, double* jac,
-                     uint8_t* ok, hipStream_t s);
 
 // ---- kernels_linalg.hip (Schur stage, the fp64 MFMA GEMM, pack / diagonal kernels) ----
 // Inverse of the (bs x bs) diagonal blocks with lambda added, and Dinv*b.

@@ -1,5 +1,6 @@
 // Passes over the observations (include/cba.h): stage timers, the residual pass, the Jacobian pass with the accumulation of
-// the normal equations, the scalar reductions across ranks.  The kernels are those of kernels_obs.hip.
+// the normal equations, the scalar reductions across ranks.  The kernels are those of kernels_project.hip,
+// kernels_fd.hip and kernels_obs.hip.
 #include "cba_problem.h"
 
 namespace cba {
@@ -137,15 +138,14 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   const bool side = !L.localize_only;      // the per-cell accumulation runs on the side stream
   // (Running the assembly / accumulation of one chunk of imagesets next to the finite-difference launches of the
   // next chunk was measured and gained nothing: the two share the same CUs and the sum stayed the same.)
-  CBA_TRY(launch_assemble(a, L, p->st[w], p->tasks_per_obs, p->rec_doubles, p->pixels, p->flags, p->fd_out, p->fd_ok,
-                          p->jrec, p->cells, p->fd_slow, p->stream));
+  CBA_TRY(launch_assemble(a, L, p->st[w], p->tasks_per_obs, p->pixels, p->flags, p->fd_out, p->fd_ok, p->cells, p->fd_slow, p->stream));
   double t0 = now_s();
   CBA_TRY(timer_begin(p, kTimerAccumulate));
   AccumTargets T{p->Dblk, p->bblk, p->B, p->Hdd, p->bd};
   Layout Lp = L;
   Lp.dense_dof = p->n_pad;  // Hdd / B use the padded leading dimension as row stride
   const double* det = p->cfg.deterministic ? (const double*)p->det_scale : nullptr;
-  if (det) CBA_TRY(launch_det_scale(p->n_obs, p->rec_doubles, p->rec_doubles, p->flags, p->jrec, p->det_bits, p->det_scale, p->stream));
+  if (det) CBA_TRY(launch_det_scale(a, p->flags, p->det_bits, p->det_scale, p->stream));
   const int points_separate = (!L.eliminate_points && p->pt_start) ? 1 : 0;
   // The four accumulation kernels write disjoint parts of the system (or add atomically).  The per-cell kernel runs on the side
   // stream next to the others; the per-point kernel (120 KB of LDS per workgroup, one per CU) goes FIRST on the main stream, alone:
@@ -154,18 +154,17 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   if (side) {
     CBA_HIP(hipEventRecord(p->ev_aux0, p->stream));
     CBA_HIP(hipStreamWaitEvent(aux, p->ev_aux0, 0));
-    CBA_TRY(launch_accumulate_cells(a, p->cams, p->cell_base_host, p->rec_doubles, p->n_pad, p->flags, p->jrec, p->cells, p->cell_base,
-                                    p->cell_count, p->cell_start, p->cell_fill, p->cell_order, p->Hdd,
+    CBA_TRY(launch_accumulate_cells(a, p->cams, p->cell_base_host, p->n_pad, p->flags, p->cells, p->cell_base, p->cell_count,
+                                    p->cell_start, p->cell_fill, p->cell_order, p->Hdd,
                                     (!L.eliminate_points && L.rig_in_state) ? L.first_camera_tr_rig - L.block_dof : -1, det, p->bd, aux));
     if (p->gridfirst) CBA_TRY(gridfirst_pass_activity(p, a, aux));      // the activity masks of this pass, behind the per-cell accumulation
     CBA_HIP(hipEventRecord(p->ev_aux1, aux));
   }
   if (points_separate)
-    CBA_TRY(launch_accumulate_points(a, Lp, p->cams, p->rec_doubles, p->flags, p->jrec, p->cells, p->pt_start, p->pt_obs, T, det, p->stream));
+    CBA_TRY(launch_accumulate_points(a, Lp, p->cams, p->flags, p->cells, p->pt_start, p->pt_obs, T, det, p->stream));
   if (!L.eliminate_points)   // B strips (plain stores), the remaining terms are added on top atomically
-    CBA_TRY(launch_accumulate_strips(a, Lp, L.n_images, p->rec_doubles, p->flags, p->jrec, p->cells, p->band_mask, p->img_start, p->B,
-                                     p->n_pad, det, p->stream));
-  CBA_TRY(launch_accumulate(a, Lp, p->rec_doubles, p->flags, p->jrec, p->cells, p->pair_tables, p->pair_counts, T, det, points_separate, p->stream));
+    CBA_TRY(launch_accumulate_strips(a, Lp, L.n_images, p->flags, p->cells, p->band_mask, p->img_start, p->B, p->n_pad, det, p->stream));
+  CBA_TRY(launch_accumulate(a, Lp, p->flags, p->cells, p->pair_tables, p->pair_counts, T, det, points_separate, p->stream));
   if (side) CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_aux1, 0));
   if (det) {   // fixed point -> fp64, in place
     CBA_TRY(launch_det_convert(p->Dblk, nb * bs * bs, det, p->stream));

@@ -61,6 +61,37 @@ def test_straggler_kernel_is_bit_identical_to_the_one_lane_kernel(config, n_imag
     print(case, "failing projections:", n_invalid)
 
 
+def test_observations_that_find_the_straggler_list_full_finish_on_the_one_lane_path():
+    """More observations than the straggler list holds (16384 here), and a threshold of 0 sends every one of them to it: the
+    list fills, and the rest take the `idx >= defer_cap` branch of k_base_project -- the whole projection on the one-lane path,
+    after the capped attempt.  Nothing may depend on which observations found room: bit-identical to the run without hand-over.
+    That the list overflows follows from the code, no counter reports it: with max_outer = 0 the loop of project_target does not
+    run and every lane returns capped, so all n_obs observations take a slot number and the n_obs - 16384 last ones find
+    idx >= defer_cap."""
+    pb, st, _ = syn.baseline_config(2, _gpu_project, n_imagesets=30, grid_wh=(20, 16))
+    assert pb.n_obs > 16384 and pb.n_obs // 8 < 16384       # capacity max(16384, n_obs / 8): about a quarter do not fit
+    out = {}
+    for name, thr in (("one-lane only", 100), ("list full", 0)):
+        e = eng.Engine(pb, deterministic=True)
+        e.set_straggler_threshold(thr)
+        e.set_state(st)
+        cost = e.debug_accumulate()
+        out[name] = dict(cost=cost, flags=e.dump(eng.DUMP_FLAGS), pixels=e.dump(eng.DUMP_PIXELS), vec=e.dump(eng.DUMP_COST_VECTOR),
+                         J=e.dump(eng.DUMP_JACOBIANS), H=e.dump(eng.DUMP_DENSE_H), lastp=e.get_last_projection())
+        e.close()
+    case = f"straggler list full, cfg 2 (30 imagesets, {pb.n_obs} observations)"
+    ref, d = out["one-lane only"], out["list full"]
+    valid, hasj = (ref["flags"] & 1).astype(bool), ((ref["flags"] >> 1) & 1).astype(bool)
+    assert (~valid).sum() > 0, "the test problem has no failing projection"
+    everyone = np.ones(pb.n_obs, dtype=bool)
+    for key, m in (("flags", everyone), ("pixels", valid), ("vec", everyone), ("J", hasj), ("H", slice(None)), ("lastp", everyone)):
+        check_equal(case, f"{key} entries that differ", int(np.count_nonzero(np.asarray(ref[key])[m] != np.asarray(d[key])[m])))
+    check_equal(case, "cost differs", int(ref["cost"] != d["cost"]))
+    _, vec_ref = orc.OracleProblem(pb).cost_pass(st)
+    check_equal(case, "valid mask vs oracle", int(np.count_nonzero((d["vec"] >= 0) != (vec_ref >= 0))))
+    print(case, "failing projections:", int((~valid).sum()))
+
+
 @pytest.mark.parametrize("config,n_imagesets,grid_wh", [(2, 16, (20, 16)), (4, 10, (16, 12)), (3, 8, (20, 16)), (2, 40, None)])
 def test_pooled_finite_difference_schedule_agrees_with_one_task_per_lane(config, n_imagesets, grid_wh):
     """The finite-difference re-projections (3 + K_cell per observation) run either one task per lane (rounds 2-4) or from a

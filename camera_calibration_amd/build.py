@@ -9,9 +9,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcalib_ba_hip.so")
-SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip",
-           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip"]
-HEADERS = ["cba_internal.h", "cba_problem.h", "model.hip.h", "obs_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
+SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip", "cba_report.hip",
+           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip"]
+HEADERS = ["cba_internal.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]  # keep MFMA accumulators in VGPRs: no AGPR<->VGPR copies in the K loop
 
@@ -66,6 +66,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if failed:
         raise RuntimeError("hipcc compilation failed")
     check_tail_m0(os.path.join(CSRC, "kernels_ldlt.o"))
+    check_no_scratch(os.path.join(CSRC, "kernels_report.o"), NO_SCRATCH_KERNELS)
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
     with open(FLAGS_STAMP, "w") as f:
         f.write(_extra_flags())
@@ -92,6 +93,48 @@ def disassemble_device_code(obj: str) -> str:
         if len(dev) != 1:
             raise RuntimeError(f"expected one gfx950 code object in {obj}, found {dev}")
         return subprocess.check_output([objdump, "-d", os.path.join(tmp, dev[0])], text=True)
+
+
+def kernel_resources(obj: str) -> dict:
+    """{mangled kernel name: {vgpr_count, group_segment_fixed_size (LDS bytes), private_segment_fixed_size (scratch bytes per lane)}}
+    from the metadata notes of the gfx950 code object in a compiled .hip object."""
+    import re
+    import tempfile
+    objdump, readelf = _llvm_tool("llvm-objdump"), _llvm_tool("llvm-readelf")
+    with tempfile.TemporaryDirectory() as tmp:
+        local = os.path.join(tmp, "k.o")
+        shutil.copy(obj, local)
+        subprocess.check_call([objdump, "--offloading", local], stdout=subprocess.DEVNULL, cwd=tmp)
+        dev = [f for f in os.listdir(tmp) if "gfx950" in f]
+        if len(dev) != 1:
+            raise RuntimeError(f"expected one gfx950 code object in {obj}, found {dev}")
+        notes = subprocess.check_output([readelf, "--notes", os.path.join(tmp, dev[0])], text=True)
+    out = {}
+    for block in notes.split("- .agpr_count")[1:]:           # one metadata map per kernel, keys in alphabetical order
+        name = re.search(r"\.name:\s+(\S+)", block)
+        if name:
+            out[name.group(1)] = {k: int(re.search(r"\." + k + r":\s+(\d+)", block).group(1))
+                                  for k in ("vgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")}
+    return out
+
+
+# kernels of the report that must keep their polygon / patch data out of scratch memory (DESIGN.md section 3)
+NO_SCRATCH_KERNELS = ("k_direction_image", "k_nearest_site", "k_clip_cells")
+
+
+def check_no_scratch(obj: str, kernels) -> int:
+    """Fails the build when one of `kernels` (substring of the mangled name) uses scratch memory.  Returns the kernels checked."""
+    res = kernel_resources(obj)
+    checked = 0
+    for want in kernels:
+        hits = {n: r for n, r in res.items() if want in n}
+        if not hits:
+            raise RuntimeError(f"check_no_scratch: {want} not found in {obj}")
+        for n, r in hits.items():
+            if r["private_segment_fixed_size"] != 0:
+                raise RuntimeError(f"check_no_scratch: {n} uses {r['private_segment_fixed_size']} bytes of scratch per lane")
+            checked += 1
+    return checked
 
 
 # the helper's own write of M0: the "s" operand of the inline asm is any scalar source the compiler picks (an SGPR, vcc_lo / vcc_hi, a

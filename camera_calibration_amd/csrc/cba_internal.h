@@ -233,6 +233,41 @@ int launch_fit_accumulate(int gw, int gh, int64_t n, const double* rec, const in
 int launch_fit_set_rhs(double* S, int ld, const double* b, int n, hipStream_t s);
 int launch_fit_diag_sum(const double* H, int ld, int n, double* out, hipStream_t s);
 
+// ---- kernels_report.hip (calibration report: direction image, nearest-feature rendering, centre point, line offsets) ----
+// directions [H][W][3] fp64 (NaN where Unproject fails) and ok [H][W] may be null; rgb [H][W][3]; use_stage = false: every tile on
+// the gather path (measurements: cba_debug_time_direction_image)
+int launch_direction_image(const CamDev* cam_dev, int model, int W, int H, double* dirs, uint8_t* ok, uint8_t* rgb, hipStream_t s,
+                           bool use_stage = true);
+// Sites of the nearest-feature rendering, bucketed on a uniform grid: bucket b = (y / side4) * bw + x / side4 of the quarter-pixel
+// coordinates holds the sites order[start[b] .. start[b + 1]), ascending by site index.
+struct SiteGrid {
+  int side4;            // bucket side in quarter pixels
+  int bw, bh;
+  const int* start;     // bw * bh + 1
+  const int* order;     // n sites
+  const int* xy;        // 2n quarter-pixel coordinates
+  const float* rgb;     // 3n colours
+};
+static_assert(std::is_trivially_copyable_v<SiteGrid>);
+// a site owns part of a pixel only within d0 + sqrt(2) pixels of its centre (d0: the nearest site); quarter pixels, with a margin
+// that only ever adds candidates (a candidate that owns nothing gets area 0)
+constexpr double kSiteReach4 = 4 * 1.4142135623730951 + 1e-6;
+constexpr int kCandCap = 32;               // candidates per pixel k_clip_cells holds; beyond it the host renders the pixel
+constexpr int kClipVerts = 4 + kCandCap;   // a half-plane adds at most one vertex to a convex polygon
+// list: (pixel, nearest site) of the pixels with several candidates, W * H entries; *list_count: zeroed by the caller
+int launch_nearest_site(const SiteGrid& g, int W, int H, uint8_t* rgb, float* accum, int2* list, int* list_count, hipStream_t s);
+// overflow: pixels with more than kCandCap candidates (W * H entries; *overflow_count zeroed by the caller), left unwritten
+int launch_clip_cells(const SiteGrid& g, int W, int H, const int2* list, int n_list, uint8_t* rgb, float* accum, int* overflow,
+                      int* overflow_count, hipStream_t s);
+// out[0..5] = A (xx xy xz yy yz zz), [6..8] = b, [9] = sum (t1 . o)^2 + (t2 . o)^2, [10] = lines; non-central model only
+constexpr int kCenterSums = 11;
+int center_point_partials_doubles();
+int launch_center_point_sums(const CamDev* cam_dev, double* partials, double* out, hipStream_t s);
+// offsets [H][W][3]; block_max: line_offset_blocks(W, H) maxima of |component|; center: HOST pointer
+int line_offset_blocks(int W, int H);
+int launch_line_offsets(const CamDev* cam_dev, int W, int H, const double* center, double* offsets, double* block_max, hipStream_t s);
+int launch_line_offset_colors(const double* offsets, int W, int H, double max_extent, uint8_t* rgb, hipStream_t s);
+
 // ---- kernels_linalg.hip (Schur stage, the fp64 MFMA GEMM, pack / diagonal kernels) ----
 // Inverse of the (bs x bs) diagonal blocks with lambda added, and Dinv*b.
 int launch_block_inverse(const double* Dblk, const double* bblk, double lambda, int bs, int nb, double* Dinv,

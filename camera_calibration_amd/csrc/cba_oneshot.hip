@@ -4,20 +4,13 @@
 #include <memory>
 
 #include "cba_internal.h"
+#include "cba_model.h"
 
 using namespace cba;
 
 extern "C" {
 
 // ---- model-level entry points: device-resident camera model -----------------------------------------
-struct cba_model {
-  cba_camera cam{};
-  int device = 0;
-  DevBuf<double> d_grid; DevBuf<CamDev> d_cam;
-  // scratch, grown on demand
-  int64_t cap = 0;
-  DevBuf<double> d_a, d_b, d_c, d_j; DevBuf<uint8_t> d_ok;
-};
 static int model_reserve(cba_model* m, int64_t n) {
   if (n <= m->cap) return CBA_OK;
   m->cap = 0;

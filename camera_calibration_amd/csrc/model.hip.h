@@ -137,10 +137,10 @@ struct StagedPatch {
 };                        // was turned into 16 branches per evaluation by the compiler)
 template <int MODEL, bool LDS>
 __device__ __forceinline__ void ctrl_point(const CamDev& c, const Subst& s, lds_cdouble_ptr stage, lds_cdouble_ptr sub_p, int r, int q, int seq,
-                                           double* d, double* o) {
+                                           double* d, double* o, int pitch = 4) {
   if (LDS) {
     constexpr int DIM = (MODEL == kCentral) ? 3 : 6;
-    lds_cdouble_ptr g = (seq == s.index) ? sub_p : stage + (r * 4 + q) * DIM;
+    lds_cdouble_ptr g = (seq == s.index) ? sub_p : stage + (r * pitch + q) * DIM;
     d[0] = g[0]; d[1] = g[1]; d[2] = g[2];
     if (MODEL == kNoncentral) { o[0] = g[3]; o[1] = g[4]; o[2] = g[5]; }
   } else {
@@ -149,9 +149,11 @@ __device__ __forceinline__ void ctrl_point(const CamDev& c, const Subst& s, lds_
 }
 
 // Unproject: exact-fraction weights, direction normalised in fp64. Returns false outside the rectangle.
+// pitch: control points per row of the LDS stage -- 4 for one staged patch; a stage that holds a whole window of the grid
+// (kernels_report.hip: k_direction_image) passes the window's width and `stage` = the evaluation's own patch inside it.
 template <int MODEL, bool LDS>
 __device__ __forceinline__ void unproject_eval(const CamDev& c, const Subst& s, lds_cdouble_ptr stage, lds_cdouble_ptr sub_p, int ix, int iy, double gx, double gy,
-                                               double* dir, double* org) {
+                                               double* dir, double* org, int pitch = 4) {
   double wx[4], wy[4];
   weights_value(gx - (ix - 3), wx);
   weights_value(gy - (iy - 3), wy);
@@ -163,7 +165,7 @@ __device__ __forceinline__ void unproject_eval(const CamDev& c, const Subst& s, 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       double d[3], o[3];
-      ctrl_point<MODEL, LDS>(c, s, stage, sub_p, r, q, rowbase + q, d, o);
+      ctrl_point<MODEL, LDS>(c, s, stage, sub_p, r, q, rowbase + q, d, o, pitch);
       rd[0] += wx[q] * d[0]; rd[1] += wx[q] * d[1]; rd[2] += wx[q] * d[2];
       if (MODEL == kNoncentral) { ro[0] += wx[q] * o[0]; ro[1] += wx[q] * o[1]; ro[2] += wx[q] * o[2]; }
     }

@@ -83,6 +83,8 @@ EXPORTED_SYMBOLS = [
     "cba_model_create", "cba_model_destroy", "cba_model_set_grid", "cba_model_project", "cba_model_unproject",
     "cba_fd_redo_overflow", "cba_debug_fd_redo_counts", "cba_schur_solve_opt", "cba_set_fd_schedule",
     "cba_gridfirst_plan_query", "cba_elimination_order",
+    "cba_model_direction_image", "cba_render_nearest_feature_image", "cba_model_center_point", "cba_model_line_offsets",
+    "cba_debug_time_direction_image",
 ]
 
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
@@ -150,6 +152,13 @@ def load() -> C.CDLL:
     L.cba_model_unproject.argtypes = [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8)]
     L.cba_gridfirst_plan_query.argtypes = [C.POINTER(CbaCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64]
     L.cba_gridfirst_plan_query.restype = C.c_int64
+    u8p = C.POINTER(C.c_uint8)
+    L.cba_model_direction_image.argtypes = [vp, u8p, dp, u8p]
+    L.cba_render_nearest_feature_image.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32,
+                                                   u8p, C.POINTER(C.c_float)]
+    L.cba_model_center_point.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    L.cba_model_line_offsets.argtypes = [vp, dp, dp, u8p, dp]
+    L.cba_debug_time_direction_image.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp]
     _lib = L
     return L
 
@@ -451,6 +460,60 @@ class DeviceModel:
         _check(self.L.cba_model_unproject(self._h, n, _dp(px), _dp(lines), _dp(jac) if jac is not None else None,
                                           ok.ctypes.data_as(C.POINTER(C.c_uint8))), "cba_model_unproject")
         return (lines, jac, ok.astype(bool)) if with_jacobian else (lines, ok.astype(bool))
+
+    # -- calibration report images ---------------------------------------------------------------
+    def direction_image(self, want_directions: bool = False, want_ok: bool = False):
+        """cba_model_direction_image: rgb (H, W, 3) uint8 [, directions (H, W, 3) with NaN where Unproject fails] [, ok (H, W) bool]."""
+        H, W = self.cam.height, self.cam.width
+        rgb = np.zeros((H, W, 3), dtype=np.uint8)
+        dirs = np.zeros((H, W, 3)) if want_directions else None
+        ok = np.zeros((H, W), dtype=np.uint8) if want_ok else None
+        u8p = C.POINTER(C.c_uint8)
+        _check(self.L.cba_model_direction_image(self._h, rgb.ctypes.data_as(u8p), _dp(dirs) if dirs is not None else None,
+                                                ok.ctypes.data_as(u8p) if ok is not None else None), "cba_model_direction_image")
+        out = (rgb,) + ((dirs,) if want_directions else ()) + ((ok.astype(bool),) if want_ok else ())
+        return out if len(out) > 1 else rgb
+
+    def time_direction_image(self, use_stage: bool = True, with_directions: bool = False, launches: int = 20) -> float:
+        """cba_debug_time_direction_image: seconds per launch of k_direction_image (kernel only)."""
+        sec = C.c_double(0)
+        _check(self.L.cba_debug_time_direction_image(self._h, int(use_stage), int(with_directions), int(launches), C.byref(sec)),
+               "cba_debug_time_direction_image")
+        return float(sec.value)
+
+    def center_point(self):
+        """cba_model_center_point (non-central model): (centre (3,), number of lines)."""
+        center = np.zeros(3)
+        n = C.c_int64(0)
+        _check(self.L.cba_model_center_point(self._h, _dp(center), C.byref(n)), "cba_model_center_point")
+        return center, int(n.value)
+
+    def line_offsets(self, center: np.ndarray):
+        """cba_model_line_offsets (non-central model): (offsets (H, W, 3), rgb (H, W, 3) uint8, max_extent)."""
+        H, W = self.cam.height, self.cam.width
+        c = np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+        off = np.zeros((H, W, 3)); rgb = np.zeros((H, W, 3), dtype=np.uint8)
+        ext = C.c_double(0)
+        _check(self.L.cba_model_line_offsets(self._h, _dp(c), _dp(off), rgb.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(ext)),
+               "cba_model_line_offsets")
+        return off, rgb, float(ext.value)
+
+
+def render_nearest_feature_image(width: int, height: int, site_xy_quarter_px: np.ndarray, site_rgb: np.ndarray, device: int = 0,
+                                 want_accum: bool = False):
+    """cba_render_nearest_feature_image: rgb (H, W, 3) uint8 [, the float image (H, W, 3) float32]."""
+    L = load()
+    xy = np.ascontiguousarray(site_xy_quarter_px, dtype=np.int32).reshape(-1, 2)
+    col = np.ascontiguousarray(site_rgb, dtype=np.float32).reshape(-1, 3)
+    assert xy.shape[0] == col.shape[0]
+    rgb = np.zeros((height, width, 3), dtype=np.uint8)
+    acc = np.zeros((height, width, 3), dtype=np.float32) if want_accum else None
+    _check(L.cba_render_nearest_feature_image(int(width), int(height), xy.shape[0], xy.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              col.ctypes.data_as(C.POINTER(C.c_float)), int(device),
+                                              rgb.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              acc.ctypes.data_as(C.POINTER(C.c_float)) if acc is not None else None),
+           "cba_render_nearest_feature_image")
+    return (rgb, acc) if want_accum else rgb
 
 
 # ---- stateless model-level API (CameraModel::Project / Unproject) -----------------------------------

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cmath>
 #include <limits>
+#include <memory>
 
 using namespace vis;
 
@@ -206,6 +207,27 @@ extern "C" int cba_host_reprojection_report(
         for (const PointFeature& f : dataset.GetImageset(i)->FeaturesOfCamera(c)) keep_out[f.id] = 1;
     }
   }
+  return 0;
+}
+
+// vis::ComputeBiasedness / ComputeApproximateFOV / WriteReportInfoFile (calibration_report.h) on one camera from packed arrays;
+// the info file gets the values computed here.
+extern "C" int cba_host_report_info(const cba_camera* cam, const double* grid, int64_t n, const double* errors, const float* features,
+                                    int imageset_count, int num_localized_images, int64_t count, double sum, double max,
+                                    double histogram_extent_in_px, double max_error_in_px, const char* info_path,
+                                    double* biasedness, double* horizontal_fov, double* vertical_fov) {
+  std::unique_ptr<CameraModel> m;
+  if (cam->model_type == CBA_CENTRAL_GENERIC)
+    m.reset(new CentralGenericModel(cam->grid_w, cam->grid_h, cam->calib_min_x, cam->calib_min_y, cam->calib_max_x, cam->calib_max_y, cam->width, cam->height));
+  else
+    m.reset(new NoncentralGenericModel(cam->grid_w, cam->grid_h, cam->calib_min_x, cam->calib_min_y, cam->calib_max_x, cam->calib_max_y, cam->width, cam->height));
+  m->set_abi_grid(grid);
+  std::vector<Vec2d> e; std::vector<Vec2f> f;
+  for (int64_t i = 0; i < n; ++i) { e.emplace_back(errors[2 * i], errors[2 * i + 1]); f.emplace_back(features[2 * i], features[2 * i + 1]); }
+  *biasedness = ComputeBiasedness(m.get(), e, f);
+  ComputeApproximateFOV(m.get(), horizontal_fov, vertical_fov);
+  if (info_path && !WriteReportInfoFile(info_path, m.get(), *horizontal_fov, *vertical_fov, imageset_count, num_localized_images, e,
+                                        (usize)count, sum, max, *biasedness, histogram_extent_in_px, max_error_in_px)) return -1;
   return 0;
 }
 

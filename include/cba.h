@@ -240,6 +240,33 @@ int cba_model_set_grid(cba_model* m, const double* grid);
 int cba_model_project(cba_model* m, int64_t n, const double* local_points, const double* init_pixels, double* pixels, uint8_t* ok);
 int cba_model_unproject(cba_model* m, int64_t n, const double* pixels, double* lines, double* jacobians, uint8_t* ok);
 
+/* ---- calibration report images (APP/calibration_report.cc:713-985; image arrays are row-major [height][width][channel]) ---- */
+/* VisualizeModelDirections over CreateObservationDirectionsImage (APP/calibration_report.cc:1165-1190, APP/util.cc:190-229): every
+ * pixel centre (x + 0.5f, y + 0.5f) of the camera's image is un-projected and coloured `70 * 255.99f / 2.f * (d.x + 1)` (y the
+ * same, z with 270; constant in float, product in double).  The value exceeds 255 by design (iso-bands) and the reference relies on
+ * its x86-64 builds' out-of-range double -> u8 conversion, fixed here as: truncate to a 32-bit integer, keep the low 8 bits.
+ * rgb: 3 width height bytes, (0, 0, 0) where Unproject fails; directions (optional): 3 width height doubles, NaN there; ok
+ * (optional): width height bytes.  One launch instead of width height CameraModel::Unproject calls. */
+int cba_model_direction_image(cba_model* m, uint8_t* rgb, double* directions /* optional */, uint8_t* ok /* optional */);
+/* RenderVoronoiDiagram (APP/calibration_report.cc:354-545; callers VisualizeReprojectionErrorDirections / ...Magnitudes :547-603):
+ * pixel = sum over sites s of area(cell_s n pixel) colour_s, cell_s = the points nearer to s than to any other site.  Sites are the
+ * v_points of CreateVoronoiDiagram (:370-383): integer coordinates in quarter pixels, 0 <= x < 4 width, 0 <= y < 4 height, with one
+ * float colour each (ColorComputer).  accum (optional): the float image, 3 width height; rgb: min(255.99f, max(0, v + 0.5f))
+ * truncated (:542).  Run-to-run identical.  Difference from the reference: outside the convex hull of the sites it closes the open
+ * cells with a 99999-long stand-in for the infinite edges (its comment: image corners "might not always work"); here every pixel
+ * is coloured by its true nearest sites. */
+int cba_render_nearest_feature_image(int32_t width, int32_t height, int64_t n_sites, const int32_t* site_xy_quarter_px,
+                                     const float* site_rgb, int32_t device, uint8_t* rgb, float* accum /* optional */);
+/* The point closest to the lines of all pixels of the calibrated area of a NON-CENTRAL model (APP/calibration_report.cc:839-867,
+ * CenterPointCostFunction :56-80).  The reference runs LMOptimizer (100 iterations) on this linear least-squares problem; returned
+ * here is the least-squares point itself (3 x 3 normal equations summed on the device in a fixed order), which LM converges to.
+ * n_lines (optional): pixels whose Unproject succeeded.  CBA_ERR_ARG for a central model. */
+int cba_model_center_point(cba_model* m, double center[3], int64_t* n_lines);
+/* Offsets of the pixels' lines from `center` (APP/calibration_report.cc:869-926): offset = o + (d . (center - o)) d - center.
+ * offsets (optional): 3 width height doubles, NaN where Unproject fails; max_extent (optional): the largest |component|; rgb
+ * (optional): 127 + 127 offset / max_extent truncated as above, (0, 0, 0) for NaN.  CBA_ERR_ARG for a central model. */
+int cba_model_line_offsets(cba_model* m, const double center[3], double* offsets, uint8_t* rgb, double* max_extent);
+
 /* ---- solver-level entry point ---- */
 /* LMOptimizer::SolveWithSchurComplementDenseOffDiag (LV/lm_optimizer.h:1247-1369) on host arrays in
  * the reference's layout (symmetric parts: upper triangles only are read).  x = [block part; dense]. */
@@ -323,6 +350,11 @@ int cba_debug_apply_update(cba_problem* p, const double* x);
  * error code.  (No reference counterpart: LV/lm_optimizer.h:1247-1369 has one elimination order.) */
 int64_t cba_gridfirst_plan_query(const cba_camera* cameras, int32_t n_cameras, int32_t n_images, int32_t n_points, int32_t strips,
                                  int32_t single_tile_tasks, int32_t what, void* out, int64_t capacity_bytes);
+
+/* Measurement of k_direction_image alone (tools/bench_report.py): seconds per launch over `launches` launches between two events on
+ * device buffers, no copies.  use_stage = 0 sends every tile down the gather path (the control points read through L1 / L2 instead
+ * of the tile's window staged in LDS); with_directions = 0 leaves the fp64 direction output out.  (No reference counterpart.) */
+int cba_debug_time_direction_image(cba_model* m, int32_t use_stage, int32_t with_directions, int32_t launches, double* seconds);
 
 /* Elimination order the problem uses (cba_solver_options.elimination resolved): 1 = pose-first, 2 = grid-first; out[0..3] (optional,
  * may be NULL) = strips of camera 0, rows of the border system that is factored densely, rows of the grid part, pivot chains. */

@@ -1,0 +1,152 @@
+// Entry points of the C ABI (include/cba.h) behind the comparison of two central-generic calibrations (APP/fitting_report.h:55-203):
+// cba_model_compare and cba_model_direction_moments.  Kernels: kernels_compare.hip.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "cba_internal.h"
+#include "cba_model.h"
+
+using namespace cba;
+
+namespace {
+
+constexpr int kDefaultStragglerThreshold = 8;
+
+// the device arrays of one comparison
+struct CompareBuffers {
+  DevBuf<double> base_dir, fit_dir, err, reproj, partials, sums;
+  DevBuf<uint8_t> flags;
+  DevBuf<int> list, count;
+  int alloc(size_t n) {
+    CBA_TRY(base_dir.alloc(3 * n)); CBA_TRY(fit_dir.alloc(3 * n)); CBA_TRY(err.alloc(3 * n)); CBA_TRY(reproj.alloc(2 * n));
+    CBA_TRY(flags.alloc(n)); CBA_TRY(list.alloc(n)); CBA_TRY(count.alloc(1));
+    CBA_TRY(partials.alloc((size_t)compare_partials_doubles())); CBA_TRY(sums.alloc(kCompareSums));
+    return CBA_OK;
+  }
+};
+
+int check_pair(const cba_model* base, const cba_model* fitted, int border_x, int border_y, const char* who) {
+  const std::string w(who);
+  if (!base || !fitted) { set_error(w + ": bad argument"); return CBA_ERR_ARG; }
+  if (base->cam.model_type != CBA_CENTRAL_GENERIC || fitted->cam.model_type != CBA_CENTRAL_GENERIC) {
+    set_error(w + ": needs two central-generic models"); return CBA_ERR_ARG;
+  }
+  if (base->device != fitted->device) { set_error(w + ": the models are on different devices"); return CBA_ERR_ARG; }
+  const int W = fitted->cam.width, H = fitted->cam.height;
+  if (W < 1 || H < 1 || (int64_t)W * H > (int64_t)1 << 28) { set_error(w + ": bad image size"); return CBA_ERR_ARG; }
+  if ((int64_t)base->cam.width - 2 * (int64_t)border_x != W || (int64_t)base->cam.height - 2 * (int64_t)border_y != H) {
+    set_error(w + ": base size minus twice the border differs from the fitted size"); return CBA_ERR_ARG;      // CHECK_EQ :65-66
+  }
+  return CBA_OK;
+}
+
+CompareArgs make_args(const cba_model* base, const cba_model* fitted, const double* R, int border_x, int border_y, const CompareBuffers& b) {
+  CompareArgs a{};
+  a.base = base->d_cam; a.fitted = fitted->d_cam;
+  for (int k = 0; k < 9; ++k) a.R[k] = R[k];
+  a.border_x = border_x; a.border_y = border_y; a.W = fitted->cam.width; a.H = fitted->cam.height;
+  a.base_dir = b.base_dir; a.fit_dir = b.fit_dir; a.err = b.err; a.reproj = b.reproj; a.flags = b.flags;
+  a.list = b.list; a.list_count = b.count;
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cba_model_compare(cba_model* base, cba_model* fitted, const cba_compare_options* options, const cba_compare_outputs* outputs,
+                      cba_compare_stats* stats) {
+  if (!options || (!outputs && !stats)) { set_error("cba_model_compare: bad argument"); return CBA_ERR_ARG; }
+  CBA_TRY(check_pair(base, fitted, options->border_x, options->border_y, "cba_model_compare"));
+  if (options->initial_estimate != 0 && options->initial_estimate != 1) { set_error("cba_model_compare: unknown initial_estimate"); return CBA_ERR_ARG; }
+  const cba_compare_outputs none{};
+  const cba_compare_outputs& o = outputs ? *outputs : none;
+  CBA_HIP(hipSetDevice(fitted->device));
+  const int W = fitted->cam.width, H = fitted->cam.height;
+  const size_t n = (size_t)W * H;
+  CompareBuffers b;
+  CBA_TRY(b.alloc(n));
+  CompareArgs a = make_args(base, fitted, options->rotation, options->border_x, options->border_y, b);
+  a.init_mode = options->initial_estimate;
+  const int thr = options->straggler_threshold;
+  a.max_outer = thr == 0 ? kDefaultStragglerThreshold : (thr < 0 ? 0 : std::min(thr, 100));
+  a.do_project = 1;
+  CBA_HIP(hipMemsetAsync(b.count, 0, sizeof(int), nullptr));
+  CBA_TRY(launch_compare_pass(a, nullptr));
+  int n_list = 0;
+  CBA_HIP(hipMemcpy(&n_list, b.count, sizeof(int), hipMemcpyDeviceToHost));
+  if (n_list < 0 || (size_t)n_list > n) { set_error("cba_model_compare: pixel list corrupt"); return CBA_ERR_HIP; }
+  CBA_TRY(launch_compare_second(a, n_list, nullptr));
+  CBA_TRY(launch_compare_reduce((int64_t)n, b.flags, b.err, b.reproj, b.fit_dir, b.base_dir, false, b.partials, b.sums, nullptr));
+  double h[kCompareSums];
+  CBA_HIP(hipMemcpy(h, b.sums, sizeof(h), hipMemcpyDeviceToHost));
+
+  const bool want_images = o.error_magnitudes || o.error_direction_angles || o.error_directions || o.reprojection_magnitudes || o.reprojections;
+  DevBuf<uint8_t> img;
+  if (want_images) {
+    CBA_TRY(img.alloc(11 * n));
+    CompareColorArgs c{};
+    c.n = (int64_t)n; c.flags = b.flags; c.base_dir = b.base_dir; c.fit_dir = b.fit_dir; c.err = b.err; c.reproj = b.reproj;
+    c.max_error_component = options->max_visualization_extent >= 0 ? options->max_visualization_extent : h[kCmpMaxComponent];              // :128-130
+    c.max_error_norm = h[kCmpMaxNorm];
+    c.reprojection_error_max = options->max_visualization_extent_pixels >= 0 ? options->max_visualization_extent_pixels : h[kCmpReprojMax];   // :131-133
+    c.max_visualization_extent_pixels = options->max_visualization_extent_pixels;
+    uint8_t* p = img;
+    c.img_magnitudes = p; c.img_angles = p + n; c.img_directions = p + 4 * n; c.img_reproj_magnitudes = p + 7 * n; c.img_reprojections = p + 8 * n;
+    CBA_TRY(launch_compare_colors(c, nullptr));
+    if (o.error_magnitudes) CBA_HIP(hipMemcpy(o.error_magnitudes, c.img_magnitudes, n, hipMemcpyDeviceToHost));
+    if (o.error_direction_angles) CBA_HIP(hipMemcpy(o.error_direction_angles, c.img_angles, 3 * n, hipMemcpyDeviceToHost));
+    if (o.error_directions) CBA_HIP(hipMemcpy(o.error_directions, c.img_directions, 3 * n, hipMemcpyDeviceToHost));
+    if (o.reprojection_magnitudes) CBA_HIP(hipMemcpy(o.reprojection_magnitudes, c.img_reproj_magnitudes, n, hipMemcpyDeviceToHost));
+    if (o.reprojections) CBA_HIP(hipMemcpy(o.reprojections, c.img_reprojections, 3 * n, hipMemcpyDeviceToHost));
+  }
+  if (o.base_directions) CBA_HIP(hipMemcpy(o.base_directions, b.base_dir, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  if (o.fitted_directions) CBA_HIP(hipMemcpy(o.fitted_directions, b.fit_dir, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  if (o.errors) CBA_HIP(hipMemcpy(o.errors, b.err, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  if (o.reprojection_errors) CBA_HIP(hipMemcpy(o.reprojection_errors, b.reproj, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
+  if (o.flags) CBA_HIP(hipMemcpy(o.flags, b.flags, n, hipMemcpyDeviceToHost));
+  if (stats) {
+    stats->n_base_ok = (int64_t)h[kCmpBaseOk]; stats->n_both_ok = (int64_t)h[kCmpBothOk]; stats->n_projected = (int64_t)h[kCmpProjected];
+    stats->n_second_launch = n_list;
+    stats->max_error_component = h[kCmpMaxComponent]; stats->max_error_norm = h[kCmpMaxNorm];
+    stats->reprojection_error_sum = h[kCmpReprojSum]; stats->reprojection_error_max = h[kCmpReprojMax];
+    stats->reprojection_error_median = 0; stats->has_median = 0;
+    if (stats->n_projected > 0) {             // std::sort, element size / 2 (:193-194)
+      std::vector<double> r(2 * n); std::vector<uint8_t> fl(n);
+      CBA_HIP(hipMemcpy(r.data(), b.reproj, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
+      CBA_HIP(hipMemcpy(fl.data(), b.flags, n, hipMemcpyDeviceToHost));
+      std::vector<double> mags;
+      mags.reserve((size_t)stats->n_projected);
+      for (size_t i = 0; i < n; ++i)
+        if (fl[i] & 4) mags.push_back(std::sqrt(r[2 * i] * r[2 * i] + r[2 * i + 1] * r[2 * i + 1]));
+      if (!mags.empty()) {
+        std::nth_element(mags.begin(), mags.begin() + mags.size() / 2, mags.end());
+        stats->reprojection_error_median = mags[mags.size() / 2]; stats->has_median = 1;
+      }
+    }
+  }
+  return CBA_OK;
+}
+
+int cba_model_direction_moments(cba_model* base, cba_model* fitted, int32_t border_x, int32_t border_y, double M[9], int64_t* n_out) {
+  if (!M) { set_error("cba_model_direction_moments: bad argument"); return CBA_ERR_ARG; }
+  CBA_TRY(check_pair(base, fitted, border_x, border_y, "cba_model_direction_moments"));
+  CBA_HIP(hipSetDevice(fitted->device));
+  const size_t n = (size_t)fitted->cam.width * fitted->cam.height;
+  CompareBuffers b;
+  CBA_TRY(b.alloc(n));
+  const double identity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};      // 1 * a + 0 * b + 0 * c is a: base_dir holds the unrotated directions
+  CompareArgs a = make_args(base, fitted, identity, border_x, border_y, b);
+  a.max_outer = 100; a.do_project = 0;
+  CBA_HIP(hipMemsetAsync(b.count, 0, sizeof(int), nullptr));
+  CBA_TRY(launch_compare_pass(a, nullptr));
+  CBA_TRY(launch_compare_reduce((int64_t)n, b.flags, b.err, b.reproj, b.fit_dir, b.base_dir, true, b.partials, b.sums, nullptr));
+  double h[kCompareSums];
+  CBA_HIP(hipMemcpy(h, b.sums, sizeof(h), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 9; ++k) M[k] = h[kCmpMoments + k];
+  if (n_out) *n_out = (int64_t)h[kCmpBothOk];
+  return CBA_OK;
+}
+
+}  // extern "C"

@@ -268,6 +268,39 @@ int line_offset_blocks(int W, int H);
 int launch_line_offsets(const CamDev* cam_dev, int W, int H, const double* center, double* offsets, double* block_max, hipStream_t s);
 int launch_line_offset_colors(const double* offsets, int W, int H, double max_extent, uint8_t* rgb, hipStream_t s);
 
+// ---- kernels_compare.hip (comparison of two central-generic calibrations, APP/fitting_report.h:55-203) ----
+// Per-pixel arrays of the fitted model's W x H image: base_dir / fit_dir / err 3 doubles, reproj 2 doubles, flags one byte (bit 0 base
+// un-projection ok, bit 1 fitted un-projection ok, bit 2 projected); list: W * H ints, *list_count zeroed by the caller.
+struct CompareArgs {
+  const CamDev* base; const CamDev* fitted;
+  double R[9];                 // row-major rotation applied to the base model's directions
+  int border_x, border_y, W, H;
+  int init_mode;               // 0 = centre of the fitted model's calibrated area, 1 = the pixel itself clamped into it
+  int max_outer;               // outer iterations of the first launch (100 = complete, 0 = every projection is listed)
+  int do_project;              // 0: un-projections only (direction moments)
+  double* base_dir; double* fit_dir; double* err; double* reproj; uint8_t* flags;
+  int* list; int* list_count;
+};
+static_assert(std::is_trivially_copyable_v<CompareArgs>);
+int launch_compare_pass(const CompareArgs& a, hipStream_t s);
+int launch_compare_second(const CompareArgs& a, int n_list, hipStream_t s);
+// slots of the reduction
+constexpr int kCmpBaseOk = 0, kCmpBothOk = 1, kCmpProjected = 2, kCmpMaxComponent = 3, kCmpMaxNorm = 4, kCmpReprojSum = 5, kCmpReprojMax = 6,
+              kCmpMoments = 7, kCompareSums = 16;
+int compare_partials_doubles();
+// moment_dir: the base model's directions before the rotation (read with want_moments only); out: kCompareSums doubles
+int launch_compare_reduce(int64_t n, const uint8_t* flags, const double* err, const double* reproj, const double* fit_dir,
+                          const double* moment_dir, bool want_moments, double* partials, double* out, hipStream_t s);
+struct CompareColorArgs {
+  int64_t n;
+  const uint8_t* flags; const double* base_dir; const double* fit_dir; const double* err; const double* reproj;
+  double max_error_component, max_error_norm, reprojection_error_max;      // after the overrides of :128-133
+  double max_visualization_extent_pixels;
+  uint8_t* img_magnitudes; uint8_t* img_angles; uint8_t* img_directions; uint8_t* img_reproj_magnitudes; uint8_t* img_reprojections;   // each may be null
+};
+static_assert(std::is_trivially_copyable_v<CompareColorArgs>);
+int launch_compare_colors(const CompareColorArgs& c, hipStream_t s);
+
 // ---- kernels_linalg.hip (Schur stage, the fp64 MFMA GEMM, pack / diagonal kernels) ----
 // Inverse of the (bs x bs) diagonal blocks with lambda added, and Dinv*b.
 int launch_block_inverse(const double* Dblk, const double* bblk, double lambda, int bs, int nb, double* Dinv,

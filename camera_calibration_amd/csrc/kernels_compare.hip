@@ -1,0 +1,266 @@
+// Kernels of the comparison of two central-generic calibrations (APP/fitting_report.h:55-203, CreateFittingErrorReport<CentralGenericModel,
+// CentralGenericModel>, called by APP/tools/compare_calibrations.cc:39-74): the per-pixel loop (:83-125), its reductions and the
+// five images (:135-178).
+//
+//  k_compare_pass     one lane per pixel (x, y) of the fitted model's image, 8 x 8 pixels per wavefront (neighbouring pixels share
+//                     control patches and take similar iteration counts): a = Unproject_A(border + (x, y) + 0.5f), g = R a,
+//                     f = Unproject_B((x, y) + 0.5f), error = f - g, Project_B(g) from the start pixel, reprojection error =
+//                     (x + 0.5f, y + 0.5f) - pixel.  A projection that reaches the iteration cap writes nothing; its pixel index goes
+//                     to a device list (ballot, one atomic per wavefront; one slot per pixel: the list cannot overflow).
+//  k_compare_second   the complete projection (100 outer iterations) of the listed pixels, packed into full wavefronts, from the same
+//                     start and from the g the first launch stored.
+//  k_compare_reduce   counts, maxima, the sum of the reprojection magnitudes and (want_moments) M = sum f a^T: a fixed assignment of
+//  (+ final)          pixels to lanes and fixed trees (as k_center_point_sums): run-to-run identical.
+//  k_compare_colors   the five images from the per-pixel arrays and the maxima.
+//
+// Both launches project through ONE non-inlined device function (compare_project): they execute the same machine code, so a pixel's
+// result does not depend on which launch finished it (cba_internal.h records what two inlined copies of the LM loop can do to one
+// contraction).  The spline and LM arithmetic is model.hip.h's, unchanged; the control points are gathered (no LDS stage).
+//
+// Per-pixel arrays: flags bit 0 = base un-projection ok, bit 1 = fitted un-projection ok, bit 2 = projected.  base_dir = g (NaN
+// without bit 0), fit_dir = f (NaN without bit 1), error = f - g with both bits, +inf with bit 0 only (:100), NaN without bit 0 (:90);
+// reprojection error = 0 without bit 2 (:85).
+//
+// DEFINED WHERE THE REFERENCE IS NOT (include/cba.h repeats this):
+//  * bit 0 without bit 1: the reference reads an uninitialised fitted_direction for the angle image and converts 255.99f * inf to
+//    u8.  Here: angle image (0, 0, 0), direction image the clamped relative error (255 per channel), magnitude image 255.
+//  * a maximum of zero (identical models, nothing projected): the reference divides by zero.  Here the relative error / magnitude
+//    ratio is 0: direction bytes 127, magnitude bytes 0.
+//  * without bit 0 the pixel has zero reprojection error and takes part in the reprojection-magnitude image with 0, as in the
+//    reference.
+#include "cba_internal.h"
+
+namespace cba {
+
+constexpr int kCmpTileW = 32, kCmpTileH = 8;      // a workgroup: four 8 x 8 wavefront tiles side by side
+
+// start pixel of the projection into B: 0 = centre of B's calibrated area (the reference), 1 = the pixel itself, clamped into the
+// area as projection_candidate clamps its iterates
+__device__ __forceinline__ void compare_start(const CamDev& cb, int mode, int x, int y, double& px, double& py) {
+  if (mode == 1) {
+    px = fmax((double)cb.min_x, fmin((double)((float)x + 0.5f), cb.max_x + 0.999));
+    py = fmax((double)cb.min_y, fmin((double)((float)y + 0.5f), cb.max_y + 0.999));
+  } else {
+    center_pixel(cb, px, py);
+  }
+}
+
+struct CompareProjection { double px, py; int ok, capped; };
+// CameraModel::ProjectWithInitialEstimate on the fitted model; NOT inlined: see the header comment
+__device__ __noinline__ CompareProjection compare_project(const CamDev* __restrict__ fitted, double gx, double gy, double gz, double px,
+                                                          double py, int max_outer) {
+  const CamDev cb = *fitted;
+  Subst none; none.index = -1;
+  const double g[3] = {gx, gy, gz};
+  bool capped = false;
+  CompareProjection r;
+  r.px = px; r.py = py;
+  r.ok = project_point<kCentral>(cb, none, g, r.px, r.py, nullptr, nullptr, max_outer, &capped) ? 1 : 0;
+  r.capped = capped ? 1 : 0;
+  return r;
+}
+
+__global__ void __launch_bounds__(256) k_compare_pass(CompareArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int x = blockIdx.x * kCmpTileW + wave * 8 + (lane & 7), y = blockIdx.y * kCmpTileH + (lane >> 3);
+  const bool inside = x < a.W && y < a.H;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll), inf = __longlong_as_double(0x7ff0000000000000ll);
+  Subst none; none.index = -1;
+  bool capped = false;
+  if (inside) {
+    const size_t p = (size_t)y * a.W + x;
+    double av[3], f[3], o[3], g[3] = {nan, nan, nan}, e[3] = {nan, nan, nan};
+    const CamDev ca = *a.base;
+    const bool base_ok = unproject<kCentral>(ca, none, (double)((float)(a.border_x + x) + 0.5f), (double)((float)(a.border_y + y) + 0.5f), av, o);
+    const CamDev cb = *a.fitted;
+    const bool fit_ok = unproject<kCentral>(cb, none, (double)((float)x + 0.5f), (double)((float)y + 0.5f), f, o);
+    if (!fit_ok) f[0] = f[1] = f[2] = nan;
+    if (base_ok) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        g[r] = a.R[3 * r] * av[0] + a.R[3 * r + 1] * av[1] + a.R[3 * r + 2] * av[2];
+        e[r] = fit_ok ? f[r] - g[r] : inf;
+      }
+    }
+    int fl = (base_ok ? 1 : 0) | (fit_ok ? 2 : 0);
+    double rx = 0, ry = 0;
+    if (base_ok && a.do_project) {
+      double px, py;
+      compare_start(cb, a.init_mode, x, y, px, py);
+      const CompareProjection pr = compare_project(a.fitted, g[0], g[1], g[2], px, py, a.max_outer);
+      capped = pr.capped != 0;
+      if (pr.ok) {
+        fl |= 4;
+        rx = (double)((float)x + 0.5f) - pr.px; ry = (double)((float)y + 0.5f) - pr.py;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { a.base_dir[3 * p + k] = g[k]; a.fit_dir[3 * p + k] = f[k]; a.err[3 * p + k] = e[k]; }
+    a.reproj[2 * p] = rx; a.reproj[2 * p + 1] = ry;
+    a.flags[p] = (uint8_t)fl;
+  }
+  const unsigned long long m = __ballot(capped);
+  if (m) {
+    const int leader = __ffsll((long long)m) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(a.list_count, __popcll(m));
+    base = __shfl(base, leader);
+    if (capped) a.list[base + __popcll(m & ((1ull << lane) - 1))] = y * a.W + x;
+  }
+}
+
+__global__ void __launch_bounds__(64) k_compare_second(CompareArgs a, int n_list) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n_list) return;
+  const int p = a.list[i];
+  const int x = p % a.W, y = p / a.W;
+  const CamDev cb = *a.fitted;
+  double px, py;
+  compare_start(cb, a.init_mode, x, y, px, py);
+  const CompareProjection pr = compare_project(a.fitted, a.base_dir[3 * (size_t)p], a.base_dir[3 * (size_t)p + 1], a.base_dir[3 * (size_t)p + 2],
+                                               px, py, 100);
+  if (pr.ok) {
+    a.reproj[2 * (size_t)p] = (double)((float)x + 0.5f) - pr.px; a.reproj[2 * (size_t)p + 1] = (double)((float)y + 0.5f) - pr.py;
+    a.flags[p] = a.flags[p] | 4;
+  }
+}
+
+int launch_compare_pass(const CompareArgs& a, hipStream_t s) {
+  dim3 grid((unsigned)((a.W + kCmpTileW - 1) / kCmpTileW), (unsigned)((a.H + kCmpTileH - 1) / kCmpTileH)), block(256);
+  hipLaunchKernelGGL(k_compare_pass, grid, block, 0, s, a);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+int launch_compare_second(const CompareArgs& a, int n_list, hipStream_t s) {
+  if (n_list == 0) return CBA_OK;
+  hipLaunchKernelGGL(k_compare_second, dim3((unsigned)((n_list + 63) / 64)), dim3(64), 0, s, a, n_list);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// reductions: slot k of kCompareSums is a sum, or a maximum for k in {kCmpMaxComponent, kCmpMaxNorm, kCmpReprojMax}
+// ------------------------------------------------------------------------------------------------
+constexpr int kCmpBlocks = 256;
+__device__ __forceinline__ double compare_combine(int k, double u, double v) {
+  return (k == kCmpMaxComponent || k == kCmpMaxNorm || k == kCmpReprojMax) ? fmax(u, v) : u + v;
+}
+// moment_dir: A's directions BEFORE the rotation (the caller's base_dir of a pass with the identity rotation)
+__global__ void __launch_bounds__(256) k_compare_reduce(int64_t n, const uint8_t* __restrict__ flags, const double* __restrict__ err,
+                                                        const double* __restrict__ reproj, const double* __restrict__ fit_dir,
+                                                        const double* __restrict__ moment_dir, int want_moments,
+                                                        double* __restrict__ partials) {
+  double acc[kCompareSums];
+#pragma unroll
+  for (int k = 0; k < kCompareSums; ++k) acc[k] = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)kCmpBlocks * 256) {
+    const int fl = flags[i];
+    if (fl & 1) acc[kCmpBaseOk] += 1;
+    if ((fl & 3) == 3) {
+      acc[kCmpBothOk] += 1;
+      const double ex = err[3 * i], ey = err[3 * i + 1], ez = err[3 * i + 2];
+      acc[kCmpMaxComponent] = fmax(acc[kCmpMaxComponent], fmax(fmax(fabs(ex), fabs(ey)), fabs(ez)));
+      acc[kCmpMaxNorm] = fmax(acc[kCmpMaxNorm], sqrt(ex * ex + ey * ey + ez * ez));
+      if (want_moments) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) acc[kCmpMoments + 3 * r + q] += fit_dir[3 * i + r] * moment_dir[3 * i + q];
+      }
+    }
+    if (fl & 4) {
+      const double rx = reproj[2 * i], ry = reproj[2 * i + 1], mag = sqrt(rx * rx + ry * ry);
+      acc[kCmpProjected] += 1;
+      acc[kCmpReprojSum] += mag;
+      acc[kCmpReprojMax] = fmax(acc[kCmpReprojMax], mag);
+    }
+  }
+  __shared__ double sh[kCompareSums][256];
+#pragma unroll
+  for (int k = 0; k < kCompareSums; ++k) sh[k][threadIdx.x] = acc[k];
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s)
+#pragma unroll
+      for (int k = 0; k < kCompareSums; ++k) sh[k][threadIdx.x] = compare_combine(k, sh[k][threadIdx.x], sh[k][threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x < kCompareSums) partials[blockIdx.x * kCompareSums + threadIdx.x] = sh[threadIdx.x][0];
+}
+__global__ void k_compare_reduce_final(const double* __restrict__ partials, double* __restrict__ out) {
+  const int k = threadIdx.x;
+  if (k >= kCompareSums) return;
+  double s = 0;
+  for (int b = 0; b < kCmpBlocks; ++b) s = compare_combine(k, s, partials[b * kCompareSums + k]);
+  out[k] = s;
+}
+int compare_partials_doubles() { return kCmpBlocks * kCompareSums; }
+int launch_compare_reduce(int64_t n, const uint8_t* flags, const double* err, const double* reproj, const double* fit_dir,
+                          const double* moment_dir, bool want_moments, double* partials, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_compare_reduce, dim3(kCmpBlocks), dim3(256), 0, s, n, flags, err, reproj, fit_dir, moment_dir, want_moments ? 1 : 0,
+                     partials);
+  hipLaunchKernelGGL(k_compare_reduce_final, dim3(1), dim3(64), 0, s, partials, out);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the five images (:135-178), every expression in the reference's types
+// ------------------------------------------------------------------------------------------------
+// double -> int of the reference's x86-64 builds: truncated; what no 32-bit integer holds (NaN included) is INT_MIN
+__device__ __forceinline__ int compare_trunc_i32(double v) { return fabs(v) < 2147483648.0 ? (int)v : (int)0x80000000; }
+__device__ __forceinline__ uint8_t compare_u8(double v) { return (uint8_t)(uint32_t)compare_trunc_i32(v); }
+
+__global__ void __launch_bounds__(256) k_compare_colors(CompareColorArgs c) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= c.n) return;
+  const int fl = c.flags[p];
+  uint8_t ang[3] = {0, 0, 0}, dir[3] = {0, 0, 0}, mag = 0;
+  if (fl & 1) {                                          // !error.hasNaN()
+    const double e[3] = {c.err[3 * p], c.err[3 * p + 1], c.err[3 * p + 2]};
+    const bool both = (fl & 2) != 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      // (error / max_error_component).cwiseMax(-1).cwiseMin(1); zero maximum: 0; error = +inf: 1
+      const double rel = !both ? 1.0 : (c.max_error_component > 0 ? fmin(1.0, fmax(-1.0, e[k] / c.max_error_component)) : 0.0);
+      dir[k] = compare_u8((double)(255.99f / 2) * (rel + (double)1.f));                              // :159-160
+    }
+    if (both) {
+      const double* g = c.base_dir + 3 * p; const double* f = c.fit_dir + 3 * p;
+      const double scale = 127 / (3.14159265358979323846 / (double)180.f * 0.025);                  // int / (double / float * double)
+      ang[0] = (uint8_t)min(255, max(0, compare_trunc_i32(127 + scale * (atan2(g[2], g[0]) - atan2(f[2], f[0])) + 0.5)));       // :155
+      ang[1] = (uint8_t)min(255, max(0, compare_trunc_i32(127 + scale * (atan2(g[1], g[2]) - atan2(f[1], f[2])) + 0.5)));       // :156
+      ang[2] = 127;
+      const double norm = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+      mag = c.max_error_norm > 0 ? compare_u8((double)255.99f * (norm / c.max_error_norm)) : (uint8_t)0;                         // :161
+    } else {
+      mag = 255;
+    }
+  }
+  const double rx = c.reproj[2 * p], ry = c.reproj[2 * p + 1];
+  const double rmag = sqrt(rx * rx + ry * ry);
+  // std::max<float>(0.f, std::min<float>(255.f, 255.99f * magnitude / max)): the double is rounded to float first (:166)
+  uint8_t rmag_u8 = 0;
+  if (c.reprojection_error_max > 0) rmag_u8 = (uint8_t)fmaxf(0.f, fminf(255.f, (float)((double)255.99f * rmag / c.reprojection_error_max)));
+  // std::max(0., std::min(1., magnitude / extent)) with std::min / std::max's own comparisons (:168)
+  const double q = rmag / c.max_visualization_extent_pixels;
+  const double smin = (q < 1.) ? q : 1.;
+  const double strength = (0. < smin) ? smin : 0.;
+  const double d = atan2(-ry, -rx);                                                                  // :171
+  const float col0 = (float)(127 + strength * 127 * sin(d)), col1 = (float)(127 + strength * 127 * cos(d));      // Vec3f
+  if (c.img_magnitudes) c.img_magnitudes[p] = mag;
+  if (c.img_angles) { c.img_angles[3 * p] = ang[0]; c.img_angles[3 * p + 1] = ang[1]; c.img_angles[3 * p + 2] = ang[2]; }
+  if (c.img_directions) { c.img_directions[3 * p] = dir[0]; c.img_directions[3 * p + 1] = dir[1]; c.img_directions[3 * p + 2] = dir[2]; }
+  if (c.img_reproj_magnitudes) c.img_reproj_magnitudes[p] = rmag_u8;
+  if (c.img_reprojections) {
+    c.img_reprojections[3 * p] = (uint8_t)(col0 + 0.5f); c.img_reprojections[3 * p + 1] = (uint8_t)(col1 + 0.5f);      // :176
+    c.img_reprojections[3 * p + 2] = (uint8_t)(127.f + 0.5f);
+  }
+}
+int launch_compare_colors(const CompareColorArgs& c, hipStream_t s) {
+  hipLaunchKernelGGL(k_compare_colors, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, s, c);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+
+}  // namespace cba

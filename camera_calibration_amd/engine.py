@@ -65,6 +65,32 @@ class CbaFitReport(C.Structure):
                 ("iterations_performed", C.c_int32), ("lm_attempts", C.c_int32), ("t_pass", C.c_double), ("t_solve", C.c_double)]
 
 
+class CbaCompareOptions(C.Structure):
+    _fields_ = [("rotation", C.c_double * 9), ("border_x", C.c_int32), ("border_y", C.c_int32),
+                ("max_visualization_extent", C.c_double), ("max_visualization_extent_pixels", C.c_double),
+                ("initial_estimate", C.c_int32), ("straggler_threshold", C.c_int32)]
+
+
+COMPARE_ARRAYS = (("base_directions", 3, np.float64), ("fitted_directions", 3, np.float64), ("errors", 3, np.float64),
+                  ("reprojection_errors", 2, np.float64), ("flags", 0, np.uint8))
+COMPARE_IMAGES = (("error_magnitudes", 0), ("error_direction_angles", 3), ("error_directions", 3), ("reprojection_magnitudes", 0),
+                  ("reprojections", 3))
+
+
+class CbaCompareOutputs(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _ in COMPARE_ARRAYS] + [(name, C.c_void_p) for name, _ in COMPARE_IMAGES]
+
+
+class CbaCompareStats(C.Structure):
+    _fields_ = [("n_base_ok", C.c_int64), ("n_both_ok", C.c_int64), ("n_projected", C.c_int64), ("n_second_launch", C.c_int64),
+                ("max_error_component", C.c_double), ("max_error_norm", C.c_double),
+                ("reprojection_error_sum", C.c_double), ("reprojection_error_max", C.c_double),
+                ("reprojection_error_median", C.c_double), ("has_median", C.c_int32)]
+
+
+INITIAL_ESTIMATE_CENTER, INITIAL_ESTIMATE_PIXEL = 0, 1
+
+
 class CbaReport(C.Structure):
     _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("lambda_", C.c_double),
                 ("accepted", C.c_int32), ("lm_attempts", C.c_int32),
@@ -85,6 +111,7 @@ EXPORTED_SYMBOLS = [
     "cba_gridfirst_plan_query", "cba_elimination_order",
     "cba_model_direction_image", "cba_render_nearest_feature_image", "cba_model_center_point", "cba_model_line_offsets",
     "cba_debug_time_direction_image",
+    "cba_model_compare", "cba_model_direction_moments",
 ]
 
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
@@ -497,6 +524,46 @@ class DeviceModel:
         _check(self.L.cba_model_line_offsets(self._h, _dp(c), _dp(off), rgb.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(ext)),
                "cba_model_line_offsets")
         return off, rgb, float(ext.value)
+
+    # -- comparison of two calibrations ------------------------------------------------------------
+    def compare(self, fitted: "DeviceModel", rotation: Optional[np.ndarray] = None, border=(0, 0), max_visualization_extent: float = -1.0,
+                max_visualization_extent_pixels: float = -1.0, initial_estimate: int = INITIAL_ESTIMATE_CENTER,
+                straggler_threshold: int = 0, want_arrays: bool = True, want_images: bool = True) -> dict:
+        """cba_model_compare with this model as the base: the per-pixel arrays ((H, W[, k]) of the fitted model's image), the five
+        images and the statistics, in one dict.  reprojection_error_median is None when nothing projected."""
+        H, W = fitted.cam.height, fitted.cam.width
+        o = CbaCompareOptions()
+        o.rotation[:] = list(np.asarray(np.eye(3) if rotation is None else rotation, dtype=np.float64).reshape(9))
+        o.border_x, o.border_y = int(border[0]), int(border[1])
+        o.max_visualization_extent, o.max_visualization_extent_pixels = float(max_visualization_extent), float(max_visualization_extent_pixels)
+        o.initial_estimate, o.straggler_threshold = int(initial_estimate), int(straggler_threshold)
+        out, res = CbaCompareOutputs(), {}
+        if want_arrays:
+            for name, k, dt in COMPARE_ARRAYS:
+                res[name] = np.zeros((H, W, k) if k else (H, W), dtype=dt)
+                setattr(out, name, res[name].ctypes.data)
+        if want_images:
+            for name, k in COMPARE_IMAGES:
+                res[name] = np.zeros((H, W, k) if k else (H, W), dtype=np.uint8)
+                setattr(out, name, res[name].ctypes.data)
+        st = CbaCompareStats()
+        self.L.cba_model_compare.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CbaCompareOptions), C.POINTER(CbaCompareOutputs),
+                                             C.POINTER(CbaCompareStats)]
+        _check(self.L.cba_model_compare(self._h, fitted._h, C.byref(o), C.byref(out), C.byref(st)), "cba_model_compare")
+        for name, _ in CbaCompareStats._fields_:
+            res[name] = getattr(st, name)
+        res["reprojection_error_median"] = st.reprojection_error_median if st.has_median else None
+        del res["has_median"]
+        return res
+
+    def direction_moments(self, fitted: "DeviceModel", border=(0, 0)):
+        """cba_model_direction_moments with this model as the base: (M (3, 3) = sum f a^T, number of pixels summed)."""
+        M = np.zeros((3, 3))
+        n = C.c_int64(0)
+        self.L.cba_model_direction_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        _check(self.L.cba_model_direction_moments(self._h, fitted._h, int(border[0]), int(border[1]), _dp(M), C.byref(n)),
+               "cba_model_direction_moments")
+        return M, int(n.value)
 
 
 def render_nearest_feature_image(width: int, height: int, site_xy_quarter_px: np.ndarray, site_rgb: np.ndarray, device: int = 0,

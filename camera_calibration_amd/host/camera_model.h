@@ -58,6 +58,8 @@ class CameraModel {
   /// use and refreshed when the grid may have changed (any non-const grid access marks it stale), so a caller that
   /// projects feature by feature (APP/calibration_report.cc:101-148) pays one small kernel launch per call.
   void grid_changed() const { m_dev_stale = true; }
+  /// That device-resident copy, current, for entry points that take models (cba_model_compare); null on failure.  Owned by the object.
+  cba_model* abi_device_model(int device_ordinal) const { return device_model(device_ordinal); }
  protected:
   cba_model* device_model(int device_ordinal) const;   // joint_optimization_hip.cc
   void release_device_model() const;

@@ -6,7 +6,9 @@
 #include "calibration_io.h"
 #include "calibration_fit.h"
 #include "calibration.h"
+#include "fitting_report.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <limits>
@@ -231,6 +233,32 @@ extern "C" int cba_host_report_info(const cba_camera* cam, const double* grid, i
   return 0;
 }
 
+// vis::CreateFittingErrorReport (fitting_report.h) on two central-generic models from packed arrays; images (optional): the five
+// arrays in the order of FittingErrorImages, 11 W H bytes.
+extern "C" int cba_host_fitting_error_report(const char* base_path, const cba_camera* cam_a, const double* grid_a, const cba_camera* cam_b,
+                                             const double* grid_b, const double* rotation9, int border_x, int border_y,
+                                             double max_visualization_extent, double max_visualization_extent_pixels, uint8_t* images) {
+  CentralGenericModel a(cam_a->grid_w, cam_a->grid_h, cam_a->calib_min_x, cam_a->calib_min_y, cam_a->calib_max_x, cam_a->calib_max_y, cam_a->width, cam_a->height);
+  CentralGenericModel b(cam_b->grid_w, cam_b->grid_h, cam_b->calib_min_x, cam_b->calib_min_y, cam_b->calib_max_x, cam_b->calib_max_y, cam_b->width, cam_b->height);
+  a.set_abi_grid(grid_a); b.set_abi_grid(grid_b);
+  Mat3d r;
+  for (int i = 0; i < 9; ++i) r.m[i / 3][i % 3] = rotation9[i];
+  FittingErrorImages img;
+  if (!CreateFittingErrorReport(base_path, a, b, r, border_x, border_y, max_visualization_extent, max_visualization_extent_pixels,
+                                images ? &img : nullptr)) return -1;
+  if (images) {
+    for (const std::vector<uint8_t>* v : {&img.error_magnitudes, &img.error_direction_angles, &img.error_directions, &img.reprojection_magnitudes,
+                                          &img.reprojections}) {
+      std::copy(v->begin(), v->end(), images);
+      images += v->size();
+    }
+  }
+  return 0;
+}
+// vis::CompareCalibrations on two calibration files
+extern "C" int cba_host_compare_calibrations(const char* calibration_a, const char* calibration_b, const char* report_base_path) {
+  return CompareCalibrations(calibration_a, calibration_b, report_base_path);
+}
 
 // F2 round trip through the C++ mirror: load dataset.bin + BAState directory, write both back elsewhere.
 extern "C" int cba_host_io_roundtrip(const char* dataset_in, const char* state_in, const char* dataset_out, const char* state_out,

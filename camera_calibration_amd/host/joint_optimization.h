@@ -27,6 +27,7 @@ double OptimizeJointly(Dataset& dataset, BAState* state, int max_iteration_count
 
 /// HIP device ordinal used by OptimizeJointly and the CameraModel calls (default 0 / env CBA_DEVICE).
 void SetHipDevice(int device);
+int GetHipDevice();   // the device the model-level calls use (SetHipDevice, else CBA_DEVICE, else 0)
 
 /// What OptimizeJointly does, split so that a caller which runs it in a loop (RunBundleAdjustment, APP/calibration.cc:
 /// 187-304, calls it with max_iteration_count = 1 up to 100 times) keeps ONE device-resident problem alive: the

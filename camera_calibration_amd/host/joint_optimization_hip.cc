@@ -19,6 +19,7 @@ static int hip_device() {
   return e ? std::atoi(e) : 0;
 }
 void SetHipDevice(int device) { g_device = device; }
+int GetHipDevice() { return hip_device(); }
 
 // ---- CameraModel calls -> the device-resident model (cba_model_*) -----------------------------------------
 cba_model* CameraModel::device_model(int device_ordinal) const {

@@ -267,6 +267,56 @@ int cba_model_center_point(cba_model* m, double center[3], int64_t* n_lines);
  * (optional): 127 + 127 offset / max_extent truncated as above, (0, 0, 0) for NaN.  CBA_ERR_ARG for a central model. */
 int cba_model_line_offsets(cba_model* m, const double center[3], double* offsets, uint8_t* rgb, double* max_extent);
 
+/* ---- comparison of two central-generic calibrations (APP/fitting_report.h:55-203, APP/tools/compare_calibrations.cc:39-74) ---- */
+typedef struct {
+  double rotation[9];                      /* row-major; applied to the base model's directions (parametric_r_dense) */
+  int32_t border_x, border_y;              /* base pixel = fitted pixel + border */
+  double max_visualization_extent;         /* < 0 = unset: the images use the measured maxima (:128-133) */
+  double max_visualization_extent_pixels;  /* < 0 = unset */
+  int32_t initial_estimate;                /* 0 = centre of the fitted model's calibrated area (the reference); 1 = the pixel itself,
+                                              clamped into that area (no reference counterpart: fewer iterations for close models) */
+  int32_t straggler_threshold;             /* outer projection iterations of the first launch before a pixel goes to the second one:
+                                              0 = default (8), >= 100 = never hand off, < 0 = every pixel.  Scheduling only: the
+                                              results do not depend on it. */
+} cba_compare_options;
+typedef struct {                           /* every member may be NULL; W, H = the fitted model's image */
+  double* base_directions;                 /* 3 W H: R * Unproject_base, NaN where that fails */
+  double* fitted_directions;               /* 3 W H: NaN where Unproject_fitted fails */
+  double* errors;                          /* 3 W H: fitted - base; +inf where only the fitted un-projection fails, NaN where the base one does */
+  double* reprojection_errors;             /* 2 W H: pixel centre - Project_fitted(base direction); 0 where nothing was projected */
+  uint8_t* flags;                          /* W H: bit 0 = base un-projection ok, bit 1 = fitted ok, bit 2 = projected */
+  uint8_t* error_magnitudes;               /* W H      _fitting_error_magnitudes */
+  uint8_t* error_direction_angles;         /* 3 W H    _fitting_error_direction_angles */
+  uint8_t* error_directions;               /* 3 W H    _fitting_error_directions */
+  uint8_t* reprojection_magnitudes;        /* W H      _fitting_error_reprojection_magnitudes */
+  uint8_t* reprojections;                  /* 3 W H    _fitting_error_reprojections */
+} cba_compare_outputs;
+typedef struct {
+  int64_t n_base_ok, n_both_ok, n_projected;
+  int64_t n_second_launch;                 /* pixels whose projection was finished by the second launch */
+  double max_error_component, max_error_norm;              /* over the pixels with both un-projections; before any override */
+  double reprojection_error_sum, reprojection_error_max;   /* over the projected pixels; before any override */
+  double reprojection_error_median;        /* sorted magnitudes[size / 2] (:193-194) */
+  int32_t has_median;                      /* 0 when nothing projected */
+} cba_compare_stats;
+/* The loops of CreateFittingErrorReport<CentralGenericModel, CentralGenericModel> (APP/fitting_report.h:83-125 and :135-178) for the
+ * call of APP/tools/compare_calibrations.cc:68-72: per pixel of the fitted model the two un-projections, the rotation, the iterative
+ * projection of the rotated base direction into the fitted model, the reductions and the five images, in device launches instead
+ * of 2 W H Unproject and W H Project calls.  outputs and stats may each be NULL, not both.
+ * CBA_ERR_ARG: a non-central model, base.width - 2 border_x != fitted.width (height the same), models on different devices.
+ * Defined where the reference is not:
+ *  - base un-projection ok, fitted one fails: the reference reads an uninitialised direction for the angle image and converts
+ *    255.99f * inf to u8; here the angle image is (0, 0, 0), the direction image 255 per channel, the magnitude image 255;
+ *  - a maximum of zero (identical models, nothing projected): the reference divides by zero; here the ratio is 0: direction bytes
+ *    127, magnitude bytes 0;
+ *  - base un-projection fails: zero reprojection error, the pixel is in the reprojection-magnitude image with 0 (as the reference). */
+int cba_model_compare(cba_model* base, cba_model* fitted, const cba_compare_options* options, const cba_compare_outputs* outputs,
+                      cba_compare_stats* stats);
+/* M = sum f a^T (row-major, f = fitted direction, a = base direction without any rotation) and the number n of pixels where both
+ * un-projections succeed, summed in a fixed order.  The rotation R minimising sum |R a - f|^2 is U diag(1, 1, det(U V^T)) V^T of
+ * M = U S V^T: the alignment APP/tools/compare_calibrations.cc:72 leaves as a TODO; the host derives it. */
+int cba_model_direction_moments(cba_model* base, cba_model* fitted, int32_t border_x, int32_t border_y, double M[9], int64_t* n);
+
 /* ---- solver-level entry point ---- */
 /* LMOptimizer::SolveWithSchurComplementDenseOffDiag (LV/lm_optimizer.h:1247-1369) on host arrays in
  * the reference's layout (symmetric parts: upper triangles only are read).  x = [block part; dense]. */

@@ -240,8 +240,9 @@ int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n
     rep.t_pass += now_s() - t0;
     if (st == 3) { set_error("cba_fit_grid_to_directions: a grid point lies outside the grid's 4x4 patches"); rc = CBA_ERR_ARG; break; }
     last_cost = h8[0];
-    if (iteration == 0) { rep.initial_cost = last_cost; lambda = init_lambda_factor * hsum / dof; }
-    if (last_cost == 0) break;
+    if (iteration == 0) rep.initial_cost = last_cost;
+    if (last_cost == 0) break;                              // lm_optimizer.h:755-760: before lambda is initialised (it stays -1)
+    if (iteration == 0) lambda = init_lambda_factor * hsum / dof;
     bool applied = false;
     for (int lm = 0; lm < 10 && rc == CBA_OK; ++lm) {
       rep.lm_attempts += 1;

@@ -46,6 +46,7 @@ __global__ void k_block_inverse(const double* __restrict__ Dblk, const double* _
     int p = -1; double best = -1.0;
     for (int i = 0; i < bs; ++i)
       if (!used[i] && fabs(A[i][i]) > best) { best = fabs(A[i][i]); p = i; }
+    if (p < 0) { bad = true; break; }        // nothing comparable left on the diagonal (NaN)
     perm[step] = p; used[p] = true;
     double piv = A[p][p];
     if (!(fabs(piv) > 0.0)) { bad = true; break; }

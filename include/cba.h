@@ -333,7 +333,7 @@ int cba_schur_solve_opt(int32_t block_size, int32_t n_blocks, int32_t dense_dof,
 typedef struct {
   double initial_cost;          /* cost of the first residual+Jacobian pass */
   double final_cost;            /* report.final_cost */
-  double lambda;                /* lambda after the last attempt */
+  double lambda;                /* lambda after the last attempt; -1 when no attempt was made (no iterations, or a zero initial cost) */
   int32_t iterations_performed; /* report.num_iterations_performed */
   int32_t lm_attempts;          /* dense solves */
   double t_pass;                /* residual / Jacobian / cost passes incl. accumulation [s] */

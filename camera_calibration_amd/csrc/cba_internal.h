@@ -301,6 +301,21 @@ struct CompareColorArgs {
 static_assert(std::is_trivially_copyable_v<CompareColorArgs>);
 int launch_compare_colors(const CompareColorArgs& c, hipStream_t s);
 
+// ---- kernels_localize.hip (localization accuracy test, APP/tools/localization_accuracy_test.cc:47-131) ----
+// Trials first_trial .. first_trial + n_trials - 1, one per 16-lane group.  Per-trial arrays are indexed by the trial's position in
+// the launch; points / bearings (3 P doubles per trial) are the kernel's own staging and always set, the other arrays may be null.
+struct LocalizeArgs {
+  const CamDev* gt; const CamDev* compared;
+  unsigned long long seed;
+  long long first_trial;
+  int n_trials, P, max_candidates, max_iterations;
+  float Wf, Hf, min_distance, distance_range;      // float(W), float(H), float(min), float(max) - float(min)
+  float* errors; double* angles; double* poses; int* iterations; uint8_t* flags; int* candidates_used;
+  float* pixels; float* distances; double* points; double* bearings;
+};
+static_assert(std::is_trivially_copyable_v<LocalizeArgs>);
+int launch_localize(const LocalizeArgs& a, hipStream_t s);
+
 // ---- kernels_linalg.hip (Schur stage, the fp64 MFMA GEMM, pack / diagonal kernels) ----
 // Inverse of the (bs x bs) diagonal blocks with lambda added, and Dinv*b.
 int launch_block_inverse(const double* Dblk, const double* bblk, double lambda, int bs, int nb, double* Dinv,

@@ -91,6 +91,32 @@ class CbaCompareStats(C.Structure):
 INITIAL_ESTIMATE_CENTER, INITIAL_ESTIMATE_PIXEL = 0, 1
 
 
+class CbaLocalizationOptions(C.Structure):
+    _fields_ = [("n_trials", C.c_int64), ("first_trial", C.c_int64), ("seed", C.c_uint64), ("min_distance", C.c_double),
+                ("max_distance", C.c_double), ("point_count", C.c_int32), ("max_candidates", C.c_int32), ("max_iterations", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+# (name, trailing shape with P = the point count, dtype) of cba_localization_outputs, in its order
+LOCALIZATION_ARRAYS = (("errors", (), np.float32), ("rotation_angles", (), np.float64), ("poses", (7,), np.float64),
+                       ("iterations", (), np.int32), ("flags", (), np.uint8), ("candidates_used", (), np.int32),
+                       ("pixels", ("P", 2), np.float32), ("distances", ("P",), np.float32), ("points", ("P", 3), np.float64),
+                       ("bearings", ("P", 3), np.float64))
+LOCALIZATION_SAMPLES = ("pixels", "distances", "points", "bearings")
+
+
+class CbaLocalizationOutputs(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _ in LOCALIZATION_ARRAYS]
+
+
+class CbaLocalizationStats(C.Structure):
+    _fields_ = [("n_trials", C.c_int64), ("n_valid", C.c_int64), ("n_converged", C.c_int64), ("mean_error", C.c_float),
+                ("median_error", C.c_float), ("max_error", C.c_float), ("reserved", C.c_float), ("median_rotation_angle", C.c_double)]
+
+
+LOCALIZATION_DEFAULTS = dict(n_trials=10000, point_count=15, min_distance=1.5, max_distance=2.5, max_iterations=50)
+
+
 class CbaReport(C.Structure):
     _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("lambda_", C.c_double),
                 ("accepted", C.c_int32), ("lm_attempts", C.c_int32),
@@ -111,7 +137,7 @@ EXPORTED_SYMBOLS = [
     "cba_gridfirst_plan_query", "cba_elimination_order",
     "cba_model_direction_image", "cba_render_nearest_feature_image", "cba_model_center_point", "cba_model_line_offsets",
     "cba_debug_time_direction_image",
-    "cba_model_compare", "cba_model_direction_moments",
+    "cba_model_compare", "cba_model_direction_moments", "cba_model_localization_accuracy",
 ]
 
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
@@ -564,6 +590,35 @@ class DeviceModel:
         _check(self.L.cba_model_direction_moments(self._h, fitted._h, int(border[0]), int(border[1]), _dp(M), C.byref(n)),
                "cba_model_direction_moments")
         return M, int(n.value)
+
+
+    # -- localization accuracy test ----------------------------------------------------------------
+    def localization_accuracy(self, compared: "DeviceModel", n_trials: int = 0, first_trial: int = 0, point_count: int = 0,
+                              min_distance: float = 0.0, max_distance: float = 0.0, seed: int = 0, max_candidates: int = 0,
+                              max_iterations: int = 0, want_trials: bool = True, want_samples: bool = False) -> dict:
+        """cba_model_localization_accuracy with this model as the ground truth (0 = an option's default): the statistics, with
+        want_trials the per-trial arrays and with want_samples the pixels, distances, points and bearings of every trial."""
+        T = int(n_trials) or LOCALIZATION_DEFAULTS["n_trials"]
+        P = int(point_count) or LOCALIZATION_DEFAULTS["point_count"]
+        o = CbaLocalizationOptions()
+        o.n_trials, o.first_trial, o.seed = int(n_trials), int(first_trial), int(seed) & 0xFFFFFFFFFFFFFFFF
+        o.min_distance, o.max_distance = float(min_distance), float(max_distance)
+        o.point_count, o.max_candidates, o.max_iterations = int(point_count), int(max_candidates), int(max_iterations)
+        out, res = CbaLocalizationOutputs(), {}
+        if T > 0 and 0 < P <= 1024:          # (anything else is the library's to reject)
+            for name, tail, dt in LOCALIZATION_ARRAYS:
+                if want_samples if name in LOCALIZATION_SAMPLES else want_trials:
+                    res[name] = np.zeros((T,) + tuple(P if d == "P" else d for d in tail), dtype=dt)
+                    setattr(out, name, res[name].ctypes.data)
+        st = CbaLocalizationStats()
+        self.L.cba_model_localization_accuracy.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CbaLocalizationOptions),
+                                                           C.POINTER(CbaLocalizationOutputs), C.POINTER(CbaLocalizationStats)]
+        _check(self.L.cba_model_localization_accuracy(self._h, compared._h, C.byref(o), C.byref(out), C.byref(st)),
+               "cba_model_localization_accuracy")
+        for name, _ in CbaLocalizationStats._fields_:
+            if name != "reserved":
+                res[name] = getattr(st, name)
+        return res
 
 
 def render_nearest_feature_image(width: int, height: int, site_xy_quarter_px: np.ndarray, site_rgb: np.ndarray, device: int = 0,

@@ -7,6 +7,7 @@
 #include "calibration_fit.h"
 #include "calibration.h"
 #include "fitting_report.h"
+#include "localization_accuracy.h"
 
 #include <algorithm>
 #include <chrono>
@@ -258,6 +259,12 @@ extern "C" int cba_host_fitting_error_report(const char* base_path, const cba_ca
 // vis::CompareCalibrations on two calibration files
 extern "C" int cba_host_compare_calibrations(const char* calibration_a, const char* calibration_b, const char* report_base_path) {
   return CompareCalibrations(calibration_a, calibration_b, report_base_path);
+}
+
+// vis::LocalizationAccuracyTest (localization_accuracy.h) on two calibration files with explicit options
+extern "C" int cba_host_localization_accuracy_test(const char* gt_model, const char* compared_model, const cba_localization_options* options,
+                                                   cba_localization_stats* stats) {
+  return options ? LocalizationAccuracyTest(gt_model, compared_model, *options, stats) : LocalizationAccuracyTest(gt_model, compared_model);
 }
 
 // F2 round trip through the C++ mirror: load dataset.bin + BAState directory, write both back elsewhere.

@@ -317,6 +317,62 @@ int cba_model_compare(cba_model* base, cba_model* fitted, const cba_compare_opti
  * M = U S V^T: the alignment APP/tools/compare_calibrations.cc:72 leaves as a TODO; the host derives it. */
 int cba_model_direction_moments(cba_model* base, cba_model* fitted, int32_t border_x, int32_t border_y, double M[9], int64_t* n);
 
+/* ---- localization accuracy test between two central-generic calibrations (APP/tools/localization_accuracy_test.cc:47-131) ---- */
+typedef struct {                           /* 0 selects the default of every member but seed and first_trial */
+  int64_t n_trials;                        /* default 10 000 (kNumTrials) */
+  int64_t first_trial;                     /* trial ids are first_trial + i: a run can be split over calls */
+  uint64_t seed;
+  double min_distance, max_distance;       /* default 1.5, 2.5 (kMinDistance, kMaxDistance); taken as float; 0 < min <= max */
+  int32_t point_count;                     /* P, default 15 (kPointCount); 3 <= P <= 1024 */
+  int32_t max_candidates;                  /* candidates a trial may draw, default 64 P */
+  int32_t max_iterations;                  /* default 50 */
+  int32_t reserved;                        /* 0 */
+} cba_localization_options;
+typedef struct {                           /* every member may be NULL; T = n_trials, P = point_count */
+  float* errors;                           /* T: |c| rounded to float (camera_error_distance); NaN for an invalid trial */
+  double* rotation_angles;                 /* T: angle of R; NaN for an invalid trial */
+  double* poses;                           /* 7 T: qw qx qy qz tx ty tz of global_tr_image (t = the centre c); NaN for an invalid trial */
+  int32_t* iterations;                     /* T: evaluations of the normal equations; 0 for an invalid trial */
+  uint8_t* flags;                          /* T: bit 0 = valid (P candidates kept), bit 1 = the stop rule was met */
+  int32_t* candidates_used;                /* T: candidates drawn: index of the last kept one + 1; max_candidates for an invalid trial */
+  float* pixels;                           /* 2 P T: the kept candidates, in index order */
+  float* distances;                        /* P T */
+  double* points;                          /* 3 P T: X_i */
+  double* bearings;                        /* 3 P T: b_i; slots an invalid trial did not fill are NaN in all four arrays */
+} cba_localization_outputs;
+typedef struct {
+  int64_t n_trials, n_valid, n_converged;  /* n_converged: valid trials with flag bit 1 */
+  float mean_error, median_error, max_error;   /* over the valid trials' float errors, NaN (max: 0) when there is none */
+  float reserved;
+  double median_rotation_angle;            /* sorted[n_valid / 2]; NaN when there is none */
+} cba_localization_stats;
+/* LocalizationAccuracyTest (APP/tools/localization_accuracy_test.cc:47-131) for two central-generic models, every trial on the device.
+ * outputs and stats may each be NULL, not both.  CBA_ERR_ARG: a model that is not central-generic, models on different devices,
+ * "The ground truth and compared camera models do not have the same image size.", an option outside its constraint.
+ *
+ * Candidate k of trial t (all arithmetic in float, every operation rounded on its own; the reference seeds rand() with the time):
+ *   mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31  (mod 2^64)
+ *   h = mix(mix(seed + t) + k)
+ *   ux = float(h >> 40 & 0xFFFFFF) * 2^-24;  uy = float(h >> 16 & 0xFFFFFF) * 2^-24;  ud = float(h & 0xFFFF) * 2^-16
+ *   pixel = (ux * float(W), uy * float(H));  distance = float(min) + ud * (float(max) - float(min))
+ * The pixel goes to Unproject as the float converted to double (the reference's Unproject(float, float, ...) call).  A trial takes
+ * its candidates in index order and keeps candidate k if both models un-project the pixel (the reference's `-- p; continue`) until it
+ * holds P; if max_candidates run out first the trial is invalid: flag bit 0 clear, NaN error, in no statistic.
+ *   X_i = normalize(dir_gt) * (double)distance,  b_i = normalize(dir_compared)
+ * Pose: the rotation R and the centre c (global_tr_image) minimising sum_i |normalize(R^T (X_i - c)) - b_i|^2 from R = I, c = 0 by
+ * damped Gauss-Newton on (omega, delta), R <- R exp(omega), c <- c + delta; the 6 x 6 system by LDL^T in fp64.  An evaluation whose cost
+ * exceeds the accepted one's (by more than 1e-9 of it + 1e-30) halves the step from the accepted pose (at most 20 times, then the
+ * trial stops unconverged) and counts as an iteration.  Stop: max |omega, delta| <= 1e-13 (the step is still applied; flag bit 1), a
+ * pivot that is not positive, or max_iterations.
+ * DEVIATION from the reference: it calls OpenGV's optimize_nonlinear (Cayley rotation, one residual 1 - f . f' per point, Eigen's
+ * numerically differentiated LM).  OpenGV is not part of the reference tree; no reference-produced vector exists for this tool.  The
+ * cost here has the same minimiser when the bearings are consistent and is the squared angular error at first order.
+ * Statistics, on the host from the valid trials' float errors in trial order: the mean is a float running sum divided by the count
+ * (Mean<float>, libvis/statistics.h:94-119), the median sorted[n / 2] (:123-124).  n_valid == 0: CBA_OK, NaN mean and median.
+ * A trial's results are a function of (models, options, t) only: not of n_trials, first_trial or where on the device it ran. */
+int cba_model_localization_accuracy(cba_model* gt, cba_model* compared, const cba_localization_options* options,
+                                    const cba_localization_outputs* outputs, cba_localization_stats* stats);
+
 /* ---- solver-level entry point ---- */
 /* LMOptimizer::SolveWithSchurComplementDenseOffDiag (LV/lm_optimizer.h:1247-1369) on host arrays in
  * the reference's layout (symmetric parts: upper triangles only are read).  x = [block part; dense]. */

@@ -217,6 +217,8 @@ int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, c
 int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const std::vector<int>& cell_base_host, int ld,
                             const uint8_t* flags, const int* cells, const int* cell_base, int* count, int* start, int* fill, int* order,
                             double* Hdd, int rig_row_first, const double* det_scale, double* bd, hipStream_t s);
+// exclusive scan of n counts into n + 1 starts (one workgroup; the counting sorts of kernels_obs.hip and kernels_fit.hip)
+int launch_exclusive_scan(const int* count, int n, int* start, hipStream_t s);
 // ---- kernels_update.hip (cost reductions, state update) ----
 // 8 outputs: [0] sum ref (valid), [1] sum test (valid), [2] masked ref, [3] masked test, [4] count both valid,
 // [5] n valid ref, [6] n valid test, [7] n jac dropped (flags)

@@ -10,7 +10,7 @@
 //  k_compare_second   the complete projection (100 outer iterations) of the listed pixels, packed into full wavefronts, from the same
 //                     start and from the g the first launch stored.
 //  k_compare_reduce   counts, maxima, the sum of the reprojection magnitudes and (want_moments) M = sum f a^T: a fixed assignment of
-//  (+ final)          pixels to lanes and fixed trees (as k_center_point_sums): run-to-run identical.
+//  (+ fold)           pixels to lanes and fixed trees (as k_center_point_sums): run-to-run identical.
 //  k_compare_colors   the five images from the per-pixel arrays and the maxima.
 //
 // Both launches project through ONE non-inlined device function (compare_project): they execute the same machine code, so a pixel's
@@ -28,7 +28,7 @@
 //    ratio is 0: direction bytes 127, magnitude bytes 0.
 //  * without bit 0 the pixel has zero reprojection error and takes part in the reprojection-magnitude image with 0, as in the
 //    reference.
-#include "cba_internal.h"
+#include "block_device.hip.h"
 
 namespace cba {
 
@@ -38,8 +38,8 @@ constexpr int kCmpTileW = 32, kCmpTileH = 8;      // a workgroup: four 8 x 8 wav
 // area as projection_candidate clamps its iterates
 __device__ __forceinline__ void compare_start(const CamDev& cb, int mode, int x, int y, double& px, double& py) {
   if (mode == 1) {
-    px = fmax((double)cb.min_x, fmin((double)((float)x + 0.5f), cb.max_x + 0.999));
-    py = fmax((double)cb.min_y, fmin((double)((float)y + 0.5f), cb.max_y + 0.999));
+    px = fmax((double)cb.min_x, fmin(pixel_center(x), cb.max_x + 0.999));
+    py = fmax((double)cb.min_y, fmin(pixel_center(y), cb.max_y + 0.999));
   } else {
     center_pixel(cb, px, py);
   }
@@ -50,7 +50,7 @@ struct CompareProjection { double px, py; int ok, capped; };
 __device__ __noinline__ CompareProjection compare_project(const CamDev* __restrict__ fitted, double gx, double gy, double gz, double px,
                                                           double py, int max_outer) {
   const CamDev cb = *fitted;
-  Subst none; none.index = -1;
+  const Subst none = no_subst();
   const double g[3] = {gx, gy, gz};
   bool capped = false;
   CompareProjection r;
@@ -64,16 +64,16 @@ __global__ void __launch_bounds__(256) k_compare_pass(CompareArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int x = blockIdx.x * kCmpTileW + wave * 8 + (lane & 7), y = blockIdx.y * kCmpTileH + (lane >> 3);
   const bool inside = x < a.W && y < a.H;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll), inf = __longlong_as_double(0x7ff0000000000000ll);
-  Subst none; none.index = -1;
+  const double nan = quiet_nan(), inf = __longlong_as_double(0x7ff0000000000000ll);
+  const Subst none = no_subst();
   bool capped = false;
   if (inside) {
     const size_t p = (size_t)y * a.W + x;
     double av[3], f[3], o[3], g[3] = {nan, nan, nan}, e[3] = {nan, nan, nan};
     const CamDev ca = *a.base;
-    const bool base_ok = unproject<kCentral>(ca, none, (double)((float)(a.border_x + x) + 0.5f), (double)((float)(a.border_y + y) + 0.5f), av, o);
+    const bool base_ok = unproject<kCentral>(ca, none, pixel_center(a.border_x + x), pixel_center(a.border_y + y), av, o);
     const CamDev cb = *a.fitted;
-    const bool fit_ok = unproject<kCentral>(cb, none, (double)((float)x + 0.5f), (double)((float)y + 0.5f), f, o);
+    const bool fit_ok = unproject<kCentral>(cb, none, pixel_center(x), pixel_center(y), f, o);
     if (!fit_ok) f[0] = f[1] = f[2] = nan;
     if (base_ok) {
 #pragma unroll
@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(256) k_compare_pass(CompareArgs a) {
       capped = pr.capped != 0;
       if (pr.ok) {
         fl |= 4;
-        rx = (double)((float)x + 0.5f) - pr.px; ry = (double)((float)y + 0.5f) - pr.py;
+        rx = pixel_center(x) - pr.px; ry = pixel_center(y) - pr.py;
       }
     }
 #pragma unroll
@@ -99,14 +99,8 @@ __global__ void __launch_bounds__(256) k_compare_pass(CompareArgs a) {
     a.reproj[2 * p] = rx; a.reproj[2 * p + 1] = ry;
     a.flags[p] = (uint8_t)fl;
   }
-  const unsigned long long m = __ballot(capped);
-  if (m) {
-    const int leader = __ffsll((long long)m) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(a.list_count, __popcll(m));
-    base = __shfl(base, leader);
-    if (capped) a.list[base + __popcll(m & ((1ull << lane) - 1))] = y * a.W + x;
-  }
+  const int slot = wave_append(capped, a.list_count);
+  if (slot >= 0) a.list[slot] = y * a.W + x;
 }
 
 __global__ void __launch_bounds__(64) k_compare_second(CompareArgs a, int n_list) {
@@ -120,7 +114,7 @@ __global__ void __launch_bounds__(64) k_compare_second(CompareArgs a, int n_list
   const CompareProjection pr = compare_project(a.fitted, a.base_dir[3 * (size_t)p], a.base_dir[3 * (size_t)p + 1], a.base_dir[3 * (size_t)p + 2],
                                                px, py, 100);
   if (pr.ok) {
-    a.reproj[2 * (size_t)p] = (double)((float)x + 0.5f) - pr.px; a.reproj[2 * (size_t)p + 1] = (double)((float)y + 0.5f) - pr.py;
+    a.reproj[2 * (size_t)p] = pixel_center(x) - pr.px; a.reproj[2 * (size_t)p + 1] = pixel_center(y) - pr.py;
     a.flags[p] = a.flags[p] | 4;
   }
 }
@@ -142,9 +136,11 @@ int launch_compare_second(const CompareArgs& a, int n_list, hipStream_t s) {
 // reductions: slot k of kCompareSums is a sum, or a maximum for k in {kCmpMaxComponent, kCmpMaxNorm, kCmpReprojMax}
 // ------------------------------------------------------------------------------------------------
 constexpr int kCmpBlocks = 256;
-__device__ __forceinline__ double compare_combine(int k, double u, double v) {
-  return (k == kCmpMaxComponent || k == kCmpMaxNorm || k == kCmpReprojMax) ? fmax(u, v) : u + v;
-}
+struct CompareCombine {
+  __device__ __forceinline__ double operator()(int k, double u, double v) const {
+    return (k == kCmpMaxComponent || k == kCmpMaxNorm || k == kCmpReprojMax) ? fmax(u, v) : u + v;
+  }
+};
 // moment_dir: A's directions BEFORE the rotation (the caller's base_dir of a pass with the identity rotation)
 __global__ void __launch_bounds__(256) k_compare_reduce(int64_t n, const uint8_t* __restrict__ flags, const double* __restrict__ err,
                                                         const double* __restrict__ reproj, const double* __restrict__ fit_dir,
@@ -176,30 +172,15 @@ __global__ void __launch_bounds__(256) k_compare_reduce(int64_t n, const uint8_t
     }
   }
   __shared__ double sh[kCompareSums][256];
-#pragma unroll
-  for (int k = 0; k < kCompareSums; ++k) sh[k][threadIdx.x] = acc[k];
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-#pragma unroll
-      for (int k = 0; k < kCompareSums; ++k) sh[k][threadIdx.x] = compare_combine(k, sh[k][threadIdx.x], sh[k][threadIdx.x + s]);
-    __syncthreads();
-  }
+  block_reduce_256(acc, sh, CompareCombine());
   if (threadIdx.x < kCompareSums) partials[blockIdx.x * kCompareSums + threadIdx.x] = sh[threadIdx.x][0];
-}
-__global__ void k_compare_reduce_final(const double* __restrict__ partials, double* __restrict__ out) {
-  const int k = threadIdx.x;
-  if (k >= kCompareSums) return;
-  double s = 0;
-  for (int b = 0; b < kCmpBlocks; ++b) s = compare_combine(k, s, partials[b * kCompareSums + k]);
-  out[k] = s;
 }
 int compare_partials_doubles() { return kCmpBlocks * kCompareSums; }
 int launch_compare_reduce(int64_t n, const uint8_t* flags, const double* err, const double* reproj, const double* fit_dir,
                           const double* moment_dir, bool want_moments, double* partials, double* out, hipStream_t s) {
   hipLaunchKernelGGL(k_compare_reduce, dim3(kCmpBlocks), dim3(256), 0, s, n, flags, err, reproj, fit_dir, moment_dir, want_moments ? 1 : 0,
                      partials);
-  hipLaunchKernelGGL(k_compare_reduce_final, dim3(1), dim3(64), 0, s, partials, out);
+  hipLaunchKernelGGL((k_fold_partials<kCompareSums, kCmpBlocks, CompareCombine>), dim3(1), dim3(64), 0, s, partials, out);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
@@ -207,10 +188,6 @@ int launch_compare_reduce(int64_t n, const uint8_t* flags, const double* err, co
 // ------------------------------------------------------------------------------------------------
 // the five images (:135-178), every expression in the reference's types
 // ------------------------------------------------------------------------------------------------
-// double -> int of the reference's x86-64 builds: truncated; what no 32-bit integer holds (NaN included) is INT_MIN
-__device__ __forceinline__ int compare_trunc_i32(double v) { return fabs(v) < 2147483648.0 ? (int)v : (int)0x80000000; }
-__device__ __forceinline__ uint8_t compare_u8(double v) { return (uint8_t)(uint32_t)compare_trunc_i32(v); }
-
 __global__ void __launch_bounds__(256) k_compare_colors(CompareColorArgs c) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= c.n) return;
@@ -223,16 +200,16 @@ __global__ void __launch_bounds__(256) k_compare_colors(CompareColorArgs c) {
     for (int k = 0; k < 3; ++k) {
       // (error / max_error_component).cwiseMax(-1).cwiseMin(1); zero maximum: 0; error = +inf: 1
       const double rel = !both ? 1.0 : (c.max_error_component > 0 ? fmin(1.0, fmax(-1.0, e[k] / c.max_error_component)) : 0.0);
-      dir[k] = compare_u8((double)(255.99f / 2) * (rel + (double)1.f));                              // :159-160
+      dir[k] = trunc_u8((double)(255.99f / 2) * (rel + (double)1.f));                              // :159-160
     }
     if (both) {
       const double* g = c.base_dir + 3 * p; const double* f = c.fit_dir + 3 * p;
       const double scale = 127 / (3.14159265358979323846 / (double)180.f * 0.025);                  // int / (double / float * double)
-      ang[0] = (uint8_t)min(255, max(0, compare_trunc_i32(127 + scale * (atan2(g[2], g[0]) - atan2(f[2], f[0])) + 0.5)));       // :155
-      ang[1] = (uint8_t)min(255, max(0, compare_trunc_i32(127 + scale * (atan2(g[1], g[2]) - atan2(f[1], f[2])) + 0.5)));       // :156
+      ang[0] = (uint8_t)min(255, max(0, trunc_i32(127 + scale * (atan2(g[2], g[0]) - atan2(f[2], f[0])) + 0.5)));       // :155
+      ang[1] = (uint8_t)min(255, max(0, trunc_i32(127 + scale * (atan2(g[1], g[2]) - atan2(f[1], f[2])) + 0.5)));       // :156
       ang[2] = 127;
       const double norm = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
-      mag = c.max_error_norm > 0 ? compare_u8((double)255.99f * (norm / c.max_error_norm)) : (uint8_t)0;                         // :161
+      mag = c.max_error_norm > 0 ? trunc_u8((double)255.99f * (norm / c.max_error_norm)) : (uint8_t)0;                         // :161
     } else {
       mag = 255;
     }

@@ -12,8 +12,7 @@
 //                       origins overlap, samples of the same origin (tens to hundreds for dense fits) do not collide
 #include <hip/hip_runtime.h>
 
-#include "cba_internal.h"
-#include "model.hip.h"
+#include "block_device.hip.h"
 
 namespace cba {
 
@@ -78,29 +77,6 @@ __global__ void __launch_bounds__(256) k_fit_key_count(const int* __restrict__ k
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && keys[i] >= 0) atomicAdd(count + keys[i], 1);
 }
-__global__ void __launch_bounds__(1024) k_fit_key_scan(const int* __restrict__ count, int n, int* __restrict__ start) {
-  __shared__ int sh[1024];
-  __shared__ int carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = (i < n) ? count[i] : 0;
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      const int t = ((int)threadIdx.x >= off) ? sh[threadIdx.x - off] : 0;
-      __syncthreads();
-      sh[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < n) start[i] = carry + sh[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += sh[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) start[n] = carry;
-}
 __global__ void __launch_bounds__(256) k_fit_key_fill(const int* __restrict__ keys, int64_t n, const int* __restrict__ start,
                                                       int* __restrict__ fill, int* __restrict__ order) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -162,9 +138,7 @@ __global__ void __launch_bounds__(256) k_fit_diag_sum(const double* __restrict__
   __shared__ double sh[256];
   double acc = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) acc += H[(size_t)i * ld + i];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) { if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s]; __syncthreads(); }
+  block_reduce_256(acc, sh, SumOp());
   if (threadIdx.x == 0) out[0] = sh[0];
 }
 
@@ -185,7 +159,7 @@ int launch_fit_accumulate(int gw, int gh, int64_t n, const double* rec, const in
   if (n == 0) return CBA_OK;
   dim3 g((unsigned)((n + 255) / 256)), block(256);
   hipLaunchKernelGGL(k_fit_key_count, g, block, 0, s, keys, n, count);
-  hipLaunchKernelGGL(k_fit_key_scan, dim3(1), dim3(1024), 0, s, count, n_keys, start);
+  CBA_TRY(launch_exclusive_scan(count, n_keys, start, s));
   hipLaunchKernelGGL(k_fit_key_fill, g, block, 0, s, keys, n, start, fill, order);
   hipLaunchKernelGGL(k_fit_accumulate, dim3((unsigned)((n_keys + 3) / 4)), block, 0, s, gw, n_keys, rec, start, order, H, ld, b);
   CBA_HIP(hipGetLastError());

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "block_device.hip.h"
 #include "linalg_internal.h"
 
 namespace cba {
@@ -683,9 +684,7 @@ __global__ void __launch_bounds__(256) k_diag_sum(const double* __restrict__ Dbl
   const int nblk = bs * nb;
   for (int i = threadIdx.x; i < nblk; i += 256) { int b = i / bs, k = i % bs; acc += Dblk[(size_t)b * bs * bs + k * bs + k]; }
   for (int i = threadIdx.x; i < dd; i += 256) acc += Hdd[(size_t)i * ld + i];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) { if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s]; __syncthreads(); }
+  block_reduce_256(acc, sh, SumOp());
   if (threadIdx.x == 0) out[0] = sh[0];
 }
 int launch_diag_sum(const double* Dblk, int bs, int nb, const double* Hdd, int ld, int dd, double* out, hipStream_t s) {

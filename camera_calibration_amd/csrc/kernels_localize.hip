@@ -120,8 +120,8 @@ __global__ void __launch_bounds__(kLocBlock) k_localize(LocalizeArgs a) {
   const bool active = slot < a.n_trials;
   const size_t first = (size_t)(active ? slot : 0) * (size_t)a.P;           // the trial's first sample
   const unsigned long long tkey = localize_mix(a.seed + (unsigned long long)(a.first_trial + slot));
-  const double nan = __longlong_as_double(0x7ff8000000000000ll), inf = __longlong_as_double(0x7ff0000000000000ll);
-  Subst none; none.index = -1;
+  const double nan = quiet_nan(), inf = __longlong_as_double(0x7ff0000000000000ll);
+  const Subst none = no_subst();
 
   // ---- sampling ----
   int count = 0, k0 = 0, used = 0;

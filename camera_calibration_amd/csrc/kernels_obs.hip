@@ -665,7 +665,9 @@ __global__ void __launch_bounds__(256) k_cell_count(PassArgs a, const uint8_t* _
   const int gw = a.cams[cam].gw;
   atomicAdd(count + cell_base[cam] + cells[2 * o + 1] * gw + cells[2 * o], 1);
 }
-__global__ void __launch_bounds__(1024) k_cell_scan(const int* __restrict__ count, int n, int* __restrict__ start) {
+// start[i] = count[0] + ... + count[i - 1] for i = 0 .. n (start[n]: the total): ONE workgroup scans 1024 entries at a time and
+// carries the running total; shared by the counting sorts of the cell buckets (here) and of the key buckets (kernels_fit.hip)
+__global__ void __launch_bounds__(1024) k_exclusive_scan(const int* __restrict__ count, int n, int* __restrict__ start) {
   __shared__ int sh[1024];
   __shared__ int carry;
   if (threadIdx.x == 0) carry = 0;
@@ -687,6 +689,11 @@ __global__ void __launch_bounds__(1024) k_cell_scan(const int* __restrict__ coun
     __syncthreads();
   }
   if (threadIdx.x == 0) start[n] = carry;
+}
+int launch_exclusive_scan(const int* count, int n, int* start, hipStream_t s) {
+  hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, s, count, n, start);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
 }
 __global__ void __launch_bounds__(256) k_cell_fill(PassArgs a, const uint8_t* __restrict__ flags, const int* __restrict__ cells,
                                                    const int* __restrict__ cell_base, const int* __restrict__ start,
@@ -826,7 +833,7 @@ int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& ca
   CBA_HIP(hipMemsetAsync(fill, 0, sizeof(int) * (size_t)n_keys, s));
   dim3 grid((unsigned)((a.n_obs + 255) / 256)), block(256);
   hipLaunchKernelGGL(k_cell_count, grid, block, 0, s, a, flags, cells, cell_base, count);
-  hipLaunchKernelGGL(k_cell_scan, dim3(1), dim3(1024), 0, s, count, n_keys, start);
+  CBA_TRY(launch_exclusive_scan(count, n_keys, start, s));
   hipLaunchKernelGGL(k_cell_fill, grid, block, 0, s, a, flags, cells, cell_base, start, fill, order);
   for (size_t c = 0; c < cams.size(); ++c) {
     const int n_cells = cams[c].grid_w * cams[c].grid_h;

@@ -92,7 +92,7 @@ int launch_tangents(const double* dir_grid, double* tang, int G, hipStream_t s) 
 template <int MODEL>
 __device__ __forceinline__ bool base_projection(const PassArgs& a, const CamDev& c, int64_t o, const double* local, int max_outer,
                                                 bool& capped, double& px, double& py) {
-  Subst none; none.index = -1;
+  const Subst none = no_subst();
   px = a.last_projection[2 * o]; py = a.last_projection[2 * o + 1];
   if (!in_calibrated_area(c, px, py) || px != px || py != py) center_pixel(c, px, py);
   capped = false;
@@ -183,7 +183,7 @@ __global__ void __launch_bounds__(256) k_base_project_slow(PassArgs a, double* _
   if (MODEL == kCentral) normalize3(target[0], target[1], target[2]);
   double px = a.last_projection[2 * o], py = a.last_projection[2 * o + 1];
   if (attempt == 1 || !in_calibrated_area(c, px, py) || px != px || py != py) center_pixel(c, px, py);
-  Subst none; none.index = -1;
+  const Subst none = no_subst();
   double dir[3] = {0, 0, 0}, org[3] = {0, 0, 0}, jd[6] = {0, 0, 0, 0, 0, 0}, jo[6] = {0, 0, 0, 0, 0, 0};
   bool cur_in = false, active = live, result = false;
   if (active) cur_in = unproject_jac<MODEL>(c, none, px, py, dir, org, jd, jo);
@@ -312,7 +312,7 @@ __global__ void __launch_bounds__(256) k_project_points(const CamDev* __restrict
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const CamDev c = *camp;
-  Subst none; none.index = -1;
+  const Subst none = no_subst();
   double px, py;
   if (init) { px = init[2 * i]; py = init[2 * i + 1]; }
   else center_pixel(c, px, py);
@@ -338,7 +338,7 @@ __global__ void __launch_bounds__(256) k_unproject(const CamDev* __restrict__ ca
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const CamDev c = *camp;
-  Subst none; none.index = -1;
+  const Subst none = no_subst();
   double d[3] = {0, 0, 0}, o[3] = {0, 0, 0}, jd[6] = {0, 0, 0, 0, 0, 0}, jo[6] = {0, 0, 0, 0, 0, 0};
   bool r;
   if (jac) r = unproject_jac<MODEL>(c, none, pixels[2 * i], pixels[2 * i + 1], d, o, jd, jo);

@@ -34,16 +34,12 @@
 // least-squares problem; the kernel sums its normal equations A = sum (t1 t1^T + t2 t2^T), b = sum (t1 t1^T + t2 t2^T) o with a
 // fixed assignment of pixels to lanes and fixed trees (as k_reduce_costs_*), the host solves the 3 x 3 system: the least-squares
 // point itself, which LM converges to and stops within its stopping rule of.
-#include "cba_internal.h"
+#include "block_device.hip.h"
 
 namespace cba {
 
 constexpr int kTileW = 32, kTileH = 8;
 constexpr int kStagePoints = 160;     // control points of a tile's window the LDS stage holds (3.75 / 7.5 KB): cells down to ~3 pixels
-
-// the reference's `u8 = double` for values beyond 255: truncate to a 32-bit integer, keep the low 8 bits (a value no 32-bit integer
-// holds, NaN included, converts to 0x80000000 there: 0)
-__device__ __forceinline__ uint8_t wrap_u8(double v) { return fabs(v) < 2147483648.0 ? (uint8_t)(uint32_t)(int32_t)v : (uint8_t)0; }
 
 template <int MODEL>
 __global__ void __launch_bounds__(256) k_direction_image(const CamDev* __restrict__ camp, int W, int H, double* __restrict__ dirs,
@@ -62,8 +58,8 @@ __global__ void __launch_bounds__(256) k_direction_image(const CamDev* __restric
   bool staged = false;
   if (xa <= xb && ya <= yb) {
     double ga, gb, gc, gd;
-    pixel_to_grid(c, (double)((float)xa + 0.5f), (double)((float)ya + 0.5f), ga, gb);
-    pixel_to_grid(c, (double)((float)xb + 0.5f), (double)((float)yb + 0.5f), gc, gd);
+    pixel_to_grid(c, pixel_center(xa), pixel_center(ya), ga, gb);
+    pixel_to_grid(c, pixel_center(xb), pixel_center(yb), gc, gd);
     wx0 = (int)(ga + 2) - 3; wy0 = (int)(gb + 2) - 3;
     ww = (int)(gc + 2) + 1 - wx0; wh = (int)(gd + 2) + 1 - wy0;
     staged = ww * wh <= min(stage_points, kStagePoints);
@@ -82,12 +78,11 @@ __global__ void __launch_bounds__(256) k_direction_image(const CamDev* __restric
     __syncthreads();
   }
   const bool inside = x < W && y < H;
-  const double px = (double)((float)x + 0.5f), py = (double)((float)y + 0.5f);
+  const double px = pixel_center(x), py = pixel_center(y);
   const bool valid = inside && in_calibrated_area(c, px, py);
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  double d[3] = {nan, nan, nan}, o[3];
+  double d[3] = {quiet_nan(), quiet_nan(), quiet_nan()}, o[3];
   if (valid) {
-    Subst none; none.index = -1;
+    const Subst none = no_subst();
     if (staged) {
       double gx, gy;
       pixel_to_grid(c, px, py, gx, gy);
@@ -101,9 +96,9 @@ __global__ void __launch_bounds__(256) k_direction_image(const CamDev* __restric
   }
   uint8_t col[3] = {0, 0, 0};
   if (valid) {
-    col[0] = wrap_u8((double)(70 * 255.99f / 2.f) * (d[0] + 1));
-    col[1] = wrap_u8((double)(70 * 255.99f / 2.f) * (d[1] + 1));
-    col[2] = wrap_u8((double)(270 * 255.99f / 2.f) * (d[2] + 1));
+    col[0] = trunc_u8((double)(70 * 255.99f / 2.f) * (d[0] + 1));
+    col[1] = trunc_u8((double)(70 * 255.99f / 2.f) * (d[1] + 1));
+    col[2] = trunc_u8((double)(270 * 255.99f / 2.f) * (d[2] + 1));
   }
   if (inside) {
     const size_t p = (size_t)y * W + x;
@@ -187,15 +182,8 @@ __global__ void __launch_bounds__(256) k_nearest_site(SiteGrid g, int W, int H, 
       for_ring(g, bx, by, k, [&](int s) { count += site_dist2(g, s, x, y) <= reach2 ? 1 : 0; });
     if (count == 1) write_pixel(g.rgb + 3 * (size_t)s0, (size_t)y * W + x, rgb, accum);
   }
-  const bool listed = inside && count > 1;
-  const unsigned long long m = __ballot(listed);
-  if (m) {
-    const int lane = __lane_id(), leader = __ffsll((long long)m) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(list_count, __popcll(m));
-    base = __shfl(base, leader);
-    if (listed) list[base + __popcll(m & ((1ull << lane) - 1))] = make_int2(y * W + x, s0);
-  }
+  const int slot = wave_append(inside && count > 1, list_count);
+  if (slot >= 0) list[slot] = make_int2(y * W + x, s0);
 }
 
 constexpr int kClipLanes = 64;
@@ -297,11 +285,11 @@ __global__ void __launch_bounds__(256) k_center_point_sums(const CamDev* __restr
   double acc[kCenterSums];
 #pragma unroll
   for (int k = 0; k < kCenterSums; ++k) acc[k] = 0;
-  Subst none; none.index = -1;
+  const Subst none = no_subst();
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)kSumBlocks * 256) {
     const int x = c.min_x + (int)(i % aw), y = c.min_y + (int)(i / aw);
     double d[3], o[3], t1[3], t2[3];
-    if (!unproject<kNoncentral>(c, none, (double)((float)x + 0.5f), (double)((float)y + 0.5f), d, o)) continue;
+    if (!unproject<kNoncentral>(c, none, pixel_center(x), pixel_center(y), d, o)) continue;
     tangents_of(d, t1, t2);
     const double M[6] = {t1[0] * t1[0] + t2[0] * t2[0], t1[0] * t1[1] + t2[0] * t2[1], t1[0] * t1[2] + t2[0] * t2[2],
                          t1[1] * t1[1] + t2[1] * t2[1], t1[1] * t1[2] + t2[1] * t2[2], t1[2] * t1[2] + t2[2] * t2[2]};
@@ -315,28 +303,13 @@ __global__ void __launch_bounds__(256) k_center_point_sums(const CamDev* __restr
     acc[10] += 1;
   }
   __shared__ double sh[kCenterSums][256];
-#pragma unroll
-  for (int k = 0; k < kCenterSums; ++k) sh[k][threadIdx.x] = acc[k];
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-#pragma unroll
-      for (int k = 0; k < kCenterSums; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
-    __syncthreads();
-  }
+  block_reduce_256(acc, sh, SumOp());
   if (threadIdx.x < kCenterSums) partials[blockIdx.x * kCenterSums + threadIdx.x] = sh[threadIdx.x][0];
-}
-__global__ void k_center_point_final(const double* __restrict__ partials, double* __restrict__ out) {
-  const int k = threadIdx.x;
-  if (k >= kCenterSums) return;
-  double s = 0;
-  for (int b = 0; b < kSumBlocks; ++b) s += partials[b * kCenterSums + k];
-  out[k] = s;
 }
 int center_point_partials_doubles() { return kSumBlocks * kCenterSums; }
 int launch_center_point_sums(const CamDev* cam_dev, double* partials, double* out, hipStream_t s) {
   hipLaunchKernelGGL(k_center_point_sums, dim3(kSumBlocks), dim3(256), 0, s, cam_dev, partials);
-  hipLaunchKernelGGL(k_center_point_final, dim3(1), dim3(64), 0, s, partials, out);
+  hipLaunchKernelGGL((k_fold_partials<kCenterSums, kSumBlocks, SumOp>), dim3(1), dim3(64), 0, s, partials, out);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
@@ -346,12 +319,11 @@ __global__ void __launch_bounds__(256) k_line_offsets(const CamDev* __restrict__
                                                       double* __restrict__ offsets, double* __restrict__ block_max) {
   const CamDev c = *camp;
   const int x = blockIdx.x * kTileW + (threadIdx.x & (kTileW - 1)), y = blockIdx.y * kTileH + threadIdx.x / kTileW;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  double off[3] = {nan, nan, nan}, ext = 0;
+  double off[3] = {quiet_nan(), quiet_nan(), quiet_nan()}, ext = 0;
   if (x < W && y < H) {
-    Subst none; none.index = -1;
+    const Subst none = no_subst();
     double d[3], o[3];
-    if (unproject<kNoncentral>(c, none, (double)((float)x + 0.5f), (double)((float)y + 0.5f), d, o)) {
+    if (unproject<kNoncentral>(c, none, pixel_center(x), pixel_center(y), d, o)) {
       const double t = d[0] * (cx - o[0]) + d[1] * (cy - o[1]) + d[2] * (cz - o[2]);
       off[0] = (o[0] + t * d[0]) - cx; off[1] = (o[1] + t * d[1]) - cy; off[2] = (o[2] + t * d[2]) - cz;
       ext = fmax(fmax(fabs(off[0]), fabs(off[1])), fabs(off[2]));
@@ -360,12 +332,7 @@ __global__ void __launch_bounds__(256) k_line_offsets(const CamDev* __restrict__
     offsets[3 * p] = off[0]; offsets[3 * p + 1] = off[1]; offsets[3 * p + 2] = off[2];
   }
   __shared__ double sh[256];
-  sh[threadIdx.x] = ext;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
-    __syncthreads();
-  }
+  block_reduce_256(ext, sh, MaxOp());
   if (threadIdx.x == 0) block_max[blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
 }
 // 127 + 127 * offset / max_extent, truncated (:920-923); NaN offsets are (0, 0, 0)
@@ -375,7 +342,7 @@ __global__ void __launch_bounds__(256) k_line_offset_colors(const double* __rest
   if (i >= n3) return;
   const int64_t p = i / 3;
   const double a = offsets[3 * p], b = offsets[3 * p + 1], cc = offsets[3 * p + 2];
-  rgb[i] = (a != a || b != b || cc != cc) ? 0 : wrap_u8(127 + 127 * offsets[i] / max_extent);
+  rgb[i] = (a != a || b != b || cc != cc) ? 0 : trunc_u8(127 + 127 * offsets[i] / max_extent);
 }
 int line_offset_blocks(int W, int H) { return ((W + kTileW - 1) / kTileW) * ((H + kTileH - 1) / kTileH); }
 int launch_line_offsets(const CamDev* cam_dev, int W, int H, const double* center, double* offsets, double* block_max, hipStream_t s) {

@@ -2,6 +2,7 @@
 //
 //  k_reduce_costs    cost sums and CostIsSmallerThan                           (lm_optimizer.h:993-1011)
 //  k_update_*        JointOptimizationState::operator-=                        (joint_optimization.cc:172-214)
+#include "block_device.hip.h"
 #include "obs_device.hip.h"
 
 namespace cba {
@@ -22,28 +23,13 @@ __global__ void __launch_bounds__(256) k_reduce_costs_partial(const double* __re
     if (flags && flags[i] == 1) acc[7] += 1;
   }
   __shared__ double sh[8][256];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) sh[k][threadIdx.x] = acc[k];
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
-    __syncthreads();
-  }
+  block_reduce_256(acc, sh, SumOp());
   if (threadIdx.x < 8) partials[blockIdx.x * 8 + threadIdx.x] = sh[threadIdx.x][0];
-}
-__global__ void k_reduce_costs_final(const double* __restrict__ partials, double* __restrict__ out8) {
-  int k = threadIdx.x;
-  if (k >= 8) return;
-  double s = 0;
-  for (int b = 0; b < kRedBlocks; ++b) s += partials[b * 8 + k];
-  out8[k] = s;
 }
 int launch_reduce_costs(const double* ref, const double* test, const uint8_t* flags, int64_t n, double* partials,
                         double* out8, hipStream_t s) {
   hipLaunchKernelGGL(k_reduce_costs_partial, dim3(kRedBlocks), dim3(256), 0, s, ref, test, flags, n, partials);
-  hipLaunchKernelGGL(k_reduce_costs_final, dim3(1), dim3(64), 0, s, partials, out8);
+  hipLaunchKernelGGL((k_fold_partials<8, kRedBlocks, SumOp>), dim3(1), dim3(64), 0, s, partials, out8);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

@@ -45,7 +45,12 @@ struct Subst {
   double d[3];
   double o[3];
 };
+__device__ __forceinline__ Subst no_subst() { Subst s; s.index = -1; return s; }
 
+// the quiet NaN a failed un-projection leaves in a per-pixel array
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+// centre of pixel x in the reference's types: `x + 0.5f` in fp32, widened
+__device__ __forceinline__ double pixel_center(int x) { return (double)((float)x + 0.5f); }
 __device__ __forceinline__ bool in_calibrated_area(const CamDev& c, double x, double y) {
   return x >= c.min_x && y >= c.min_y && x < c.max_x + 1 && y < c.max_y + 1;  // camera_model.h:159-162
 }

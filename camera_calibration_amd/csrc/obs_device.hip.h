@@ -1,5 +1,6 @@
 // Device helpers of the per-observation kernels that more than one unit uses (kernels_project.hip, kernels_fd.hip,
-// kernels_obs.hip, kernels_update.hip).  A helper with one user stays in that user's unit.
+// kernels_obs.hip, kernels_update.hip).  A helper with one user stays in that user's unit; the workgroup- and wavefront-level
+// idioms shared across stages (block reduction, partial fold, list append) are block_device.hip.h's.
 #pragma once
 #include "cba_internal.h"
 

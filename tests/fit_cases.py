@@ -3,7 +3,7 @@ seeded builders, no fixtures.  Every builder returns (cam, grid, grid_points, di
 whose calibrated area is the whole image.  tests/test_fit_cases.py proves with the oracle alone that each case is what its
 name says; tests/test_gpu_fit_edges.py runs the HIP fit on them.
 
-  keys_past_1024     40 x 32 grid: patch origins (bucket keys) up to 1156 -- the second chunk of k_fit_key_scan and its carry
+  keys_past_1024     40 x 32 grid: patch origins (bucket keys) up to 1156 -- the second chunk of k_exclusive_scan and its carry
   keys_exactly_1024  32 x 32 grid: 1024 keys, the scan's chunk loop ends exactly at the chunk boundary
   on_the_seams       samples on cell boundaries and on the last valid coordinate gp = gw - 3 (ix = gw - 1, fraction 3.0)
   one_bucket         1500 samples in one cell (one wavefront, a long serial loop; 32 of 48 control points are never reached)

@@ -1,4 +1,4 @@
-"""The cost reductions on the GPU (k_reduce_costs_partial / _final: the eight sums behind cba_cost, report.initial_cost,
+"""The cost reductions on the GPU (k_reduce_costs_partial / k_fold_partials: the eight sums behind cba_cost, report.initial_cost,
 n_residuals_valid, n_jacobians_dropped and the CostIsSmallerThan decision h[4] > 0 && h[3] < h[2]) against plain sums of the
 engine's own dumped cost vectors, on the problems of tests/update_cases.py: observation counts on both sides of the grid-stride
 boundary (256 blocks x 256 lanes), and LM attempts whose residuals are valid on one side only (shown on the CPU in

@@ -1,5 +1,5 @@
 """Edge inputs of the state update (k_update_poses, k_update_points, k_update_grid; cba_debug_apply_update) and of the cost
-reductions (k_reduce_costs_partial / _final) of kernels_update.hip: plain seeded builders, no fixtures.  tests/test_update_cases.py
+reductions (k_reduce_costs_partial / k_fold_partials) of kernels_update.hip: plain seeded builders, no fixtures.  tests/test_update_cases.py
 shows on the CPU that the cases contain what is said here and that the oracle meets tests/update_reference.py on them;
 tests/test_gpu_update_edges.py and tests/test_gpu_cost_reductions.py run the HIP kernels on them.
 

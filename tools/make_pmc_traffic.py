@@ -29,7 +29,7 @@ def stage_b(path, counter):
         if counter not in f:
             continue
         name = f[0]
-        if any(k in name for k in ("k_assemble", "k_accumulate", "k_cell_count", "k_cell_fill", "k_cell_scan", "k_strip_band_mask")):
+        if any(k in name for k in ("k_assemble", "k_accumulate", "k_cell_count", "k_cell_fill", "k_cell_scan", "k_exclusive_scan", "k_strip_band_mask")):
             i = f.index(counter)
             rows[name[:90]] = {"launches": int(f[i + 1]), "bytes_raw": float(f[i + 2]) * 1024.0}
     return rows

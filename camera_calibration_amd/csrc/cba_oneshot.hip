@@ -154,6 +154,71 @@ int cba_schur_solve_opt(int32_t block_size, int32_t n_blocks, int32_t dense_dof,
   return CBA_OK;
 }
 
+// Debug: the pose-first reduced system of posefirst_enqueue, launch for launch, from host arrays, UNFACTORED (tests/test_gpu_schur_product.py)
+int cba_debug_reduced_system(int32_t block_size, int32_t n_blocks, int32_t dense_dof, const double* block_diag_H,
+                             const double* off_diag_H, const double* dense_H, const double* block_diag_b, const double* dense_b,
+                             double lambda, int32_t mode, double* S_out, uint64_t* mask_out, int32_t dims[4], int32_t device) {
+  if (block_size < 1 || block_size > 6 || n_blocks < 1 || dense_dof < 1 || mode < 0 || mode > 2 || !dims) {
+    set_error("cba_debug_reduced_system: bad argument"); return CBA_ERR_ARG;
+  }
+  const int bs = block_size, nb = n_blocks, dd = dense_dof, bdof = bs * nb;
+  int n_pad, n_fact; padded_dims(dd, &n_pad, &n_fact);
+  const int ld = n_pad, Kpad = round_up(bdof, 48);          // as cba_create: a multiple of the dense K slab and of the block-sparse one
+  const int mask_tiles = n_pad / 128, mask_words = schur_mask_words(Kpad), n_chunks = schur_chunk_count(n_pad);
+  dims[0] = n_pad; dims[1] = Kpad; dims[2] = mask_words; dims[3] = n_chunks;
+  if (!S_out) return CBA_OK;
+  if (!block_diag_H || !off_diag_H || !dense_H || !block_diag_b || !dense_b) { set_error("cba_debug_reduced_system: bad argument"); return CBA_ERR_ARG; }
+  CBA_TRY(select_device(device, ""));
+  DevBuf<double> Dblk, bblk, Dinv, dinvb, B, W, Hdd, bd, S, gws; DevBuf<int> status, order; DevBuf<unsigned long long> kmask;
+  CBA_TRY(gws.alloc((size_t)gemv_t_workspace_doubles(n_pad)));
+  CBA_TRY(Dblk.alloc((size_t)nb * bs * bs)); CBA_TRY(bblk.alloc((size_t)bdof)); CBA_TRY(Dinv.alloc((size_t)nb * bs * bs));
+  CBA_TRY(dinvb.alloc((size_t)Kpad)); CBA_TRY(B.alloc((size_t)Kpad * ld)); CBA_TRY(W.alloc((size_t)Kpad * ld));
+  CBA_TRY(Hdd.alloc((size_t)ld * ld)); CBA_TRY(bd.alloc((size_t)ld)); CBA_TRY(S.alloc((size_t)ld * ld)); CBA_TRY(status.alloc(1));
+  CBA_TRY(kmask.alloc((size_t)mask_tiles * mask_words));
+  if (n_chunks > 0) CBA_TRY(order.alloc((size_t)n_chunks));
+  CBA_HIP(hipMemset(B, 0, sizeof(double) * (size_t)Kpad * ld)); CBA_HIP(hipMemset(W, 0, sizeof(double) * (size_t)Kpad * ld));
+  CBA_HIP(hipMemset(Hdd, 0, sizeof(double) * (size_t)ld * ld)); CBA_HIP(hipMemset(S, 0, sizeof(double) * (size_t)ld * ld));
+  CBA_HIP(hipMemset(bd, 0, sizeof(double) * ld)); CBA_HIP(hipMemset(status, 0, sizeof(int))); CBA_HIP(hipMemset(dinvb, 0, sizeof(double) * Kpad));
+  CBA_HIP(hipMemset(kmask, 0, sizeof(unsigned long long) * (size_t)mask_tiles * mask_words));
+  // upper triangles only, as cba_schur_solve_opt
+  std::vector<double> hD(block_diag_H, block_diag_H + (size_t)nb * bs * bs), hH((size_t)dd * dd);
+  for (int b = 0; b < nb; ++b)
+    for (int r = 0; r < bs; ++r)
+      for (int c = 0; c < r; ++c) hD[(size_t)b * bs * bs + r * bs + c] = 0.0;
+  for (int r = 0; r < dd; ++r)
+    for (int c = 0; c < dd; ++c) hH[(size_t)r * dd + c] = (c >= r) ? dense_H[(size_t)r * dd + c] : 0.0;
+  CBA_HIP(hipMemcpy(Dblk, hD.data(), sizeof(double) * hD.size(), hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(bblk, block_diag_b, sizeof(double) * bdof, hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy2D(B, ld * sizeof(double), off_diag_H, dd * sizeof(double), dd * sizeof(double), bdof, hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy2D(Hdd, ld * sizeof(double), hH.data(), dd * sizeof(double), dd * sizeof(double), dd, hipMemcpyHostToDevice));
+  CBA_HIP(hipMemcpy(bd, dense_b, sizeof(double) * dd, hipMemcpyHostToDevice));
+  hipStream_t s = nullptr;
+  std::vector<unsigned long long> hmask((size_t)mask_tiles * mask_words, 0ull);
+  const int* chunk_order = nullptr;
+  if (mode >= 1) {
+    CBA_TRY(launch_touch_mask(B, Kpad, n_pad, ld, kmask, s));              // (the engine: at the end of the Jacobian pass)
+    CBA_HIP(hipMemcpy(hmask.data(), kmask, sizeof(unsigned long long) * hmask.size(), hipMemcpyDeviceToHost));
+    if (mode == 2 && n_chunks > 0) {                                        // (the engine: posefirst_finish, from the pinned copy of the masks)
+      std::vector<int> horder((size_t)n_chunks);
+      schur_chunk_order(hmask.data(), n_pad, Kpad, horder.data());
+      CBA_HIP(hipMemcpy(order, horder.data(), sizeof(int) * (size_t)n_chunks, hipMemcpyHostToDevice));
+      chunk_order = order;
+    }
+  }
+  CBA_TRY(launch_block_inverse(Dblk, bblk, lambda, bs, nb, Dinv, dinvb, status, s));
+  CBA_TRY(launch_gemv_t_partial(B, bdof, dd, ld, dinvb, gws, s));
+  CBA_TRY(launch_gemv_t_final(dd, bd, S + (ld - 1), ld, gws, n_pad, s));
+  CBA_TRY(launch_dinv_times_B_ld(Dinv, B, bs, nb, dd, ld, W, s));
+  CBA_TRY(schur_gemm(B, W, Kpad, ld, Hdd, S, n_pad, ld, dd, 1, lambda, mode >= 1 ? (const unsigned long long*)kmask : nullptr, s, chunk_order, ld - 1));
+  CBA_HIP(hipDeviceSynchronize());
+  int st = 0;
+  CBA_HIP(hipMemcpy(&st, status, sizeof(int), hipMemcpyDeviceToHost));
+  CBA_HIP(hipMemcpy(S_out, S, sizeof(double) * (size_t)ld * ld, hipMemcpyDeviceToHost));
+  if (mask_out) std::memcpy(mask_out, hmask.data(), sizeof(unsigned long long) * hmask.size());   // mode 0: no masks are built, zeros
+  if (st) { set_error("cba_debug_reduced_system: zero pivot"); return CBA_ERR_NUMERIC; }
+  return CBA_OK;
+}
+
 int64_t cba_gridfirst_plan_query(const cba_camera* cameras, int32_t n_cameras, int32_t n_images, int32_t n_points, int32_t strips,
                                  int32_t single_tile_tasks, int32_t what, void* out, int64_t capacity_bytes) {
   GfPlan pl;

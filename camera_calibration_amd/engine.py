@@ -133,7 +133,7 @@ EXPORTED_SYMBOLS = [
     "cba_total_dof", "cba_dense_dof", "cba_jacobian_record_doubles", "cba_reduce_buffer_doubles",
     "cba_kernel_stats", "cba_fit_grid_to_directions", "cba_prepare_device",
     "cba_model_create", "cba_model_destroy", "cba_model_set_grid", "cba_model_project", "cba_model_unproject",
-    "cba_fd_redo_overflow", "cba_debug_fd_redo_counts", "cba_schur_solve_opt", "cba_set_fd_schedule",
+    "cba_fd_redo_overflow", "cba_debug_fd_redo_counts", "cba_schur_solve_opt", "cba_debug_reduced_system", "cba_set_fd_schedule",
     "cba_gridfirst_plan_query", "cba_elimination_order",
     "cba_model_direction_image", "cba_render_nearest_feature_image", "cba_model_center_point", "cba_model_line_offsets",
     "cba_debug_time_direction_image",
@@ -687,6 +687,34 @@ def schur_solve(block_diag_H: np.ndarray, off_diag_H: np.ndarray, dense_H: np.nd
     else:
         _check(L.cba_schur_solve(bs, nb, dd, _dp(bD), _dp(oH), _dp(dH), _dp(bb), _dp(db), _dp(x), device), "cba_schur_solve")
     return x
+
+
+def reduced_system(block_diag_H: np.ndarray, off_diag_H: np.ndarray, dense_H: np.ndarray, block_diag_b: np.ndarray,
+                   dense_b: np.ndarray, lam: float, mode: int, device: int = 0):
+    """cba_debug_reduced_system: the pose-first reduced system of these arrays, unfactored, formed by the engine's own launches.
+    mode 0 dense product, 1 block-sparse, 2 block-sparse with the chunk order.  Returns (S (n_pad, n_pad), upper triangle valid, last
+    column = right-hand side; mask (n_pad / 128, mask_words) uint64; dims = (n_pad, Kpad, mask_words, n_chunks))."""
+    L = load()
+    bD = np.ascontiguousarray(block_diag_H, dtype=np.float64)
+    nb, bs = bD.shape[0], bD.shape[1]
+    oH = np.ascontiguousarray(off_diag_H, dtype=np.float64)
+    dH = np.ascontiguousarray(dense_H, dtype=np.float64)
+    bb = np.ascontiguousarray(block_diag_b, dtype=np.float64)
+    db = np.ascontiguousarray(dense_b, dtype=np.float64)
+    dd = dH.shape[0]
+    assert oH.shape == (nb * bs, dd) and dH.shape == (dd, dd) and bb.size == nb * bs and db.size == dd
+    L.cba_debug_reduced_system.argtypes = ([C.c_int32] * 3 + [C.POINTER(C.c_double)] * 5 + [C.c_double, C.c_int32, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int32])
+    dims = np.zeros(4, dtype=np.int32)
+    ip = dims.ctypes.data_as(C.POINTER(C.c_int32))
+    _check(L.cba_debug_reduced_system(bs, nb, dd, None, None, None, None, None, float(lam), int(mode), None, None, ip, device),
+           "cba_debug_reduced_system")
+    n_pad, words = int(dims[0]), int(dims[2])
+    S = np.zeros((n_pad, n_pad))
+    mask = np.zeros((n_pad // 128, words), dtype=np.uint64)
+    _check(L.cba_debug_reduced_system(bs, nb, dd, _dp(bD), _dp(oH), _dp(dH), _dp(bb), _dp(db), float(lam), int(mode), _dp(S),
+                                      mask.ctypes.data_as(C.POINTER(C.c_uint64)), ip, device), "cba_debug_reduced_system")
+    return S, mask, tuple(int(v) for v in dims)
 
 
 # ---- host mirror of the reference entry point ---------------------------------------------------------

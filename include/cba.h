@@ -383,6 +383,15 @@ int cba_schur_solve(int32_t block_size, int32_t n_blocks, int32_t dense_dof, con
 int cba_schur_solve_opt(int32_t block_size, int32_t n_blocks, int32_t dense_dof, const double* block_diag_H,
                         const double* off_diag_H, const double* dense_H, const double* block_diag_b,
                         const double* dense_b, double* x, const cba_solver_options* options, int32_t device);
+/* Debug: forms the pose-first reduced system from caller-supplied arrays with the engine's own launches and returns it UNFACTORED.
+ * mode 0: dense product (no touch masks); 1: block-sparse, touch masks, no chunk order; 2: block-sparse with the chunk order derived
+ * from the masks (as the engine does after its first solve; the same as mode 1 where the launch is too small for chunks: n_chunks = 0).
+ * S: n_pad * n_pad, row-major, upper triangle valid; its last column holds the right-hand side.  S == NULL: only dims is filled.
+ * mask: optional, (n_pad / 128) * mask_words words, bit (tile, 12-row slab of off_diag_H) = the slab has a non-zero in the tile's 128
+ * columns (mode 0: zeros).  dims = n_pad, Kpad, mask_words, n_chunks.  A singular block: CBA_ERR_NUMERIC. */
+int cba_debug_reduced_system(int32_t block_size, int32_t n_blocks, int32_t dense_dof, const double* block_diag_H,
+                             const double* off_diag_H, const double* dense_H, const double* block_diag_b, const double* dense_b,
+                             double lambda, int32_t mode, double* S, uint64_t* mask, int32_t dims[4], int32_t device);
 
 /* ---- grid-only LM ---- */
 /* OptimizationReport of the fit + the optimizer's final lambda */

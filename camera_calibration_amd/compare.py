@@ -25,8 +25,15 @@ Defined where the reference is not: a pixel whose base un-projection succeeds an
 direction (255, 255, 255) and magnitude 255 (the reference reads an uninitialised direction and converts 255.99f * inf); a maximum
 of zero gives relative error / magnitude ratio 0, i.e. direction bytes 127 and magnitude bytes 0 (the reference divides by zero).
 
+* ``create_fitting_visualization`` -- ``--create_fitting_visualization`` (``CreateFittingVisualization``, APP/fitting_report.h:219-261,
+  APP/main.cc:397-406): for every central camera of a saved state, fit the thin-prism fisheye model plus a free rotation to the
+  camera's direction image (``parametric.fit_to_dense_model``, the image stays on the device) and write the six files for generic
+  versus fitted (``cba_model_compare_parametric``).  Non-central cameras are logged and skipped.  ``fit_fn`` and ``compare_fn`` are
+  injectable, so the file logic runs on the CPU.
+
 CLI: ``python -m camera_calibration_amd.compare --calibration_a A.yaml --calibration_b B.yaml --report_base_path out/cmp
-[--align_rotation]``.
+[--align_rotation]`` and ``python -m camera_calibration_amd.compare --create_fitting_visualization --state_directory DIR
+--report_base_path out/fit [--max_visualization_extent E] [--max_visualization_extent_pixels P]``.
 """
 from __future__ import annotations
 
@@ -266,15 +273,94 @@ def compare_calibrations(calibration_a: str, calibration_b: str, report_base_pat
     return res
 
 
+MSG_FITTING_ARGUMENTS = ("For the fitting visualization (--create_fitting_visualization), the state must be given with --state_directory "
+                         "and the output base path with --report_base_path.")
+MSG_NONCENTRAL = "Fitting visualization not supported for non-central camera with index "
+FITTING_SUBSAMPLE_STEP = 5                  # fitting_report.h:241
+
+
+def _fit_on_device(cam: Camera, grid: np.ndarray, device: int = 0):
+    from . import parametric
+    dm = _engine.DeviceModel(cam, grid, device)
+    try:
+        return parametric.fit_to_dense_model(dm, subsample_step=FITTING_SUBSAMPLE_STEP, device=device)
+    finally:
+        dm.close()
+
+
+def _compare_on_device(cam: Camera, grid: np.ndarray, model, rotation: np.ndarray, max_visualization_extent: float,
+                       max_visualization_extent_pixels: float, device: int = 0) -> dict:
+    dm = _engine.DeviceModel(cam, grid, device)
+    try:
+        return dm.compare_parametric(model, rotation, (0, 0), max_visualization_extent, max_visualization_extent_pixels)
+    finally:
+        dm.close()
+
+
+def create_fitting_visualization(state_directory: Optional[str] = None, report_base_path: str = "", max_visualization_extent: float = -1.0,
+                                 max_visualization_extent_pixels: float = -1.0, cameras=None, grids=None,
+                                 fit_fn: Optional[Callable] = None, compare_fn: Optional[Callable] = None, device: int = 0,
+                                 log: Callable = print) -> list:
+    """CreateFittingVisualization (APP/fitting_report.h:219-261) over the cameras of `state_directory` (LoadBAState) or over `cameras` /
+    `grids`.  Per central camera i: fit_fn(cam, grid) -> (ThinPrismFisheye of the camera's size with the equidistant step, rotation,
+    reports), compare_fn(cam, grid, model, rotation, extent, extent_pixels) -> the dict of fitting_errors, then the five PNGs and
+    `_fitting_info.txt` under `<report_base_path>_cam<i>_equidistant`.  The two extents are floats in the reference's command line and
+    are rounded to float here.  Returns one entry per camera: None for a skipped (non-central) one, else dict(model, rotation, reports,
+    base_path, result)."""
+    if cameras is None:
+        if not state_directory or not report_base_path:
+            raise ValueError(MSG_FITTING_ARGUMENTS)
+        from .calibration_io import load_ba_state
+        _, cameras, state, _ = load_ba_state(state_directory)
+        grids = state.grids
+    if not report_base_path:
+        raise ValueError(MSG_FITTING_ARGUMENTS)
+    extent = float(_F32(max_visualization_extent)); extent_pixels = float(_F32(max_visualization_extent_pixels))
+    fit_fn = fit_fn or (lambda cam, grid: _fit_on_device(cam, grid, device))
+    compare_fn = compare_fn or (lambda cam, grid, model, R, e, ep: _compare_on_device(cam, grid, model, R, e, ep, device))
+    out = []
+    for i, (cam, grid) in enumerate(zip(cameras, grids)):
+        if cam.model_type != CENTRAL_GENERIC:
+            log(MSG_NONCENTRAL + str(i))
+            out.append(None)
+            continue
+        model, R, reports = fit_fn(cam, grid)
+        base = f"{report_base_path}_cam{i}_equidistant"
+        res = compare_fn(cam, grid, model, R, extent, extent_pixels)
+        os.makedirs(os.path.dirname(os.path.abspath(base)), exist_ok=True)
+        for key, suffix in zip(IMAGE_KEYS, FILE_SUFFIXES):
+            write_png(base + suffix, res[key])
+        write_fitting_info_file(base + FILE_SUFFIXES[5], res, extent, extent_pixels)
+        out.append(dict(model=model, rotation=np.asarray(R, dtype=np.float64).reshape(3, 3), reports=reports, base_path=base, result=res))
+    return out
+
+
 def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m camera_calibration_amd.compare", description="Compare two central-generic calibrations.")
+    ap.add_argument("--create_fitting_visualization", action="store_true",
+                    help="fit a thin-prism fisheye model to every central camera of --state_directory and report generic versus fitted")
+    ap.add_argument("--state_directory", default="")
+    ap.add_argument("--max_visualization_extent", type=float, default=-1.0)
+    ap.add_argument("--max_visualization_extent_pixels", type=float, default=-1.0)
     ap.add_argument("--calibration_a", default="")
     ap.add_argument("--calibration_b", default="")
     ap.add_argument("--report_base_path", default="")
     ap.add_argument("--align_rotation", action="store_true", help="rotate calibration A onto B (least squares over the directions) first")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    if args.create_fitting_visualization:
+        try:
+            done = create_fitting_visualization(args.state_directory, args.report_base_path, args.max_visualization_extent,
+                                                args.max_visualization_extent_pixels, device=args.device)
+        except (ValueError, OSError, KeyError) as e:
+            print(e, file=sys.stderr)
+            return 1
+        for i, d in enumerate(done):
+            if d is not None:
+                print(f"camera {i} :", " ".join(_g14(v) for v in d["model"].parameters))
+                print(open(d["base_path"] + FILE_SUFFIXES[5]).read(), end="")
+        return 0
     try:
         res = compare_calibrations(args.calibration_a, args.calibration_b, args.report_base_path, args.align_rotation, device=args.device)
     except (ValueError, OSError, KeyError) as e:

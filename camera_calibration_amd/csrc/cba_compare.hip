@@ -51,33 +51,9 @@ CompareArgs make_args(const cba_model* base, const cba_model* fitted, const doub
   return a;
 }
 
-}  // namespace
-
-extern "C" {
-
-int cba_model_compare(cba_model* base, cba_model* fitted, const cba_compare_options* options, const cba_compare_outputs* outputs,
-                      cba_compare_stats* stats) {
-  if (!options || (!outputs && !stats)) { set_error("cba_model_compare: bad argument"); return CBA_ERR_ARG; }
-  CBA_TRY(check_pair(base, fitted, options->border_x, options->border_y, "cba_model_compare"));
-  if (options->initial_estimate != 0 && options->initial_estimate != 1) { set_error("cba_model_compare: unknown initial_estimate"); return CBA_ERR_ARG; }
-  const cba_compare_outputs none{};
-  const cba_compare_outputs& o = outputs ? *outputs : none;
-  CBA_HIP(hipSetDevice(fitted->device));
-  const int W = fitted->cam.width, H = fitted->cam.height;
-  const size_t n = (size_t)W * H;
-  CompareBuffers b;
-  CBA_TRY(b.alloc(n));
-  CompareArgs a = make_args(base, fitted, options->rotation, options->border_x, options->border_y, b);
-  a.init_mode = options->initial_estimate;
-  const int thr = options->straggler_threshold;
-  a.max_outer = thr == 0 ? kDefaultStragglerThreshold : (thr < 0 ? 0 : std::min(thr, 100));
-  a.do_project = 1;
-  CBA_HIP(hipMemsetAsync(b.count, 0, sizeof(int), nullptr));
-  CBA_TRY(launch_compare_pass(a, nullptr));
-  int n_list = 0;
-  CBA_HIP(hipMemcpy(&n_list, b.count, sizeof(int), hipMemcpyDeviceToHost));
-  if (n_list < 0 || (size_t)n_list > n) { set_error("cba_model_compare: pixel list corrupt"); return CBA_ERR_HIP; }
-  CBA_TRY(launch_compare_second(a, n_list, nullptr));
+// What follows the per-pixel pass: the reductions, the five images (:127-178), the copies and the statistics (:192-200)
+int compare_finish(const cba_compare_options* options, const cba_compare_outputs& o, cba_compare_stats* stats, CompareBuffers& b, size_t n,
+                   int n_list) {
   CBA_TRY(launch_compare_reduce((int64_t)n, b.flags, b.err, b.reproj, b.fit_dir, b.base_dir, false, b.partials, b.sums, nullptr));
   double h[kCompareSums];
   CBA_HIP(hipMemcpy(h, b.sums, sizeof(h), hipMemcpyDeviceToHost));
@@ -127,6 +103,64 @@ int cba_model_compare(cba_model* base, cba_model* fitted, const cba_compare_opti
     }
   }
   return CBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cba_model_compare(cba_model* base, cba_model* fitted, const cba_compare_options* options, const cba_compare_outputs* outputs,
+                      cba_compare_stats* stats) {
+  if (!options || (!outputs && !stats)) { set_error("cba_model_compare: bad argument"); return CBA_ERR_ARG; }
+  CBA_TRY(check_pair(base, fitted, options->border_x, options->border_y, "cba_model_compare"));
+  if (options->initial_estimate != 0 && options->initial_estimate != 1) { set_error("cba_model_compare: unknown initial_estimate"); return CBA_ERR_ARG; }
+  const cba_compare_outputs none{};
+  const cba_compare_outputs& o = outputs ? *outputs : none;
+  CBA_HIP(hipSetDevice(fitted->device));
+  const int W = fitted->cam.width, H = fitted->cam.height;
+  const size_t n = (size_t)W * H;
+  CompareBuffers b;
+  CBA_TRY(b.alloc(n));
+  CompareArgs a = make_args(base, fitted, options->rotation, options->border_x, options->border_y, b);
+  a.init_mode = options->initial_estimate;
+  const int thr = options->straggler_threshold;
+  a.max_outer = thr == 0 ? kDefaultStragglerThreshold : (thr < 0 ? 0 : std::min(thr, 100));
+  a.do_project = 1;
+  CBA_HIP(hipMemsetAsync(b.count, 0, sizeof(int), nullptr));
+  CBA_TRY(launch_compare_pass(a, nullptr));
+  int n_list = 0;
+  CBA_HIP(hipMemcpy(&n_list, b.count, sizeof(int), hipMemcpyDeviceToHost));
+  if (n_list < 0 || (size_t)n_list > n) { set_error("cba_model_compare: pixel list corrupt"); return CBA_ERR_HIP; }
+  CBA_TRY(launch_compare_second(a, n_list, nullptr));
+  return compare_finish(options, o, stats, b, n, n_list);
+}
+
+int cba_model_compare_parametric(cba_model* base, const cba_parametric_camera* fitted, const cba_compare_options* options,
+                                 const cba_compare_outputs* outputs, cba_compare_stats* stats) {
+  if (!base || !fitted || !options || (!outputs && !stats)) { set_error("cba_model_compare_parametric: bad argument"); return CBA_ERR_ARG; }
+  if (base->cam.model_type != CBA_CENTRAL_GENERIC) {               // the reference skips such cameras (fitting_report.h:229-232)
+    set_error("cba_model_compare_parametric: needs a central-generic base model"); return CBA_ERR_ARG;
+  }
+  const int W = fitted->width, H = fitted->height;
+  if (W < 1 || H < 1 || (int64_t)W * H > (int64_t)1 << 28) { set_error("cba_model_compare_parametric: bad image size"); return CBA_ERR_ARG; }
+  if ((int64_t)base->cam.width - 2 * (int64_t)options->border_x != W || (int64_t)base->cam.height - 2 * (int64_t)options->border_y != H) {
+    set_error("cba_model_compare_parametric: base size minus twice the border differs from the fitted size"); return CBA_ERR_ARG;
+  }
+  const cba_compare_outputs none{};
+  const cba_compare_outputs& o = outputs ? *outputs : none;
+  CBA_HIP(hipSetDevice(base->device));
+  const size_t n = (size_t)W * H;
+  CompareBuffers b;
+  CBA_TRY(b.alloc(n));
+  CompareParametricArgs a{};
+  a.base = base->d_cam;
+  a.fitted.width = W; a.fitted.height = H; a.fitted.equidistant = fitted->use_equidistant_projection ? 1 : 0;
+  std::memcpy(a.fitted.p, fitted->parameters, sizeof(a.fitted.p));
+  for (int k = 0; k < 9; ++k) a.R[k] = options->rotation[k];
+  a.border_x = options->border_x; a.border_y = options->border_y; a.W = W; a.H = H;
+  a.base_dir = b.base_dir; a.fit_dir = b.fit_dir; a.err = b.err; a.reproj = b.reproj; a.flags = b.flags;
+  CBA_TRY(launch_compare_parametric(a, nullptr));
+  return compare_finish(options, o, stats, b, n, 0);               // no iterative projection: nothing for a second launch
 }
 
 int cba_model_direction_moments(cba_model* base, cba_model* fitted, int32_t border_x, int32_t border_y, double M[9], int64_t* n_out) {

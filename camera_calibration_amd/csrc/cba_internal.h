@@ -303,6 +303,43 @@ struct CompareColorArgs {
 static_assert(std::is_trivially_copyable_v<CompareColorArgs>);
 int launch_compare_colors(const CompareColorArgs& c, hipStream_t s);
 
+// ---- kernels_parametric.hip (thin-prism fisheye model and its fit to a dense direction image, APP/models/parametric.cc) ----
+struct ParVec { double v[12]; };                       // fx fy cx cy k1 k2 k3 k4 p1 p2 sx1 sy1
+struct ParDirection { double x, y, z; int ok; };
+struct ParPixel { double x, y; int ok; };
+struct ParCam { int width, height, equidistant, reserved; double p[12]; };
+static_assert(sizeof(ParCam) == sizeof(cba_parametric_camera), "ParCam mirrors cba_parametric_camera");
+// A pass of the fit over the samples x, y = 0, step, 2 step, ... of the dense image (nsx * nsy of them, row by row).  cost: 3 slots
+// per sample (0.5 r^2, -1 = invalid or no target); flags per sample: bit 0 target used, bit 1 base un-projection ok, bit 2 every
+// perturbed un-projection ok (Jacobian pass only).  R: row-major; q = (w, x, y, z) of R (read with allow_rotation).
+struct ParFitArgs {
+  ParCam cam;
+  const double* dense; int dense_w, dense_h, step, nsx, nsy;
+  int has_rotation, allow_rotation;
+  double R[9], q[4], delta;
+  double* cost; uint8_t* flags;
+};
+static_assert(std::is_trivially_copyable_v<ParFitArgs>);
+int launch_parametric_unproject(const ParCam& c, int64_t n, const double* pixels, double* dirs, uint8_t* ok, hipStream_t s);
+int launch_parametric_project(const ParCam& c, int64_t n, const double* points, double* pixels, uint8_t* ok, hipStream_t s);
+// partials: parametric_partials_doubles(); sums: 240 doubles, [row * 16 + c] = H[row][c] for c < 15 (all columns), [row * 16 + 15] = b[row]
+int parametric_partials_doubles();
+int launch_parametric_jacobian(const ParFitArgs& a, double* partials, double* sums, hipStream_t s);
+int launch_parametric_cost(const ParFitArgs& a, hipStream_t s);
+// sums: 30 doubles, per axis the upper triangle of sum v v^T (10), sum v * pixel (4), rows (1); v = (n, n r^2, n r^4, 1)
+int launch_parametric_linear(const double* dense, int dw, int dh, int width, int height, int equidistant, double* partials,
+                             double* sums, hipStream_t s);
+
+// per-pixel pass of a central-generic base model against a thin-prism fisheye model: the arrays of CompareArgs, W x H = the fitted image
+struct CompareParametricArgs {
+  const CamDev* base; ParCam fitted;
+  double R[9];
+  int border_x, border_y, W, H;
+  double* base_dir; double* fit_dir; double* err; double* reproj; uint8_t* flags;
+};
+static_assert(std::is_trivially_copyable_v<CompareParametricArgs>);
+int launch_compare_parametric(const CompareParametricArgs& a, hipStream_t s);
+
 // ---- kernels_localize.hip (localization accuracy test, APP/tools/localization_accuracy_test.cc:47-131) ----
 // Trials first_trial .. first_trial + n_trials - 1, one per 16-lane group.  Per-trial arrays are indexed by the trial's position in
 // the launch; points / bearings (3 P doubles per trial) are the kernel's own staging and always set, the other arrays may be null.

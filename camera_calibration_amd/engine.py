@@ -65,6 +65,16 @@ class CbaFitReport(C.Structure):
                 ("iterations_performed", C.c_int32), ("lm_attempts", C.c_int32), ("t_pass", C.c_double), ("t_solve", C.c_double)]
 
 
+class CbaParametricCamera(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("use_equidistant_projection", C.c_int32), ("reserved", C.c_int32),
+                ("parameters", C.c_double * 12)]
+
+
+class CbaParametricFitOptions(C.Structure):
+    _fields_ = [("subsample_step", C.c_int32), ("max_iteration_count", C.c_int32), ("max_lm_attempts", C.c_int32),
+                ("allow_rotation", C.c_int32), ("n_deltas", C.c_int32), ("reserved", C.c_int32), ("deltas", C.c_double * 8)]
+
+
 class CbaCompareOptions(C.Structure):
     _fields_ = [("rotation", C.c_double * 9), ("border_x", C.c_int32), ("border_y", C.c_int32),
                 ("max_visualization_extent", C.c_double), ("max_visualization_extent_pixels", C.c_double),
@@ -138,6 +148,8 @@ EXPORTED_SYMBOLS = [
     "cba_model_direction_image", "cba_render_nearest_feature_image", "cba_model_center_point", "cba_model_line_offsets",
     "cba_debug_time_direction_image",
     "cba_model_compare", "cba_model_direction_moments", "cba_model_localization_accuracy",
+    "cba_parametric_project", "cba_parametric_unproject", "cba_parametric_fit_pass", "cba_fit_parametric_to_dense_model",
+    "cba_model_compare_parametric",
 ]
 
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
@@ -212,6 +224,12 @@ def load() -> C.CDLL:
     L.cba_model_center_point.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     L.cba_model_line_offsets.argtypes = [vp, dp, dp, u8p, dp]
     L.cba_debug_time_direction_image.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp]
+    pc = C.POINTER(CbaParametricCamera)
+    L.cba_parametric_project.argtypes = [pc, C.c_int64, dp, dp, u8p, C.c_int32]
+    L.cba_parametric_unproject.argtypes = [pc, C.c_int64, dp, dp, u8p, C.c_int32]
+    L.cba_parametric_fit_pass.argtypes = [pc, dp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, dp, u8p, dp, dp, dp, dp, C.c_int32]
+    L.cba_fit_parametric_to_dense_model.argtypes = [pc, dp, C.c_int32, C.c_int32, vp, C.POINTER(CbaParametricFitOptions), dp,
+                                                    C.POINTER(CbaFitReport), C.c_int32]
     _lib = L
     return L
 
@@ -557,7 +575,24 @@ class DeviceModel:
                 straggler_threshold: int = 0, want_arrays: bool = True, want_images: bool = True) -> dict:
         """cba_model_compare with this model as the base: the per-pixel arrays ((H, W[, k]) of the fitted model's image), the five
         images and the statistics, in one dict.  reprojection_error_median is None when nothing projected."""
-        H, W = fitted.cam.height, fitted.cam.width
+        return self._compare(fitted.cam.width, fitted.cam.height, rotation, border, max_visualization_extent, max_visualization_extent_pixels,
+                             initial_estimate, straggler_threshold, want_arrays, want_images,
+                             lambda o, out, st: _check(self.L.cba_model_compare(self._h, fitted._h, o, out, st), "cba_model_compare"))
+
+    def compare_parametric(self, fitted, rotation: Optional[np.ndarray] = None, border=(0, 0), max_visualization_extent: float = -1.0,
+                           max_visualization_extent_pixels: float = -1.0, want_arrays: bool = True, want_images: bool = True) -> dict:
+        """cba_model_compare_parametric with this model as the base and a ``parametric.ThinPrismFisheye`` as the fitted model: the
+        dict of ``compare`` (n_second_launch is 0: the fitted model projects in closed form)."""
+        cs = fitted.struct()
+        self.L.cba_model_compare_parametric.argtypes = [C.c_void_p, C.POINTER(CbaParametricCamera), C.POINTER(CbaCompareOptions),
+                                                        C.POINTER(CbaCompareOutputs), C.POINTER(CbaCompareStats)]
+        return self._compare(int(fitted.width), int(fitted.height), rotation, border, max_visualization_extent, max_visualization_extent_pixels,
+                             INITIAL_ESTIMATE_CENTER, 0, want_arrays, want_images,
+                             lambda o, out, st: _check(self.L.cba_model_compare_parametric(self._h, C.byref(cs), o, out, st),
+                                                       "cba_model_compare_parametric"))
+
+    def _compare(self, W, H, rotation, border, max_visualization_extent, max_visualization_extent_pixels, initial_estimate,
+                 straggler_threshold, want_arrays, want_images, call) -> dict:
         o = CbaCompareOptions()
         o.rotation[:] = list(np.asarray(np.eye(3) if rotation is None else rotation, dtype=np.float64).reshape(9))
         o.border_x, o.border_y = int(border[0]), int(border[1])
@@ -575,7 +610,7 @@ class DeviceModel:
         st = CbaCompareStats()
         self.L.cba_model_compare.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CbaCompareOptions), C.POINTER(CbaCompareOutputs),
                                              C.POINTER(CbaCompareStats)]
-        _check(self.L.cba_model_compare(self._h, fitted._h, C.byref(o), C.byref(out), C.byref(st)), "cba_model_compare")
+        call(C.byref(o), C.byref(out), C.byref(st))
         for name, _ in CbaCompareStats._fields_:
             res[name] = getattr(st, name)
         res["reprojection_error_median"] = st.reprojection_error_median if st.has_median else None

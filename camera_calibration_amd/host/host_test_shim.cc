@@ -261,6 +261,24 @@ extern "C" int cba_host_compare_calibrations(const char* calibration_a, const ch
   return CompareCalibrations(calibration_a, calibration_b, report_base_path);
 }
 
+// vis::CreateFittingVisualization (fitting_report.h) on a saved state directory; parameters / rotations (optional): 12 / 9 doubles per
+// camera (untouched for a skipped camera), fitted (optional): one byte per camera
+extern "C" int cba_host_create_fitting_visualization(const char* state_directory, const char* report_base_path, float max_visualization_extent,
+                                                     float max_visualization_extent_pixels, int max_cameras, double* parameters,
+                                                     double* rotations, uint8_t* fitted) {
+  BAState state;
+  if (!LoadBAState(state_directory, &state, nullptr)) return -1;
+  std::vector<FittingVisualizationResult> results;
+  if (CreateFittingVisualization(state, report_base_path, max_visualization_extent, max_visualization_extent_pixels, &results) != EXIT_SUCCESS) return -2;
+  for (int c = 0; c < (int)results.size() && c < max_cameras; ++c) {
+    if (fitted) fitted[c] = results[c].fitted ? 1 : 0;
+    if (!results[c].fitted) continue;
+    if (parameters) std::copy(results[c].model.parameters, results[c].model.parameters + 12, parameters + 12 * c);
+    if (rotations) std::copy(&results[c].parametric_r_dense.m[0][0], &results[c].parametric_r_dense.m[0][0] + 9, rotations + 9 * c);
+  }
+  return (int)results.size();
+}
+
 // vis::LocalizationAccuracyTest (localization_accuracy.h) on two calibration files with explicit options
 extern "C" int cba_host_localization_accuracy_test(const char* gt_model, const char* compared_model, const cba_localization_options* options,
                                                    cba_localization_stats* stats) {

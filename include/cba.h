@@ -414,6 +414,66 @@ typedef struct {
 int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n, const double* grid_points,
                                const double* directions, int32_t max_iteration_count, cba_fit_report* report, int32_t device);
 
+/* ---- thin-prism fisheye model fitted to a dense direction image ---- */
+/* CentralThinPrismFisheyeModel (APP/models/central_thin_prism_fisheye.cc).  The model lives outside cba_camera / cba_problem: it is
+ * fitted to a calibration, never bundle-adjusted. */
+typedef struct {
+  int32_t width, height;
+  int32_t use_equidistant_projection;
+  int32_t reserved;
+  double parameters[12];                 /* fx fy cx cy k1 k2 k3 k4 p1 p2 sx1 sy1 */
+} cba_parametric_camera;
+/* Project (:59-113), batched: pixels 2n, ok n (z > 0 and the pixel inside the image; the pixel is NaN for z <= 0).
+ * Unproject (:153-169 over UnprojectWithGaussNewton, APP/models/parametric.h:60-148), batched: directions 3n (unit; NaN where the
+ * Gauss-Newton does not converge), ok n.
+ * DEVIATION from the reference: the equidistant step of Unproject (theta, its sine and cosine) is evaluated in fp64.  The reference
+ * evaluates it with sqrtf / sinf / cosf, which quantises the direction to ~6e-8; divided by the finite-difference step of the fit
+ * (down to 1e-5) that is noise of the size of the derivatives themselves.  Everything else follows the reference term by term. */
+int cba_parametric_project(const cba_parametric_camera* camera, int64_t n, const double* local_points, double* pixels, uint8_t* ok,
+                           int32_t device);
+int cba_parametric_unproject(const cba_parametric_camera* camera, int64_t n, const double* pixels, double* directions, uint8_t* ok,
+                             int32_t device);
+/* Debug: ONE pass of the fit's cost function (ParametricDirectionCostFunction, APP/models/parametric.cc:68-194) at caller-given
+ * parameters (camera), rotation (row-major, NULL = no rotation at all: 12 columns), delta and step over the dense image (3 dense_width
+ * dense_height doubles, NaN = no direction).  jacobian != 0: Compute<true>; 0: Compute<false> (H and b are not written).
+ * The samples are x, y = 0, step, ... row by row, n = ceil(dense_width / step) ceil(dense_height / step) of them; every output may
+ * be NULL.  cost_vector: 3n slots, 0.5 r^2, -1 for an invalid residual and for a sample without target (the reference has no slot
+ * for those); flags: n bytes, bit 0 = target used, bit 1 = base un-projection ok, bit 2 = every perturbed un-projection ok (Jacobian
+ * pass only); H: 15 x 15 row-major, upper triangle, the rest zero; b: 15; cost: the sum of the valid slots;
+ * linear_sums: 30 doubles of the linear start (per axis: upper triangle of the 4 x 4 normal matrix (10), right-hand side (4), rows). */
+int cba_parametric_fit_pass(const cba_parametric_camera* camera, const double* rotation, const double* dense, int32_t dense_width,
+                            int32_t dense_height, int32_t step, double delta, int32_t jacobian, double* cost_vector, uint8_t* flags,
+                            double* H, double* b, double* cost, double* linear_sums, int32_t device);
+typedef struct {                         /* 0 selects the default of every member but allow_rotation */
+  int32_t subsample_step;                /* 5 */
+  int32_t max_iteration_count;           /* 300, per stage */
+  int32_t max_lm_attempts;               /* 10 */
+  int32_t allow_rotation;                /* 1: the 15-column fit of FitToDenseModel(dense, &R, ...); 0: the 12-column one */
+  int32_t n_deltas;                      /* stages; 0 = the reference's four, {1e-2, 1e-3, 1e-4, 1e-5} */
+  int32_t reserved;
+  double deltas[8];
+} cba_parametric_fit_options;
+/* ParametricCameraModel::FitToDenseModel (APP/models/parametric.cc:427-494): the linear start (:197-319; fewer than 4 usable rows:
+ * CBA_ERR_NUMERIC), then one LMOptimizer::Optimize per delta (init_lambda_factor = 0.001f, lambda re-initialised per stage, x 0.5 on
+ * accept, x 2 on reject, a NaN update rejects; LV/lm_optimizer.h:629-990) with the passes on the device and the 15 x 15 solve and the
+ * state update (ParametricStateWrapper::operator-=, with the float norm / sine / cosine of ApplyLocalUpdateToQuaternion) on the host.
+ * The dense image is either `dense` (host, 3 dense_width dense_height doubles, NaN = no direction) or, with dense == NULL, the
+ * direction image of `dense_model` (central-generic; rendered and kept on the device, dense_width / dense_height ignored).
+ * camera: width, height, use_equidistant_projection in, parameters out.  rotation: 9 doubles out, row-major (identity at the start, as
+ * CreateFittingVisualization; identity without allow_rotation).  reports: one per stage (n_deltas of them), may be NULL. */
+int cba_fit_parametric_to_dense_model(cba_parametric_camera* camera, const double* dense, int32_t dense_width, int32_t dense_height,
+                                      cba_model* dense_model, const cba_parametric_fit_options* options, double* rotation,
+                                      cba_fit_report* reports, int32_t device);
+
+/* CreateFittingErrorReport<CentralGenericModel, CentralThinPrismFisheyeModel> (APP/fitting_report.h:55-203), the per-pixel pass of
+ * CreateFittingVisualization (:219-261): cba_model_compare with a thin-prism fisheye model as the fitted one.  Options, outputs,
+ * statistics and the defined-where-the-reference-is-not rules are those of cba_model_compare; W, H = fitted->width, fitted->height;
+ * options->initial_estimate and straggler_threshold are not read (the fitted model projects in closed form) and n_second_launch is 0.
+ * CBA_ERR_ARG: a base that is not central-generic (the reference skips such cameras), base size minus twice the border differs from
+ * the fitted size. */
+int cba_model_compare_parametric(cba_model* base, const cba_parametric_camera* fitted, const cba_compare_options* options,
+                                 const cba_compare_outputs* outputs, cba_compare_stats* stats);
+
 /* ---- parity/debug access (read-only views of the last cba_step / cba_debug_* call) ---- */
 enum {
   CBA_DUMP_COST_VECTOR = 1,      /* n doubles: Jacobian-pass residual costs (-1 invalid) */

@@ -10,8 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcalib_ba_hip.so")
 SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip", "cba_report.hip", "cba_compare.hip",
-           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "cba_localize.hip", "kernels_localize.hip", "cba_parametric.hip", "kernels_parametric.hip"]
-HEADERS = ["cba_internal.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "block_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
+           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip"]
+HEADERS = ["cba_internal.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "block_device.hip.h", "localize_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]  # keep MFMA accumulators in VGPRs: no AGPR<->VGPR copies in the K loop
 
@@ -69,6 +69,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     check_no_scratch(os.path.join(CSRC, "kernels_report.o"), NO_SCRATCH_KERNELS)
     check_no_scratch(os.path.join(CSRC, "kernels_localize.o"), NO_SCRATCH_LOCALIZE)
     check_no_scratch(os.path.join(CSRC, "kernels_parametric.o"), NO_SCRATCH_PARAMETRIC)
+    check_no_scratch(os.path.join(CSRC, "kernels_localize_images.o"), NO_SCRATCH_LOCALIZE_IMAGES)
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
     with open(FLAGS_STAMP, "w") as f:
         f.write(_extra_flags())
@@ -124,6 +125,8 @@ def kernel_resources(obj: str) -> dict:
 NO_SCRATCH_KERNELS = ("k_direction_image", "k_nearest_site", "k_clip_cells")
 # the localization accuracy test keeps its 28 fp64 sums, the 3 x 6 Jacobian and the 6 x 6 factor in registers
 NO_SCRATCH_LOCALIZE = ("k_localize",)
+# the localization of images keeps the same sums, and a hypothesis' quartic, depths and pose, in registers
+NO_SCRATCH_LOCALIZE_IMAGES = ("k_localize_images", "k_localize_bearings")
 # the passes of the thin-prism fisheye fit call one un-projection that is not inlined: its twelve parameters and a lane's row of H
 # stay in registers
 NO_SCRATCH_PARAMETRIC = ("k_parametric_jacobian", "k_parametric_cost", "k_parametric_unproject")
@@ -198,12 +201,12 @@ def _check_kernel_m0(asm: str, kernel: str, obj: str) -> int:
 
 HOST_DIR = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HERE, "libcalib_ba_host.so")
-HOST_SOURCES = ["joint_optimization_hip.cc", "calibration_report_hip.cc", "calibration_io.cc", "central_generic_fit_hip.cc", "calibration_hip.cc", "fitting_report_hip.cc", "localization_accuracy_hip.cc"]
+HOST_SOURCES = ["joint_optimization_hip.cc", "calibration_report_hip.cc", "calibration_io.cc", "central_generic_fit_hip.cc", "calibration_hip.cc", "fitting_report_hip.cc", "localization_accuracy_hip.cc", "image_localization_hip.cc"]
 # test scaffolding (extern "C" entry points that build Dataset / BAState objects from packed arrays for the Python tests):
 # its own library, NOT part of the product library
 HOST_TEST_LIB = os.path.join(HERE, "libcalib_ba_host_test.so")
 HOST_TEST_SOURCES = ["host_test_shim.cc"]
-HOST_HEADERS = ["vis_types.h", "camera_model.h", "dataset.h", "joint_optimization.h", "fitting_report.h", "localization_accuracy.h"]
+HOST_HEADERS = ["vis_types.h", "camera_model.h", "dataset.h", "joint_optimization.h", "fitting_report.h", "localization_accuracy.h", "image_localization.h"]
 
 
 def build_host(force: bool = False) -> str:

@@ -355,6 +355,26 @@ struct LocalizeArgs {
 static_assert(std::is_trivially_copyable_v<LocalizeArgs>);
 int launch_localize(const LocalizeArgs& a, hipStream_t s);
 
+// ---- kernels_localize_images.hip (localization of a dataset's images, APP/calibration_initialization/dense_initialization.cc:293-405) ----
+// Slot i holds the features feature_start[i] .. feature_start[i + 1] - 1.  bearings / valid / list / in_fit (per feature) are the
+// kernels' own staging and always set; the per-slot arrays, samples (n_slots x n_hypotheses x 4), hypothesis_poses and start_poses
+// (12 per slot: R row-major, c) may be null.
+struct LocalizeImagesArgs {
+  const CamDev* const* models; const int* model_size /* width, height per model */; const int* slot_model; const unsigned long long* slot_id; const int* feature_start; const int* feature_slot;
+  const float* pixels; const double* points; const uint8_t* candidate; const double* start_poses;
+  int n_slots, n_features;
+  unsigned long long seed;
+  double threshold;
+  int bearing_mode, n_hypotheses, min_calibrated_match_count, min_inliers, refine_set, max_iterations;
+  double* bearings; uint8_t* valid; int* list; uint8_t* in_fit;
+  int* samples; double* hypothesis_poses;
+  double* poses; uint8_t* flags; int* match_count; int* list_length; int* best_hypothesis; int* best_inliers;
+  int* inliers_after_refinement; int* iterations; double* final_cost;
+};
+static_assert(std::is_trivially_copyable_v<LocalizeImagesArgs>);
+// stage A over the features, then stage B over the slots, on stream s
+int launch_localize_images(const LocalizeImagesArgs& a, hipStream_t s);
+
 // ---- kernels_linalg.hip (Schur stage, the fp64 MFMA GEMM, pack / diagonal kernels) ----
 // Inverse of the (bs x bs) diagonal blocks with lambda added, and Dinv*b.
 int launch_block_inverse(const double* Dblk, const double* bblk, double lambda, int bs, int nb, double* Dinv,

@@ -16,103 +16,11 @@
 // group reads only its own lanes (the ballot is masked, the butterfly stays inside the row), no atomics, no waits between
 // workgroups: a trial's results depend on (models, options, t) only.
 #include "cba_internal.h"
+#include "localize_device.hip.h"
 
 namespace cba {
 
 constexpr int kLocBlock = 256;      // 16 trials
-
-__device__ __forceinline__ unsigned long long localize_mix(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// v of the lane a DPP control selects, within the lane's row of 16
-template <int CTRL>
-__device__ __forceinline__ double row_move(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-// sum over the 16 lanes of a row, the same bits in every lane; all 64 lanes must be active
-__device__ __forceinline__ double row_sum(double v) {
-  v += row_move<0xB1>(v);       // quad_perm [1, 0, 3, 2]
-  v += row_move<0x4E>(v);       // quad_perm [2, 3, 0, 1]
-  v += row_move<0x141>(v);      // row_half_mirror
-  v += row_move<0x140>(v);      // row_mirror
-  return v;
-}
-
-// R = Rb exp(s w), c = cb + s d, (w, d) = step
-__device__ __forceinline__ void localize_apply(const double* Rb, const double* cb, double s, const double* step, double* R, double* c) {
-  const double w0 = s * step[0], w1 = s * step[1], w2 = s * step[2];
-  const double th2 = w0 * w0 + w1 * w1 + w2 * w2;
-  double A = 1.0, B = 0.5;
-  if (th2 >= 1e-20) {
-    const double th = sqrt(th2), sh = sin(0.5 * th);
-    A = sin(th) / th;
-    B = 2.0 * sh * sh / th2;
-  }
-  // exp(w) = I + A [w]x + B ([w]x)^2, ([w]x)^2 = w w^T - |w|^2 I
-  const double E[9] = {1.0 + B * (w0 * w0 - th2), B * w0 * w1 - A * w2, B * w0 * w2 + A * w1,
-                       B * w0 * w1 + A * w2, 1.0 + B * (w1 * w1 - th2), B * w1 * w2 - A * w0,
-                       B * w0 * w2 - A * w1, B * w1 * w2 + A * w0, 1.0 + B * (w2 * w2 - th2)};
-  double out[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) out[3 * r + q] = Rb[3 * r] * E[q] + Rb[3 * r + 1] * E[3 + q] + Rb[3 * r + 2] * E[6 + q];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) R[k] = out[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) c[k] = cb[k] + s * step[3 + k];
-}
-
-// x of H x = -g by LDL^T; acc = the upper triangle of H row by row (21), then g (6).  false: a pivot that is not positive
-__device__ __forceinline__ bool localize_solve(const double* acc, double* x) {
-  double L[6][6], D[6];
-  {
-    int q = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = i; j < 6; ++j) L[j][i] = acc[q++];      // lower triangle: L[j][i] = H[i][j]
-  }
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = L[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k] * D[k];
-    if (!(d > 0)) ok = false;
-    D[j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double v = L[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k] * D[k];
-      L[i][j] = v / d;
-    }
-  }
-  double z[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double v = -acc[21 + i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= L[i][k] * z[k];
-    z[i] = v;
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double v = z[i] / D[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
-    x[i] = v;
-  }
-  return ok;
-}
 
 __global__ void __launch_bounds__(kLocBlock) k_localize(LocalizeArgs a) {
   const int lane = threadIdx.x & 63, gl = lane & 15, shift = lane & 48;      // shift: first lane of the group

@@ -127,6 +127,35 @@ class CbaLocalizationStats(C.Structure):
 LOCALIZATION_DEFAULTS = dict(n_trials=10000, point_count=15, min_distance=1.5, max_distance=2.5, max_iterations=50)
 
 
+class CbaLocalizeImagesOptions(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("threshold", C.c_double), ("bearing_mode", C.c_int32), ("n_hypotheses", C.c_int32),
+                ("min_calibrated_match_count", C.c_int32), ("min_inliers", C.c_int32), ("refine_set", C.c_int32),
+                ("max_iterations", C.c_int32)]
+
+
+class CbaLocalizeImagesInput(C.Structure):
+    _fields_ = [("n_slots", C.c_int64), ("n_features", C.c_int64), ("n_models", C.c_int32), ("reserved", C.c_int32),
+                ("models", C.POINTER(C.c_void_p)), ("slot_id", C.c_void_p), ("slot_model", C.c_void_p), ("feature_start", C.c_void_p),
+                ("pixels", C.c_void_p), ("points", C.c_void_p), ("candidate", C.c_void_p), ("start_poses", C.c_void_p)]
+
+
+# (name, per "slot" / "feature", trailing shape with H = the hypothesis count, dtype) of cba_localize_images_outputs, in its order
+LOCALIZE_IMAGES_ARRAYS = (("image_tr_global", "slot", (7,), np.float64), ("flags", "slot", (), np.uint8),
+                          ("match_count", "slot", (), np.int32), ("list_length", "slot", (), np.int32),
+                          ("best_hypothesis", "slot", (), np.int32), ("best_inliers", "slot", (), np.int32),
+                          ("inliers_after_refinement", "slot", (), np.int32), ("iterations", "slot", (), np.int32),
+                          ("final_cost", "slot", (), np.float64), ("bearings", "feature", (3,), np.float64),
+                          ("valid", "feature", (), np.uint8), ("list", "feature", (), np.int32), ("samples", "slot", ("H", 4), np.int32),
+                          ("hypothesis_poses", "slot", (12,), np.float64))
+LOCALIZE_IMAGES_DEBUG = ("bearings", "valid", "list", "samples", "hypothesis_poses")
+LOCALIZE_IMAGES_DEFAULTS = dict(n_hypotheses=16, min_calibrated_match_count=7, min_inliers=4, max_iterations=50)
+LOCALIZED, LOCALIZE_STOP_RULE_MET, LOCALIZE_NONCENTRAL = 2, 4, 8      # bits of the flags (bit 0: more than 3 features)
+
+
+class CbaLocalizeImagesOutputs(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _, _ in LOCALIZE_IMAGES_ARRAYS]
+
+
 class CbaReport(C.Structure):
     _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("lambda_", C.c_double),
                 ("accepted", C.c_int32), ("lm_attempts", C.c_int32),
@@ -147,7 +176,7 @@ EXPORTED_SYMBOLS = [
     "cba_gridfirst_plan_query", "cba_elimination_order",
     "cba_model_direction_image", "cba_render_nearest_feature_image", "cba_model_center_point", "cba_model_line_offsets",
     "cba_debug_time_direction_image",
-    "cba_model_compare", "cba_model_direction_moments", "cba_model_localization_accuracy",
+    "cba_model_compare", "cba_model_direction_moments", "cba_model_localization_accuracy", "cba_model_localize_images",
     "cba_parametric_project", "cba_parametric_unproject", "cba_parametric_fit_pass", "cba_fit_parametric_to_dense_model",
     "cba_model_compare_parametric",
 ]
@@ -653,6 +682,51 @@ class DeviceModel:
         for name, _ in CbaLocalizationStats._fields_:
             if name != "reserved":
                 res[name] = getattr(st, name)
+        return res
+
+
+    # -- localization of a dataset's images ----------------------------------------------------------
+    @staticmethod
+    def localize_images(models, slot_id, slot_model, feature_start, pixels, points, candidate, seed: int = 0, threshold: float = 0.0,
+                        bearing_mode: int = 0, n_hypotheses: int = 0, min_calibrated_match_count: int = 0, min_inliers: int = 0,
+                        refine_set: int = 0, max_iterations: int = 0, want_debug: bool = False, start_poses=None) -> dict:
+        """cba_model_localize_images over the slots of `models` (DeviceModel objects on one device; 0 = an option's default): the
+        per-slot arrays, with want_debug also the bearings and valid bytes of stage A, the correspondence lists, the sample table and
+        the best hypotheses' poses."""
+        L = load()
+        ids = np.ascontiguousarray(slot_id, dtype=np.uint64).reshape(-1)
+        sm = np.ascontiguousarray(slot_model, dtype=np.int32).reshape(-1)
+        fs = np.ascontiguousarray(feature_start, dtype=np.int32).reshape(-1)
+        px = np.ascontiguousarray(pixels, dtype=np.float32).reshape(-1, 2)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        cand = np.ascontiguousarray(candidate, dtype=np.uint8).reshape(-1)
+        S, F = ids.shape[0], px.shape[0]
+        if not (sm.shape[0] == S and fs.shape[0] == S + 1 and pts.shape[0] == F and cand.shape[0] == F):
+            raise ValueError("localize_images: array lengths do not agree")
+        handles = (C.c_void_p * max(1, len(models)))(*[m._h for m in models])
+        inp = CbaLocalizeImagesInput()
+        inp.n_slots, inp.n_features, inp.n_models = S, F, len(models)
+        inp.models = C.cast(handles, C.POINTER(C.c_void_p))
+        inp.slot_id, inp.slot_model, inp.feature_start = ids.ctypes.data, sm.ctypes.data, fs.ctypes.data
+        inp.pixels, inp.points, inp.candidate = px.ctypes.data, pts.ctypes.data, cand.ctypes.data
+        sp = None
+        if start_poses is not None:
+            sp = np.ascontiguousarray(start_poses, dtype=np.float64).reshape(S, 12)
+            inp.start_poses = sp.ctypes.data
+        o = CbaLocalizeImagesOptions()
+        o.seed, o.threshold, o.bearing_mode, o.n_hypotheses = int(seed) & 0xFFFFFFFFFFFFFFFF, float(threshold), int(bearing_mode), int(n_hypotheses)
+        o.min_calibrated_match_count, o.min_inliers, o.refine_set, o.max_iterations = (int(min_calibrated_match_count), int(min_inliers),
+                                                                                      int(refine_set), int(max_iterations))
+        H = int(n_hypotheses) or LOCALIZE_IMAGES_DEFAULTS["n_hypotheses"]
+        out, res = CbaLocalizeImagesOutputs(), {}
+        if 0 < H <= 256:                     # (anything else is the library's to reject)
+            for name, per, tail, dt in LOCALIZE_IMAGES_ARRAYS:
+                if want_debug or name not in LOCALIZE_IMAGES_DEBUG:
+                    res[name] = np.zeros((S if per == "slot" else F,) + tuple(H if d == "H" else d for d in tail), dtype=dt)
+                    setattr(out, name, res[name].ctypes.data)
+        L.cba_model_localize_images.argtypes = [C.POINTER(CbaLocalizeImagesInput), C.POINTER(CbaLocalizeImagesOptions),
+                                                C.POINTER(CbaLocalizeImagesOutputs)]
+        _check(L.cba_model_localize_images(C.byref(inp), C.byref(o), C.byref(out)), "cba_model_localize_images")
         return res
 
 

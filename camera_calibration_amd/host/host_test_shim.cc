@@ -8,6 +8,7 @@
 #include "calibration.h"
 #include "fitting_report.h"
 #include "localization_accuracy.h"
+#include "image_localization.h"
 
 #include <algorithm>
 #include <chrono>
@@ -283,6 +284,36 @@ extern "C" int cba_host_create_fitting_visualization(const char* state_directory
 extern "C" int cba_host_localization_accuracy_test(const char* gt_model, const char* compared_model, const cba_localization_options* options,
                                                    cba_localization_stats* stats) {
   return options ? LocalizationAccuracyTest(gt_model, compared_model, *options, stats) : LocalizationAccuracyTest(gt_model, compared_model);
+}
+
+// vis::InitializeBAStateForLocalization (image_localization.h) on a dataset file and a saved calibration: rig_tr_global (7 per imageset:
+// qw qx qy qz tx ty tz), camera_tr_rig (7 per camera) and image_used (one byte per imageset) of the state it builds; the state is saved
+// to state_out unless that is NULL.  counts: slots attempted, localized, with too few matches, on a line.
+extern "C" int cba_host_localize_dataset(const char* dataset_path, const char* state_in, const char* state_out, int subpixel_bearings,
+                                         int refine_on_inliers, int hypotheses, uint64_t seed, double* rig_tr_global, double* camera_tr_rig,
+                                         uint8_t* image_used, int* counts) {
+  Dataset dataset;
+  if (!LoadDataset(dataset_path, &dataset)) return -1;
+  BAState loaded;
+  {
+    Dataset none(dataset.num_cameras());
+    if (!LoadBAState(state_in, &loaded, &none)) return -2;
+  }
+  BAState state;
+  state.intrinsics = loaded.intrinsics;
+  ImageLocalizationOptions options;
+  options.subpixel_bearings = subpixel_bearings != 0; options.refine_on_inliers = refine_on_inliers != 0; options.hypotheses = hypotheses; options.seed = seed;
+  ImageLocalizationReport report;
+  if (!InitializeBAStateForLocalization(&dataset, &state, options, &report)) return -3;
+  auto put = [](const SE3d& p, double* out) {
+    out[0] = p.unit_quaternion().w(); out[1] = p.unit_quaternion().x(); out[2] = p.unit_quaternion().y(); out[3] = p.unit_quaternion().z();
+    for (int k = 0; k < 3; ++k) out[4 + k] = p.translation()(k);
+  };
+  for (size_t i = 0; i < state.rig_tr_global.size(); ++i) { put(state.rig_tr_global[i], rig_tr_global + 7 * i); image_used[i] = state.image_used[i] ? 1 : 0; }
+  for (size_t c = 0; c < state.camera_tr_rig.size(); ++c) put(state.camera_tr_rig[c], camera_tr_rig + 7 * c);
+  counts[0] = report.slots_attempted; counts[1] = report.slots_localized; counts[2] = report.slots_too_few_matches; counts[3] = report.slots_on_a_line;
+  if (state_out && !SaveBAState(state_out, state)) return -4;
+  return 0;
 }
 
 // F2 round trip through the C++ mirror: load dataset.bin + BAState directory, write both back elsewhere.

@@ -373,6 +373,84 @@ typedef struct {
 int cba_model_localization_accuracy(cba_model* gt, cba_model* compared, const cba_localization_options* options,
                                     const cba_localization_outputs* outputs, cba_localization_stats* stats);
 
+/* ---- localization of a dataset's images against a calibration (APP/calibration_initialization/dense_initialization.cc:293-405) ---- */
+typedef struct {                           /* 0 selects the default of every member but seed, bearing_mode and refine_set */
+  uint64_t seed;
+  double threshold;                        /* inlier bound on 1 - b . f; default 1 - cos(atan(3 / 720)) (:389) */
+  int32_t bearing_mode;                    /* 0 = the centre of the pixel that contains the feature (the reference); 1 = the feature itself */
+  int32_t n_hypotheses;                    /* H, default 16, at most 256 */
+  int32_t min_calibrated_match_count;      /* default 7 (:1113) */
+  int32_t min_inliers;                     /* default 4 */
+  int32_t refine_set;                      /* 0 = the fit runs over all correspondences (the reference, :396-399); 1 = over the inliers */
+  int32_t max_iterations;                  /* of the fit, default 50 */
+} cba_localize_images_options;
+typedef struct {
+  int64_t n_slots, n_features;
+  int32_t n_models, reserved;
+  cba_model* const* models;                /* n_models, all on one device */
+  const uint64_t* slot_id;                 /* n_slots: the caller's name of the slot (imageset_index * n_cameras + camera_index) */
+  const int32_t* slot_model;               /* n_slots: index into models */
+  const int32_t* feature_start;            /* n_slots + 1: slot i holds the features feature_start[i] .. feature_start[i + 1] - 1;
+                                              feature_start[0] = 0, feature_start[n_slots] = n_features */
+  const float* pixels;                     /* 2 n_features */
+  const double* points;                    /* 3 n_features: the global 3D point of every feature */
+  const uint8_t* candidate;                /* n_features: the feature may enter the correspondence list */
+  const double* start_poses;               /* NULL; tests: 12 n_slots, (R row-major, c) the fit starts from instead of the best hypothesis */
+} cba_localize_images_input;
+typedef struct {                           /* every member may be NULL; H = n_hypotheses */
+  double* image_tr_global;                 /* 7 n_slots: qw qx qy qz tx ty tz, the inverse of the fitted (R, c); NaN when not localized */
+  uint8_t* flags;                          /* n_slots: bit 0 = more than 3 features, bit 1 = localized, bit 2 = the stop rule was met,
+                                              bit 3 = non-central model, line origins ignored */
+  int32_t* match_count;                    /* n_slots: valid features, candidate or not */
+  int32_t* list_length;                    /* n_slots: M */
+  int32_t* best_hypothesis;                /* n_slots: -1 when no hypothesis gave a pose */
+  int32_t* best_inliers;                   /* n_slots */
+  int32_t* inliers_after_refinement;       /* n_slots: correspondences of the list within the threshold of the refined pose */
+  int32_t* iterations;                     /* n_slots: evaluations of the normal equations */
+  double* final_cost;                      /* n_slots: the cost of the last accepted evaluation; NaN when not localized */
+  double* bearings;                        /* 3 n_features: stage A, NaN for an invalid feature */
+  uint8_t* valid;                          /* n_features: stage A */
+  int32_t* list;                           /* n_features: at feature_start[i] the M list entries of slot i (feature index within the slot), -1 behind */
+  int32_t* samples;                        /* 4 H n_slots: list positions of every hypothesis; -1 for a slot that drew none */
+  double* hypothesis_poses;                /* 12 n_slots: (R row-major, c) of the best hypothesis; NaN when not localized */
+} cba_localize_images_outputs;
+/* Localizes every slot -- one (imageset, camera) pair with its features -- against the model of its camera: the localize_only path of
+ * DenseInitialization (InitializeForLocalization / AttemptToLocalizeImage / LocalizePattern, dense_initialization.cc:293-405, 933-969,
+ * 1072-1115) as one call.  The host rules (which features match, the line test, the candidate bytes) are the caller's
+ * (camera_calibration_amd/localize_images.py, host/image_localization.h).  CBA_ERR_ARG: no model, models on different devices, a
+ * slot_model outside the models, a feature_start that is not ascending from 0 to n_features, an option outside its constraint.
+ *
+ * Stage A, per feature.  bearing = normalize(direction of Unproject(pixel)); for a non-central model the line's origin is ignored
+ * (CreateObservationDirectionsImage, APP/util.cc:206-226; flag bit 3).  bearing_mode 0: with ix = int(x), iy = int(y) (truncated, what
+ * no int holds is invalid) a feature with 0 <= ix < width, 0 <= iy < height un-projects (ix + 0.5f, iy + 0.5f) -- the reference's lookup
+ * in the direction image (:356-370) -- and any other feature is invalid.  bearing_mode 1: the finite pixel itself.  A failed
+ * Unproject makes the feature invalid (calibration_count == 0).
+ * Stage B, per slot.  match_count = the valid features.  The correspondence list = the features with candidate && valid, in feature
+ * order; M its length.  match_count < min_calibrated_match_count or M < 4: not localized.
+ * Hypothesis h in [0, H): with mix() as for cba_model_localization_accuracy,
+ *   key = mix(mix(seed + slot_id) + h);   r_j = (uint32(mix(key + j) >> 32) * (M - j)) >> 32 for j = 0 .. 3   (64-bit product)
+ * and r_j selects the r_j-th list position not yet chosen, in ascending order: four distinct positions s_0 .. s_3.
+ * P3P on s_0, s_1, s_2: Grunert's quartic in v = lam_3 / lam_1 (Haralick et al., "Review and analysis of solutions of the three point
+ * perspective pose estimation problem", IJCV 1994, eq. 8-9), its real roots by Ferrari's closed form in real arithmetic (the largest
+ * real root of the resolvent cubic by Cardano / the cosine form, two guarded Newton steps on it, then two quadratics), u = lam_2 / lam_1
+ * and lam_1 from the root; roots with v <= 0, u <= 0 are dropped.  Every solution is polished by two Gauss-Newton steps on
+ * |lam_i b_i - lam_j b_j| = |X_i - X_j| and kept if its depths are positive; (R, c) follows from the orthonormal frames of the two
+ * triangles.  A triple with |(X_1 - X_0) x (X_2 - X_0)|^2 <= 1e-10 |X_1 - X_0|^2 |X_2 - X_0|^2 (collinear) or a quartic whose leading
+ * coefficient is below 1e-14 of its largest has no solution.  Among the solutions s_3 picks the one with the smallest
+ * 1 - b . normalize(R^T (X - c)); a hypothesis without a solution is dead.
+ * Score: correspondence i of the list is an inlier of (R, c) if 1 - b_i . normalize(R^T (X_i - c)) < threshold.  The best hypothesis
+ * has the most inliers, the lowest h among equals.  No live hypothesis, or best_inliers < min_inliers: not localized.
+ * Fit: the damped Gauss-Newton of cba_model_localization_accuracy (cost, step rule, stop rule as stated there) from the best
+ * hypothesis, over all M correspondences (refine_set 0) or over the inliers of the best hypothesis (refine_set 1).
+ * image_tr_global = (R^T, -R^T c).  A slot's results are a function of (models, options, slot_id, its features) only: not of n_slots,
+ * of the order of the slots or of where on the device it ran.
+ * DEVIATIONS from the reference: it calls OpenGV's Kneip P3P inside OpenGV's rand()-driven RANSAC (10 iterations with an adaptive
+ * stop, two-point samples for the choice among solutions) and OpenGV's optimize_nonlinear; OpenGV is not part of the reference tree
+ * and no reference-produced vector exists.  Here H fixed hypotheses replace the adaptive ones and a sample has four members, so a
+ * list needs M >= 4 where the reference stops below 3.  Kept: the threshold, the match counts, the fit over all correspondences. */
+int cba_model_localize_images(const cba_localize_images_input* input, const cba_localize_images_options* options,
+                              const cba_localize_images_outputs* outputs);
+
 /* ---- solver-level entry point ---- */
 /* LMOptimizer::SolveWithSchurComplementDenseOffDiag (LV/lm_optimizer.h:1247-1369) on host arrays in
  * the reference's layout (symmetric parts: upper triangles only are read).  x = [block part; dense]. */

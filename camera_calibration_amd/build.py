@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcalib_ba_hip.so")
 SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip", "cba_report.hip", "cba_compare.hip",
            "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip"]
-HEADERS = ["cba_internal.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "block_device.hip.h", "localize_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
+HEADERS = ["cba_internal.h", "hip_buf.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "block_device.hip.h", "localize_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]  # keep MFMA accumulators in VGPRs: no AGPR<->VGPR copies in the K loop
 
@@ -237,8 +237,9 @@ def build_rccl(force: bool = False) -> str:
 
 
 def build_host_test(force: bool = False) -> str:
-    """Test-only shim over the C++ host adapter (tests/test_gpu_host_adapter.py etc.)."""
+    """Test-only shim over the C++ host adapter (tests/test_gpu_host_adapter.py etc.), and the check program of the device buffers."""
     build_host(force)
+    build_hip_buf_check(force)
     deps = [os.path.join(HOST_DIR, f) for f in HOST_TEST_SOURCES + HOST_HEADERS] + [HOST_LIB]
     if not force and os.path.exists(HOST_TEST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_TEST_LIB) for d in deps):
         return HOST_TEST_LIB
@@ -246,6 +247,17 @@ def build_host_test(force: bool = False) -> str:
            *[os.path.join(HOST_DIR, f) for f in HOST_TEST_SOURCES], "-L" + HERE, "-lcalib_ba_host", "-lcalib_ba_hip", "-Wl,-rpath,$ORIGIN"]
     subprocess.check_call(cmd)
     return HOST_TEST_LIB
+
+
+# check program of csrc/hip_buf.h (its own main, host HIP API only; tests/test_gpu_hip_buf.py runs it)
+HIP_BUF_CHECK = os.path.join(HERE, "hip_buf_check")
+
+
+def build_hip_buf_check(force: bool = False) -> str:
+    deps = [os.path.join(HOST_DIR, "hip_buf_check.cc"), os.path.join(CSRC, "hip_buf.h")]
+    if force or not os.path.exists(HIP_BUF_CHECK) or any(os.path.getmtime(d) > os.path.getmtime(HIP_BUF_CHECK) for d in deps):
+        subprocess.check_call([_hipcc(), "-O2", "-std=c++17", "-Wall", "-Wno-unused-value", "-Wno-unused-result", "--offload-arch=gfx950", deps[0], "-o", HIP_BUF_CHECK])
+    return HIP_BUF_CHECK
 
 
 if __name__ == "__main__":

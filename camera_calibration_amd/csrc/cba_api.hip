@@ -135,7 +135,8 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
   CBA_TRY(p->cost_ref.alloc((size_t)n)); CBA_TRY(p->cost_test.alloc((size_t)n));
   CBA_TRY(p->pixels.alloc(2 * (size_t)n)); CBA_TRY(p->flags.alloc((size_t)n));
   CBA_TRY(p->fd_out.alloc(2 * (size_t)n * p->tasks_per_obs)); CBA_TRY(p->fd_ok.alloc((size_t)n * p->tasks_per_obs));
-  CBA_TRY(p->jrec.alloc((size_t)n * p->rec_doubles)); CBA_TRY(p->cells.alloc(2 * (size_t)n));
+  // (jrec is cleared: records of mixed-model problems have unused tails)
+  CBA_TRY(p->jrec.alloc_zero((size_t)n * p->rec_doubles)); CBA_TRY(p->cells.alloc(2 * (size_t)n));
   {
     // gather-path follow-up lists of the finite-difference kernel: a quarter of all tasks (the share of tasks whose iterate
     // crosses a cell boundary is a few per cent) + 65 536
@@ -143,15 +144,13 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
     p->fd_redo_cap = (int)(cap > 0x7fffff00u ? 0x7fffff00u : cap);
     for (int i = 0; i < 2; ++i) CBA_TRY(p->fd_redo[i].alloc((size_t)p->fd_redo_cap));
   }
-  CBA_HIP(hipMemset(p->jrec, 0, sizeof(double) * (size_t)(n > 0 ? n : 1) * p->rec_doubles));   // records of mixed-model problems have unused tails
   CBA_TRY(p->cell_order.alloc((size_t)n));
   CBA_TRY(p->band_mask.alloc((size_t)(n > 0 ? n : 1)));
   {
     std::vector<int64_t> is((size_t)L.n_images + 1, 0);
     for (int64_t i = 0; i < n; ++i) is[image_index[i] + 1] += 1;
     for (int i = 0; i < L.n_images; ++i) is[i + 1] += is[i];
-    CBA_TRY(p->img_start.alloc(is.size()));
-    CBA_HIP(hipMemcpy(p->img_start, is.data(), sizeof(int64_t) * is.size(), hipMemcpyHostToDevice));
+    CBA_TRY(p->img_start.assign(is));
   }
   // observations of each (camera, pattern point), for the per-point accumulation (static: the point of an observation is data)
   p->pt_start.reset(); p->pt_obs.reset();
@@ -162,26 +161,20 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
     for (size_t k = 0; k < nk; ++k) ks[k + 1] += ks[k];
     std::vector<int> fill(ks.begin(), ks.end() - 1);
     for (int64_t i = 0; i < n; ++i) ko[(size_t)fill[(size_t)camera_index[i] * L.n_points + point_index[i]]++] = (int)i;
-    CBA_TRY(p->pt_start.alloc(ks.size())); CBA_TRY(p->pt_obs.alloc(ko.size()));
-    CBA_HIP(hipMemcpy(p->pt_start, ks.data(), sizeof(int) * ks.size(), hipMemcpyHostToDevice));
-    CBA_HIP(hipMemcpy(p->pt_obs, ko.data(), sizeof(int) * ko.size(), hipMemcpyHostToDevice));
+    CBA_TRY(p->pt_start.assign(ks)); CBA_TRY(p->pt_obs.assign(ko));
   }
   p->slow_cap = (int)std::min<int64_t>(std::max<int64_t>(kSlowCapMin, n / 8), 1 << 24);
   CBA_TRY(p->slow_list.alloc((size_t)p->slow_cap));
-  CBA_TRY(p->slow_skip.alloc((size_t)(n > 0 ? n : 1)));
-  CBA_HIP(hipMemset(p->slow_skip, 0, (size_t)(n > 0 ? n : 1)));
-  CBA_TRY(p->fd_slow.alloc((size_t)(n > 0 ? n : 1)));
-  CBA_HIP(hipMemset(p->fd_slow, 0, (size_t)(n > 0 ? n : 1)));
-  CBA_HIP(hipMemset(p->slow_count, 0, sizeof(int)));
-  if (n > 0) {
-    CBA_HIP(hipMemcpy(p->obs_xy, xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-    CBA_HIP(hipMemcpy(p->obs_point, point_index, sizeof(int) * n, hipMemcpyHostToDevice));
-    CBA_HIP(hipMemcpy(p->obs_image, image_index, sizeof(int) * n, hipMemcpyHostToDevice));
-    CBA_HIP(hipMemcpy(p->obs_camera, camera_index, sizeof(int) * n, hipMemcpyHostToDevice));
-    if (last_projection) CBA_HIP(hipMemcpy(p->last_projection, last_projection, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-    else CBA_HIP(hipMemset(p->last_projection, 0, sizeof(double) * 2 * n));
-    CBA_HIP(hipMemset(p->flags, 0, (size_t)n));
-  }
+  CBA_TRY(p->slow_skip.alloc_zero((size_t)(n > 0 ? n : 1)));
+  CBA_TRY(p->fd_slow.alloc_zero((size_t)(n > 0 ? n : 1)));
+  CBA_TRY(p->slow_count.zero());
+  CBA_TRY(p->obs_xy.upload(xy, 2 * (size_t)n));
+  CBA_TRY(p->obs_point.upload(point_index, (size_t)n));
+  CBA_TRY(p->obs_image.upload(image_index, (size_t)n));
+  CBA_TRY(p->obs_camera.upload(camera_index, (size_t)n));
+  if (last_projection) CBA_TRY(p->last_projection.upload(last_projection, 2 * (size_t)n));
+  else CBA_TRY(p->last_projection.zero());
+  CBA_TRY(p->flags.zero());
   // block order of the imagesets (eliminate_points = 0 only: the pose blocks are the Schur blocks)
   p->pose_slot.reset();
   p->pose_slot_host.clear();
@@ -190,8 +183,7 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
     order_imagesets(p, n, xy, point_index, image_index, camera_index, order);
     p->pose_slot_host.assign(L.n_images, 0);
     for (int r = 0; r < L.n_images; ++r) p->pose_slot_host[order[r]] = r;
-    CBA_TRY(p->pose_slot.alloc((size_t)L.n_images));
-    CBA_HIP(hipMemcpy(p->pose_slot, p->pose_slot_host.data(), sizeof(int) * L.n_images, hipMemcpyHostToDevice));
+    CBA_TRY(p->pose_slot.assign(p->pose_slot_host));
   }
   p->have_obs = true;
   return CBA_OK;
@@ -204,13 +196,12 @@ int cba_set_state(cba_problem* p, const double* rig_tr_global, const double* cam
   CBA_HIP(hipSetDevice(p->device));
   DevState& s = p->st[p->cur];
   const Layout& L = p->L;
-  if (L.n_images) CBA_HIP(hipMemcpy(s.rig_tr_global, rig_tr_global, sizeof(double) * 7 * L.n_images, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(s.camera_tr_rig, camera_tr_rig, sizeof(double) * 7 * L.n_cameras, hipMemcpyHostToDevice));
-  if (L.n_points) CBA_HIP(hipMemcpy(s.points, points, sizeof(double) * 3 * L.n_points, hipMemcpyHostToDevice));
+  CBA_TRY(s.rig_tr_global.upload(rig_tr_global, s.rig_tr_global.size()));
+  CBA_TRY(s.camera_tr_rig.upload(camera_tr_rig, s.camera_tr_rig.size()));
+  CBA_TRY(s.points.upload(points, s.points.size()));
   for (int c = 0; c < L.n_cameras; ++c) {
     if (!grids[c]) { set_error("cba_set_state: null grid"); return CBA_ERR_ARG; }
-    size_t G = (size_t)p->cams[c].grid_w * p->cams[c].grid_h;
-    CBA_HIP(hipMemcpy(s.grids[c], grids[c], sizeof(double) * doubles_per_point(p->cams[c].model_type) * G, hipMemcpyHostToDevice));
+    CBA_TRY(s.grids[c].upload(grids[c], s.grids[c].size()));
   }
   p->have_state = true; p->have_system = false;
   return CBA_OK;
@@ -222,15 +213,12 @@ int cba_get_state(cba_problem* p, double* rig_tr_global, double* camera_tr_rig, 
   CBA_HIP(hipStreamSynchronize(p->stream));
   const DevState& s = p->st[p->cur];
   const Layout& L = p->L;
-  if (rig_tr_global && L.n_images) CBA_HIP(hipMemcpy(rig_tr_global, s.rig_tr_global, sizeof(double) * 7 * L.n_images, hipMemcpyDeviceToHost));
-  if (camera_tr_rig) CBA_HIP(hipMemcpy(camera_tr_rig, s.camera_tr_rig, sizeof(double) * 7 * L.n_cameras, hipMemcpyDeviceToHost));
-  if (points && L.n_points) CBA_HIP(hipMemcpy(points, s.points, sizeof(double) * 3 * L.n_points, hipMemcpyDeviceToHost));
+  if (rig_tr_global) CBA_TRY(s.rig_tr_global.download(rig_tr_global, s.rig_tr_global.size()));
+  if (camera_tr_rig) CBA_TRY(s.camera_tr_rig.download(camera_tr_rig, s.camera_tr_rig.size()));
+  if (points) CBA_TRY(s.points.download(points, s.points.size()));
   if (grids)
-    for (int c = 0; c < L.n_cameras; ++c) {
-      if (!grids[c]) continue;
-      size_t G = (size_t)p->cams[c].grid_w * p->cams[c].grid_h;
-      CBA_HIP(hipMemcpy(grids[c], s.grids[c], sizeof(double) * doubles_per_point(p->cams[c].model_type) * G, hipMemcpyDeviceToHost));
-    }
+    for (int c = 0; c < L.n_cameras; ++c)
+      if (grids[c]) CBA_TRY(s.grids[c].download(grids[c], s.grids[c].size()));
   return CBA_OK;
 }
 
@@ -238,8 +226,7 @@ int cba_get_last_projection(cba_problem* p, double* out) {
   if (!p || !out || !p->have_obs) { set_error("cba_get_last_projection: bad argument"); return CBA_ERR_ARG; }
   CBA_HIP(hipSetDevice(p->device));
   CBA_HIP(hipStreamSynchronize(p->stream));
-  if (p->n_obs) CBA_HIP(hipMemcpy(out, p->last_projection, sizeof(double) * 2 * p->n_obs, hipMemcpyDeviceToHost));
-  return CBA_OK;
+  return p->last_projection.download(out, p->last_projection.size());
 }
 
 int cba_cost(cba_problem* p, double* cost, int64_t* n_valid, double* cost_vector) {
@@ -250,10 +237,10 @@ int cba_cost(cba_problem* p, double* cost, int64_t* n_valid, double* cost_vector
   CBA_TRY(launch_reduce_costs(nullptr, p->cost_test, nullptr, p->n_obs, p->red_partials, p->red8, p->stream));
   CBA_TRY(allreduce(p, p->red8, 8));
   double h[8];
-  CBA_TRY(read_scalars(p, p->red8, h, 8));
+  CBA_TRY(p->red8.download_sync(h, 8, p->stream));
   if (cost) *cost = h[1];
   if (n_valid) *n_valid = (int64_t)h[6];
-  if (cost_vector && p->n_obs) CBA_HIP(hipMemcpy(cost_vector, p->cost_test, sizeof(double) * p->n_obs, hipMemcpyDeviceToHost));
+  if (cost_vector) CBA_TRY(p->cost_test.download(cost_vector, (size_t)p->n_obs));
   return CBA_OK;
 }
 
@@ -275,7 +262,7 @@ int cba_debug_accumulate(cba_problem* p, double* cost) {
   CBA_TRY(jacobian_pass_and_accumulate(p, nullptr));
   CBA_TRY(launch_reduce_costs(p->cost_ref, nullptr, p->flags, p->n_obs, p->red_partials, p->red8, p->stream));
   double h[8];
-  CBA_TRY(read_scalars(p, p->red8, h, 8));
+  CBA_TRY(p->red8.download_sync(h, 8, p->stream));
   if (cost) *cost = h[0];
   return CBA_OK;
 }
@@ -295,7 +282,7 @@ int cba_debug_apply_update(cba_problem* p, const double* x) {
       for (int i = 0; i < p->L.n_images; ++i)
         for (int k = 0; k < 6; ++k) xp[p->L.first_rig_tr_global + 6 * p->pose_slot_host[i] + k] = x[p->L.first_rig_tr_global + 6 * i + k];
     for (int i = 0; i < p->L.dense_dof; ++i) xp[p->L.block_dof + p->dense_perm_host[i]] = x[p->L.block_dof + i];
-    CBA_HIP(hipMemcpy(p->x, xp.data(), sizeof(double) * p->L.total_dof, hipMemcpyHostToDevice));
+    CBA_TRY(p->x.upload(xp.data(), xp.size()));
   }
   CBA_TRY(launch_apply_update(p->L, p->cams, p->st[p->cur], p->x, p->st[p->cur ^ 1], p->pose_slot, gperm_view(p).v, p->stream));
   CBA_HIP(hipStreamSynchronize(p->stream));
@@ -334,10 +321,10 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
     report->final_cost = last_cost;
   };
   if (defer_cost_read) {
-    CBA_HIP(hipMemcpyAsync(p->pin_cost, p->red8, 8 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CBA_TRY(p->red8.download_async(p->pin_cost, 8, p->stream));
   } else {
     CBA_TRY(allreduce(p, p->red8, 8));
-    CBA_TRY(read_scalars(p, p->red8, h, 8));
+    CBA_TRY(p->red8.download_sync(h, 8, p->stream));
     take_pass_scalars();
     if (last_cost == 0) return finish_zero_cost_step(p, report, lambda);
   }
@@ -351,7 +338,7 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
       CBA_TRY(allreduce(p, p->scal, 1));
     }
     double sum;
-    CBA_TRY(read_scalars(p, p->scal, &sum, 1));
+    CBA_TRY(p->scal.download_sync(&sum, 1, p->stream));
     const int n_img_global = (multi && p->cfg.n_images_global > 0) ? p->cfg.n_images_global : L.n_images;
     const double dof_global = (double)L.total_dof + 6.0 * (n_img_global - L.n_images);
     lambda = init_lambda_factor * sum / dof_global;
@@ -372,7 +359,7 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
       if (rc == CBA_OK) {
         CBA_TRY(timer_begin(p, kTimerCost));
         CBA_TRY(enqueue_candidate_cost(p, cand, p->status + 1));
-        CBA_HIP(hipMemcpyAsync(p->pin_cost + 8, p->red8, 8 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        CBA_TRY(p->red8.download_async(p->pin_cost, 8, p->stream, 0, 8));
         CBA_TRY(timer_end(p, kTimerCost, 0, 0, 1));
         rc = solve_finish(p);            // the attempt's one host wait
       }
@@ -397,10 +384,10 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
       // take the same accept / reject / NaN branch -- otherwise one rank would enter the next solve's all-reduce of the
       // packed system while the others wait in the 8-double cost all-reduce -- so the failure flag is summed over ranks.
       const double f = failed ? 1.0 : 0.0;
-      CBA_HIP(hipMemcpyAsync(p->scal + 8, &f, sizeof(double), hipMemcpyHostToDevice, p->stream));
+      CBA_TRY(p->scal.upload_async(&f, 1, p->stream, 8));
       CBA_TRY(allreduce(p, p->scal + 8, 1));
       double fs = 0.0;
-      CBA_TRY(read_scalars(p, p->scal + 8, &fs, 1));
+      CBA_TRY(p->scal.download_sync(&fs, 1, p->stream, 8));
       failed = fs != 0.0;
     }
     if (failed) {   // NaN update -> lambda *= 2 (lm_optimizer.h:905-913)
@@ -413,7 +400,7 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
       const double t0 = now_s();
       CBA_TRY(enqueue_candidate_cost(p, cand, nullptr));
       CBA_TRY(allreduce(p, p->red8, 8));
-      CBA_TRY(read_scalars(p, p->red8, h, 8));
+      CBA_TRY(p->red8.download_sync(h, 8, p->stream));
       report->t_cost += now_s() - t0;
     }
     // CostIsSmallerThan (lm_optimizer.h:993-1011): only residuals valid in both passes
@@ -461,10 +448,10 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
   CBA_HIP(hipStreamSynchronize(p->stream));
   const Layout& L = p->L;
   const size_t n = (size_t)p->n_obs, bs = L.block_size, nb = L.n_blocks, dd = L.dense_dof, ld = p->n_pad;
-  auto copy = [&](const void* src, size_t need) -> int {
-    if (bytes < need) { set_error("cba_debug_dump: buffer too small"); return CBA_ERR_ARG; }
-    if (need) CBA_HIP(hipMemcpy(out, src, need, hipMemcpyDeviceToHost));
-    return CBA_OK;
+  auto copy = [&](const auto& buf, size_t count) -> int {      // the first `count` elements of a device buffer
+    using T = typename std::decay_t<decltype(buf)>::value_type;
+    if (bytes < count * sizeof(T)) { set_error("cba_debug_dump: buffer too small"); return CBA_ERR_ARG; }
+    return buf.download(static_cast<T*>(out), count);
   };
   auto copy2d = [&](const double* src, size_t rows, size_t cols) -> int {
     if (bytes < rows * cols * sizeof(double)) { set_error("cba_debug_dump: buffer too small"); return CBA_ERR_ARG; }
@@ -492,13 +479,13 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
     }
   };
   switch (what) {
-    case CBA_DUMP_COST_VECTOR: return copy(p->cost_ref, n * sizeof(double));
-    case CBA_DUMP_TEST_COST_VECTOR: return copy(p->cost_test, n * sizeof(double));
-    case CBA_DUMP_PIXELS: return copy(p->pixels, 2 * n * sizeof(double));
+    case CBA_DUMP_COST_VECTOR: return copy(p->cost_ref, n);
+    case CBA_DUMP_TEST_COST_VECTOR: return copy(p->cost_test, n);
+    case CBA_DUMP_PIXELS: return copy(p->pixels, 2 * n);
     case CBA_DUMP_FLAGS: return copy(p->flags, n);
-    case CBA_DUMP_JACOBIANS: return copy(p->jrec, n * p->rec_doubles * sizeof(double));
-    case CBA_DUMP_BLOCK_DIAG_H: { int rc = copy(p->Dblk, nb * bs * bs * sizeof(double)); if (rc == CBA_OK) unpermute_rows(bs); return rc; }
-    case CBA_DUMP_BLOCK_DIAG_B: { int rc = copy(p->bblk, nb * bs * sizeof(double)); if (rc == CBA_OK) unpermute_rows(1); return rc; }
+    case CBA_DUMP_JACOBIANS: return copy(p->jrec, n * p->rec_doubles);
+    case CBA_DUMP_BLOCK_DIAG_H: { int rc = copy(p->Dblk, nb * bs * bs); if (rc == CBA_OK) unpermute_rows(bs); return rc; }
+    case CBA_DUMP_BLOCK_DIAG_B: { int rc = copy(p->bblk, nb * bs); if (rc == CBA_OK) unpermute_rows(1); return rc; }
     case CBA_DUMP_OFF_DIAG_H: {
       int rc = copy2d(p->B, nb * bs, dd);
       if (rc == CBA_OK) { unpermute_rows(dd); unpermute_cols(nb * bs, 0); }
@@ -519,10 +506,9 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
         }
       return CBA_OK;
     }
-    case CBA_DUMP_DENSE_B: { int rc = copy(p->bd, dd * sizeof(double)); if (rc == CBA_OK) unpermute_cols(1, 0); return rc; }
+    case CBA_DUMP_DENSE_B: { int rc = copy(p->bd, dd); if (rc == CBA_OK) unpermute_cols(1, 0); return rc; }
     case CBA_DUMP_X: {
-      if (bytes < (size_t)L.total_dof * sizeof(double)) { set_error("cba_debug_dump: buffer too small"); return CBA_ERR_ARG; }
-      CBA_HIP(hipMemcpy(out, p->x, (size_t)L.total_dof * sizeof(double), hipMemcpyDeviceToHost));
+      CBA_TRY(copy(p->x, (size_t)L.total_dof));
       if (!p->pose_slot_host.empty()) unpermute_rows(1);   // the block part comes first in x (eliminate_points = 0)
       unpermute_cols(1, L.block_dof);
       return CBA_OK;
@@ -535,7 +521,7 @@ int64_t cba_fd_redo_overflow(cba_problem* p) {
   if (!p || !p->fd_redo_count) return -1;
   int v = 0;
   if (hipSetDevice(p->device) != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess ||
-      hipMemcpy(&v, p->fd_redo_count + 2, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+      p->fd_redo_count.download(&v, 1, 2) != CBA_OK) return -1;
   return v;
 }
 int cba_debug_fd_redo_counts(cba_problem* p, int64_t out[3]) {
@@ -543,7 +529,7 @@ int cba_debug_fd_redo_counts(cba_problem* p, int64_t out[3]) {
   int v[3] = {0, 0, 0};
   CBA_HIP(hipSetDevice(p->device));
   CBA_HIP(hipStreamSynchronize(p->stream));
-  CBA_HIP(hipMemcpy(v, p->fd_redo_count, sizeof(v), hipMemcpyDeviceToHost));
+  CBA_TRY(p->fd_redo_count.download(v, 3));
   for (int i = 0; i < 3; ++i) out[i] = v[i];
   return CBA_OK;
 }

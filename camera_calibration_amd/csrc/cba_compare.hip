@@ -56,7 +56,7 @@ int compare_finish(const cba_compare_options* options, const cba_compare_outputs
                    int n_list) {
   CBA_TRY(launch_compare_reduce((int64_t)n, b.flags, b.err, b.reproj, b.fit_dir, b.base_dir, false, b.partials, b.sums, nullptr));
   double h[kCompareSums];
-  CBA_HIP(hipMemcpy(h, b.sums, sizeof(h), hipMemcpyDeviceToHost));
+  CBA_TRY(b.sums.download(h, kCompareSums));
 
   const bool want_images = o.error_magnitudes || o.error_direction_angles || o.error_directions || o.reprojection_magnitudes || o.reprojections;
   DevBuf<uint8_t> img;
@@ -71,17 +71,17 @@ int compare_finish(const cba_compare_options* options, const cba_compare_outputs
     uint8_t* p = img;
     c.img_magnitudes = p; c.img_angles = p + n; c.img_directions = p + 4 * n; c.img_reproj_magnitudes = p + 7 * n; c.img_reprojections = p + 8 * n;
     CBA_TRY(launch_compare_colors(c, nullptr));
-    if (o.error_magnitudes) CBA_HIP(hipMemcpy(o.error_magnitudes, c.img_magnitudes, n, hipMemcpyDeviceToHost));
-    if (o.error_direction_angles) CBA_HIP(hipMemcpy(o.error_direction_angles, c.img_angles, 3 * n, hipMemcpyDeviceToHost));
-    if (o.error_directions) CBA_HIP(hipMemcpy(o.error_directions, c.img_directions, 3 * n, hipMemcpyDeviceToHost));
-    if (o.reprojection_magnitudes) CBA_HIP(hipMemcpy(o.reprojection_magnitudes, c.img_reproj_magnitudes, n, hipMemcpyDeviceToHost));
-    if (o.reprojections) CBA_HIP(hipMemcpy(o.reprojections, c.img_reprojections, 3 * n, hipMemcpyDeviceToHost));
+    if (o.error_magnitudes) CBA_TRY(img.download(o.error_magnitudes, n, 0));
+    if (o.error_direction_angles) CBA_TRY(img.download(o.error_direction_angles, 3 * n, n));
+    if (o.error_directions) CBA_TRY(img.download(o.error_directions, 3 * n, 4 * n));
+    if (o.reprojection_magnitudes) CBA_TRY(img.download(o.reprojection_magnitudes, n, 7 * n));
+    if (o.reprojections) CBA_TRY(img.download(o.reprojections, 3 * n, 8 * n));
   }
-  if (o.base_directions) CBA_HIP(hipMemcpy(o.base_directions, b.base_dir, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-  if (o.fitted_directions) CBA_HIP(hipMemcpy(o.fitted_directions, b.fit_dir, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-  if (o.errors) CBA_HIP(hipMemcpy(o.errors, b.err, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-  if (o.reprojection_errors) CBA_HIP(hipMemcpy(o.reprojection_errors, b.reproj, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
-  if (o.flags) CBA_HIP(hipMemcpy(o.flags, b.flags, n, hipMemcpyDeviceToHost));
+  if (o.base_directions) CBA_TRY(b.base_dir.download(o.base_directions, 3 * n));
+  if (o.fitted_directions) CBA_TRY(b.fit_dir.download(o.fitted_directions, 3 * n));
+  if (o.errors) CBA_TRY(b.err.download(o.errors, 3 * n));
+  if (o.reprojection_errors) CBA_TRY(b.reproj.download(o.reprojection_errors, 2 * n));
+  if (o.flags) CBA_TRY(b.flags.download(o.flags, n));
   if (stats) {
     stats->n_base_ok = (int64_t)h[kCmpBaseOk]; stats->n_both_ok = (int64_t)h[kCmpBothOk]; stats->n_projected = (int64_t)h[kCmpProjected];
     stats->n_second_launch = n_list;
@@ -90,8 +90,8 @@ int compare_finish(const cba_compare_options* options, const cba_compare_outputs
     stats->reprojection_error_median = 0; stats->has_median = 0;
     if (stats->n_projected > 0) {             // std::sort, element size / 2 (:193-194)
       std::vector<double> r(2 * n); std::vector<uint8_t> fl(n);
-      CBA_HIP(hipMemcpy(r.data(), b.reproj, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
-      CBA_HIP(hipMemcpy(fl.data(), b.flags, n, hipMemcpyDeviceToHost));
+      CBA_TRY(b.reproj.download(r.data(), r.size()));
+      CBA_TRY(b.flags.download(fl.data(), fl.size()));
       std::vector<double> mags;
       mags.reserve((size_t)stats->n_projected);
       for (size_t i = 0; i < n; ++i)
@@ -126,10 +126,10 @@ int cba_model_compare(cba_model* base, cba_model* fitted, const cba_compare_opti
   const int thr = options->straggler_threshold;
   a.max_outer = thr == 0 ? kDefaultStragglerThreshold : (thr < 0 ? 0 : std::min(thr, 100));
   a.do_project = 1;
-  CBA_HIP(hipMemsetAsync(b.count, 0, sizeof(int), nullptr));
+  CBA_TRY(b.count.zero_async(nullptr));
   CBA_TRY(launch_compare_pass(a, nullptr));
   int n_list = 0;
-  CBA_HIP(hipMemcpy(&n_list, b.count, sizeof(int), hipMemcpyDeviceToHost));
+  CBA_TRY(b.count.download(&n_list, 1));
   if (n_list < 0 || (size_t)n_list > n) { set_error("cba_model_compare: pixel list corrupt"); return CBA_ERR_HIP; }
   CBA_TRY(launch_compare_second(a, n_list, nullptr));
   return compare_finish(options, o, stats, b, n, n_list);
@@ -173,11 +173,11 @@ int cba_model_direction_moments(cba_model* base, cba_model* fitted, int32_t bord
   const double identity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};      // 1 * a + 0 * b + 0 * c is a: base_dir holds the unrotated directions
   CompareArgs a = make_args(base, fitted, identity, border_x, border_y, b);
   a.max_outer = 100; a.do_project = 0;
-  CBA_HIP(hipMemsetAsync(b.count, 0, sizeof(int), nullptr));
+  CBA_TRY(b.count.zero_async(nullptr));
   CBA_TRY(launch_compare_pass(a, nullptr));
   CBA_TRY(launch_compare_reduce((int64_t)n, b.flags, b.err, b.reproj, b.fit_dir, b.base_dir, true, b.partials, b.sums, nullptr));
   double h[kCompareSums];
-  CBA_HIP(hipMemcpy(h, b.sums, sizeof(h), hipMemcpyDeviceToHost));
+  CBA_TRY(b.sums.download(h, kCompareSums));
   for (int k = 0; k < 9; ++k) M[k] = h[kCmpMoments + k];
   if (n_out) *n_out = (int64_t)h[kCmpBothOk];
   return CBA_OK;

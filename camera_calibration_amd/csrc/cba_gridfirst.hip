@@ -11,19 +11,13 @@ namespace cba {
 int alloc_gridfirst_system(cba_problem* p) {
   const GfPlan& g = p->gf.plan;
   const size_t nf = (size_t)g.n_pad, wb = (size_t)(g.n_pad - g.Gf);
-  CBA_TRY(p->gf.F.alloc(nf * nf));
-  CBA_HIP(hipMemset(p->gf.F, 0, sizeof(double) * nf * nf));          // tiles outside the plan's structure stay zero for ever
-  CBA_TRY(p->gf.Xb.alloc((size_t)g.Gf * wb));
-  CBA_HIP(hipMemset(p->gf.Xb, 0, sizeof(double) * (size_t)g.Gf * wb));
+  CBA_TRY(p->gf.F.alloc_zero(nf * nf));          // tiles outside the plan's structure stay zero for ever
+  CBA_TRY(p->gf.Xb.alloc_zero((size_t)g.Gf * wb));
   CBA_TRY(p->gf.xF.alloc(nf));
-  CBA_TRY(p->gf.dev.tasks.alloc(g.tasks.size()));
-  CBA_TRY(p->gf.dev.ivals.alloc(g.ivals.size()));
-  CBA_TRY(p->gf.dev.chains.alloc(g.chains.size()));
-  CBA_TRY(p->gf.dev.rowmask.alloc(g.rowmask.size()));
-  CBA_HIP(hipMemcpy(p->gf.dev.tasks, g.tasks.data(), sizeof(GfTask) * g.tasks.size(), hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(p->gf.dev.ivals, g.ivals.data(), sizeof(GfIval) * g.ivals.size(), hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(p->gf.dev.chains, g.chains.data(), sizeof(GfChain) * g.chains.size(), hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(p->gf.dev.rowmask, g.rowmask.data(), sizeof(uint64_t) * g.rowmask.size(), hipMemcpyHostToDevice));
+  CBA_TRY(p->gf.dev.tasks.assign(g.tasks));
+  CBA_TRY(p->gf.dev.ivals.assign(g.ivals));
+  CBA_TRY(p->gf.dev.chains.assign(g.chains));
+  CBA_TRY(p->gf.dev.rowmask.assign(reinterpret_cast<const unsigned long long*>(g.rowmask.data()), g.rowmask.size()));
   p->gf.dev.n_tasks0 = g.n_tasks0; p->gf.dev.n_tasks1 = (int)g.tasks.size() - g.n_tasks0; p->gf.dev.n_chains = (int)g.chains.size();
   p->gf.dev.nbg = g.nbg; p->gf.dev.nbf = g.nbf; p->gf.dev.mask_words = g.mask_words; p->gf.dev.flops_grid = g.flops_grid;
   // tiles the forming kernel writes per attempt: the structural tiles of the grid x grid part, the row strips of the grid rows
@@ -39,12 +33,9 @@ int alloc_gridfirst_system(cba_problem* p) {
   for (int r = g.nbg; r < g.ntc; ++r)
     for (int c = r; c < g.ntc; ++c) { tiles.push_back(r); tiles.push_back(c); }
   p->gf.n_tiles = (int)(tiles.size() / 2);
-  CBA_TRY(p->gf.tiles.alloc(tiles.size()));
-  CBA_HIP(hipMemcpy(p->gf.tiles, tiles.data(), sizeof(int) * tiles.size(), hipMemcpyHostToDevice));
-  CBA_TRY(p->gf.grid_of_f.alloc(g.grid_of_f.size()));
-  CBA_HIP(hipMemcpy(p->gf.grid_of_f, g.grid_of_f.data(), sizeof(int) * g.grid_of_f.size(), hipMemcpyHostToDevice));
-  CBA_TRY(p->gf.f_of_grid.alloc(g.f_of_grid.size()));
-  CBA_HIP(hipMemcpy(p->gf.f_of_grid, g.f_of_grid.data(), sizeof(int) * g.f_of_grid.size(), hipMemcpyHostToDevice));
+  CBA_TRY(p->gf.tiles.assign(tiles));
+  CBA_TRY(p->gf.grid_of_f.assign(g.grid_of_f));
+  CBA_TRY(p->gf.f_of_grid.assign(g.f_of_grid));
   // activity of the row strips (per pass): bit sets over the grid block rows per 128-column border tile, and what is derived
   {
     GfDevice& d = p->gf.dev;
@@ -52,21 +43,18 @@ int alloc_gridfirst_system(cba_problem* p) {
     d.n_act_tiles = (g.n_pad - g.Gf) / 128;
     d.kmask_words = (g.Gf / 16 + 63) / 64;
     CBA_TRY(d.act.alloc((size_t)d.n_act_tiles * d.act_words));
-    CBA_TRY(d.kmask.alloc((size_t)(g.n_pad / 128) * d.kmask_words));
-    CBA_HIP(hipMemset(d.kmask, 0, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words));
+    CBA_TRY(d.kmask.alloc_zero((size_t)(g.n_pad / 128) * d.kmask_words));
     CBA_TRY(d.rowmask_dyn.alloc(g.rowmask.size()));
-    CBA_TRY(d.gridrow.alloc(g.gridrow.size()));
-    CBA_HIP(hipMemcpy(d.gridrow, g.gridrow.data(), sizeof(uint64_t) * g.gridrow.size(), hipMemcpyHostToDevice));
+    CBA_TRY(d.gridrow.assign(reinterpret_cast<const unsigned long long*>(g.gridrow.data()), g.gridrow.size()));
     {
       const size_t nt = (size_t)d.n_act_tiles;
       // entries of four ints (tm, tn, K-slab range), eight interleaved per-XCD lists padded to the longest: 4 x 8 x (tiles in up to three
       // parts each, dealt evenly) is a quarter of this
-      p->gf.tile_list_capacity = (size_t)32 * nt * (nt + 1) + 4096;
-      CBA_TRY(p->gf.tile_list.alloc(p->gf.tile_list_capacity));
-      CBA_TRY(p->gf.tile_list_host.alloc(p->gf.tile_list_capacity));
+      CBA_TRY(p->gf.tile_list.alloc((size_t)32 * nt * (nt + 1) + 4096));
+      CBA_TRY(p->gf.tile_list_host.alloc(p->gf.tile_list.size()));
     }
-    CBA_TRY(p->gf.kmask_host.alloc((size_t)(g.n_pad / 128) * d.kmask_words));
-    std::memset(p->gf.kmask_host, 0, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words);
+    CBA_TRY(p->gf.kmask_host.alloc(d.kmask.size()));
+    std::memset(p->gf.kmask_host, 0, sizeof(unsigned long long) * d.kmask.size());
   }
   return CBA_OK;
 }
@@ -117,24 +105,22 @@ static int gf_exchange(cba_problem* p) {
   const int nw = d.n_act_tiles * d.act_words, M = p->sh.max_local, nloc = L.n_images;
   const int64_t oD = 2 * (int64_t)nw, ob = oD + 36 * (int64_t)M, oB = ob + 6 * (int64_t)M;
   CBA_TRY(launch_gf_words_to_doubles(d.act, nw, p->sh.gsend, s));
-  if (nloc > 0) {
-    CBA_HIP(hipMemcpyAsync(p->sh.gsend + oD, p->Dblk, sizeof(double) * 36 * (size_t)nloc, hipMemcpyDeviceToDevice, s));
-    CBA_HIP(hipMemcpyAsync(p->sh.gsend + ob, p->bblk, sizeof(double) * 6 * (size_t)nloc, hipMemcpyDeviceToDevice, s));
-    CBA_HIP(hipMemcpyAsync(p->sh.gsend + oB, p->B, sizeof(double) * 6 * (size_t)nloc * ld, hipMemcpyDeviceToDevice, s));
-  }
+  CBA_TRY(p->sh.gsend.copy_from_async(p->Dblk, 36 * (size_t)nloc, oD, 0, s));
+  CBA_TRY(p->sh.gsend.copy_from_async(p->bblk, 6 * (size_t)nloc, ob, 0, s));
+  CBA_TRY(p->sh.gsend.copy_from_async(p->B, 6 * (size_t)nloc * ld, oB, 0, s));
   CBA_TRY(gf_allgather(p));
   for (int r = 0; r < p->sh.world; ++r) {
     const size_t cnt = (size_t)p->sh.counts[r], off = (size_t)p->sh.offsets[r];
     if (!cnt) continue;
-    const double* src = p->sh.grecv + (size_t)r * p->sh.gblk;
-    CBA_HIP(hipMemcpyAsync(p->sh.gDblk + 36 * off, src + oD, sizeof(double) * 36 * cnt, hipMemcpyDeviceToDevice, s));
-    CBA_HIP(hipMemcpyAsync(p->sh.gbblk + 6 * off, src + ob, sizeof(double) * 6 * cnt, hipMemcpyDeviceToDevice, s));
-    CBA_HIP(hipMemcpyAsync(p->sh.gB + 6 * off * ld, src + oB, sizeof(double) * 6 * cnt * ld, hipMemcpyDeviceToDevice, s));
+    const size_t src = (size_t)r * p->sh.gblk;      // block r of grecv
+    CBA_TRY(p->sh.gDblk.copy_from_async(p->sh.grecv, 36 * cnt, 36 * off, src + oD, s));
+    CBA_TRY(p->sh.gbblk.copy_from_async(p->sh.grecv, 6 * cnt, 6 * off, src + ob, s));
+    CBA_TRY(p->sh.gB.copy_from_async(p->sh.grecv, 6 * cnt * ld, 6 * off * ld, src + oB, s));
   }
   CBA_TRY(launch_gf_or_words(p->sh.grecv, p->sh.world, p->sh.gblk, nw, d.act, s));
   CBA_TRY(launch_gf_close_masks(d.n_act_tiles, d.act_words, g.nbg, g.nbf, d.gridrow, d.act, d.kmask, d.kmask_words, g.Gf / 128, d.rowmask,
                                 d.rowmask_dyn, d.mask_words, s));
-  CBA_HIP(hipMemcpyAsync(p->gf.kmask_host, d.kmask, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words, hipMemcpyDeviceToHost, s));
+  CBA_TRY(d.kmask.download_async(p->gf.kmask_host, d.kmask.size(), s));
   return CBA_OK;
 }
 
@@ -166,15 +152,12 @@ int setup_gf_sharding(cba_problem* p) {
   CBA_TRY(p->sh.gB.alloc(6 * Ng * ld));
   const GfDevice& d = p->gf.dev;
   p->sh.gblk = 2 * (int64_t)d.n_act_tiles * d.act_words + (int64_t)p->sh.max_local * (42 + 6 * (int64_t)ld);
-  CBA_TRY(p->sh.gsend.alloc((size_t)p->sh.gblk));
-  CBA_HIP(hipMemset(p->sh.gsend, 0, sizeof(double) * (size_t)p->sh.gblk));
+  CBA_TRY(p->sh.gsend.alloc_zero((size_t)p->sh.gblk));
   CBA_TRY(p->sh.grecv.alloc((size_t)p->sh.gblk * W));
   // band position -> engine dense column (the engine's grid order is the plan's elimination order, build_grid_order)
   std::vector<int> col(p->sh.shared.ref_col.size());
   for (size_t k = 0; k < col.size(); ++k) col[k] = p->dense_perm_host[p->sh.shared.ref_col[k]];
-  CBA_TRY(p->sh.shared_col.alloc(col.size()));
-  CBA_HIP(hipMemcpy(p->sh.shared_col, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
-  return CBA_OK;
+  return p->sh.shared_col.assign(col);
 }
 
 // Jacobian pass, side stream: which grid block rows each 128-column tile of the border can reach in THIS pass (the control patch of an
@@ -191,7 +174,7 @@ int gridfirst_pass_activity(cba_problem* p, const PassArgs& a, hipStream_t aux) 
     CBA_TRY(launch_gf_activity(a, p->flags, p->cells, p->img_start, L.n_images, p->gf.f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
                                d.n_act_tiles, d.act_words, g.nbg, g.nbf, d.gridrow, d.act, d.kmask, d.kmask_words, g.Gf / 128, d.rowmask, d.rowmask_dyn,
                                d.mask_words, aux));
-    CBA_HIP(hipMemcpyAsync(p->gf.kmask_host, d.kmask, sizeof(unsigned long long) * (size_t)(g.n_pad / 128) * d.kmask_words, hipMemcpyDeviceToHost, aux));
+    CBA_TRY(d.kmask.download_async(p->gf.kmask_host, d.kmask.size(), aux));
   }
   return CBA_OK;
 }
@@ -264,7 +247,7 @@ static void gf_build_tile_list(cba_problem* p, int nt, int n_slabs, Weight weigh
   }
   size_t longest = 0;
   for (int x = 0; x < 8; ++x) longest = std::max(longest, lists[x].size());
-  if (4 * 8 * longest > p->gf.tile_list_capacity) return;      // (cannot happen with the sizing of cba_create; the previous list stays)
+  if (4 * 8 * longest > p->gf.tile_list_host.size()) return;      // (cannot happen with the sizing of cba_create; the previous list stays)
   p->gf.tile_list_entries = (int)(8 * longest);
   for (size_t i = 0; i < longest; ++i)
     for (int x = 0; x < 8; ++x) {
@@ -295,7 +278,7 @@ int gridfirst_enqueue(cba_problem* p, double lambda) {
   const int* tile_list = nullptr;
   if (p->gf.tile_list_valid) {
     if (p->gf.tile_list_dirty) {      // (rebuilt by gridfirst_finish behind a stream wait: nothing in flight reads the device copy)
-      CBA_HIP(hipMemcpyAsync(p->gf.tile_list, p->gf.tile_list_host, sizeof(int) * 4 * (size_t)p->gf.tile_list_entries, hipMemcpyHostToDevice, p->stream));
+      CBA_TRY(p->gf.tile_list.upload_async(p->gf.tile_list_host, 4 * (size_t)p->gf.tile_list_entries, p->stream));
       p->gf.tile_list_dirty = false;
     }
     tile_list = p->gf.tile_list;

@@ -10,54 +10,13 @@
 
 #include "../../include/cba.h"
 #include "gridfirst_plan.h"
+#include "hip_buf.h"
 #include "model.hip.h"
 
 namespace cba {
 
-void set_error(const std::string& msg);
-#define CBA_HIP(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      ::cba::set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                     \
-      return CBA_ERR_HIP;                                                                      \
-    }                                                                                          \
-  } while (0)
-#define CBA_TRY(expr) do { int _rc = (expr); if (_rc != CBA_OK) return _rc; } while (0)
-
-// Owning handles of device memory (DevBuf), pinned host memory (PinnedBuf) and events (Event); host only, move-only.
-// alloc(n) / create() first release what the handle holds, then allocate (n = 0 allocates one element); on failure the
-// handle stays empty and the error is set as by CBA_HIP.  The read-only conversion keeps launch sites as they are (p->Dblk).
-template <typename T, bool kPinned>
-class HipBuf {
- public:
-  HipBuf() = default;
-  HipBuf(HipBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-  HipBuf& operator=(HipBuf&& o) noexcept {
-    if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
-    return *this;
-  }
-  ~HipBuf() { reset(); }
-  int alloc(size_t n) {
-    reset();
-    void* q = nullptr;
-    if (kPinned) CBA_HIP(hipHostMalloc(&q, (n ? n : 1) * sizeof(T)));
-    else CBA_HIP(hipMalloc(&q, (n ? n : 1) * sizeof(T)));
-    p_ = static_cast<T*>(q);
-    return CBA_OK;
-  }
-  void reset() {
-    if (p_) { if (kPinned) hipHostFree(p_); else hipFree(p_); }
-    p_ = nullptr;
-  }
-  operator T*() const { return p_; }
-
- private:
-  T* p_ = nullptr;
-};
-template <typename T> using DevBuf = HipBuf<T, false>;
-template <typename T> using PinnedBuf = HipBuf<T, true>;
-
+// Owning handle of an event; host only, move-only.  create() first releases what the handle holds; on failure the handle stays
+// empty and the error is set as by CBA_HIP.
 class Event {
  public:
   Event() = default;
@@ -182,7 +141,7 @@ int launch_tangents(const double* dir_grid, double* tang, int G, hipStream_t s);
 // base projection of every observation; lanes that exceed the iteration cap are appended to defer_list (and marked in
 // defer_skip) for launch_base_project_slow, which takes the list through PassArgs::obs_list / obs_count / obs_list_cap
 int launch_base_project(const PassArgs& a, int model_mask, double* cost_vec, double* pixels, uint8_t* flags, int* defer_list,
-                        int* defer_count, int defer_cap, uint8_t* defer_skip, int outer_cap, const uint8_t* fd_slow, hipStream_t s);
+                        DevBuf<int>& defer_count, int defer_cap, uint8_t* defer_skip, int outer_cap, const uint8_t* fd_slow, hipStream_t s);
 int launch_base_project_slow(const PassArgs& a, int model_mask, double* cost_vec, double* pixels, uint8_t* flags, hipStream_t s);
 int launch_project_points(const CamDev* cam_dev, int model, int64_t n, const double* local, const double* init,
                           double* pixels, uint8_t* ok, hipStream_t s);
@@ -210,12 +169,12 @@ int launch_accumulate(const PassArgs& a, const Layout& L, const uint8_t* flags, 
 int launch_accumulate_points(const PassArgs& a, const Layout& L, const std::vector<cba_camera>& cams, const uint8_t* flags, const int* cells,
                              const int* key_start, const int* key_obs, AccumTargets t, const double* det_scale, hipStream_t s);
 // deterministic mode (cba_config.deterministic): fixed-point scale of a pass, conversion of an accumulated array
-int launch_det_scale(const PassArgs& a, const uint8_t* flags, unsigned long long* bits, double* scale, hipStream_t s);
+int launch_det_scale(const PassArgs& a, const uint8_t* flags, DevBuf<unsigned long long>& bits, double* scale, hipStream_t s);
 int launch_det_convert(double* p, size_t n, const double* det_scale, hipStream_t s);
 int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, const uint8_t* flags, const int* cells,
                              unsigned long long* band_mask, const int64_t* img_start, double* B, int ld, const double* det_scale, hipStream_t s);
 int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const std::vector<int>& cell_base_host, int ld,
-                            const uint8_t* flags, const int* cells, const int* cell_base, int* count, int* start, int* fill, int* order,
+                            const uint8_t* flags, const int* cells, const int* cell_base, DevBuf<int>& count, int* start, DevBuf<int>& fill, int* order,
                             double* Hdd, int rig_row_first, const double* det_scale, double* bd, hipStream_t s);
 // exclusive scan of n counts into n + 1 starts (one workgroup; the counting sorts of kernels_obs.hip and kernels_fit.hip)
 int launch_exclusive_scan(const int* count, int n, int* start, hipStream_t s);
@@ -230,7 +189,7 @@ int launch_update_direction_grid(const double* in, const double* x, int G, doubl
 // ---- kernels_fit.hip (grid-only LM) ----
 int launch_fit_pass(bool jac, int gw, int gh, const double* grid, const double* tang, int64_t n, const double* gp,
                     const double* dirs, double* cost_vec, double* rec, int* keys, int* status, hipStream_t s);
-int launch_fit_accumulate(int gw, int gh, int64_t n, const double* rec, const int* keys, int* count, int* start, int* fill,
+int launch_fit_accumulate(int gw, int gh, int64_t n, const double* rec, const int* keys, DevBuf<int>& count, int* start, DevBuf<int>& fill,
                           int* order, double* H, int ld, double* b, hipStream_t s);
 int launch_fit_set_rhs(double* S, int ld, const double* b, int n, hipStream_t s);
 int launch_fit_diag_sum(const double* H, int ld, int n, double* out, hipStream_t s);
@@ -395,7 +354,7 @@ int schur_chunk_count(int n_pad);
 void schur_chunk_order(const unsigned long long* mask_host, int n_pad, int Kpad, int* order);
 int schur_mask_words(int Kpad);
 int schur_slab_rows();
-int launch_touch_mask(const double* B, int Kpad, int n_pad, int ld, unsigned long long* mask, hipStream_t s);
+int launch_touch_mask(const double* B, int Kpad, int n_pad, int ld, DevBuf<unsigned long long>& mask, hipStream_t s);
 int launch_finish_diag(double* S, int ld, int n_real, int n_pad, double lambda, hipStream_t s);
 int launch_diag_sum(const double* Dblk, int bs, int nb, const double* Hdd, int ld, int dd, double* out, hipStream_t s);
 int64_t packed_upper_doubles(int n_pad);
@@ -417,7 +376,6 @@ struct LdltWorkspace {
   // stream; users: the exchanges of the distributed variant, the Jacobian pass' side work (cba_passes.hip)
   hipStream_t panel_stream = nullptr, mid_stream = nullptr, far_stream = nullptr;
   Event ev_strip, ev_mid;
-  size_t n_alloc = 0;
   // kernel-only timing of the 128 x 128 GEMM launches of the factorisation (bulk and row-strip updates): event pairs
   // on the stream of each launch, read back by the caller after the step (ldlt_collect_spans)
   struct Span { Event e0, e1; double flops = 0; bool masked_update = false; };
@@ -488,11 +446,11 @@ int launch_gf_form(double* F, int ldf, int Gf, int n_rp, int n_border, const int
                    const double* B, const double* Dblk, const double* bblk, double lambda, const int* tiles, int n_tiles,
                    const unsigned long long* act, int act_words, hipStream_t s);
 int launch_gf_activity(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
-                       int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
+                       int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, DevBuf<unsigned long long>& act,
                        unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
                        int mask_words, hipStream_t s);
 int launch_gf_touch(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
-                    int n_rp, int rig_dof, int n_tiles, int words, int slot0, unsigned long long* act, hipStream_t s);
+                    int n_rp, int rig_dof, int n_tiles, int words, int slot0, DevBuf<unsigned long long>& act, hipStream_t s);
 int launch_gf_close_masks(int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
                           unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
                           int mask_words, hipStream_t s);

@@ -75,16 +75,16 @@ extern "C" int cba_model_localization_accuracy(cba_model* gt, cba_model* compare
     const size_t n = (size_t)std::min<int64_t>(chunk, T - at), ns = n * (size_t)P;
     a.first_trial = options->first_trial + at; a.n_trials = (int)n;
     CBA_TRY(launch_localize(a, nullptr));
-    CBA_HIP(hipMemcpy(errors.data() + at, d_errors, sizeof(float) * n, hipMemcpyDeviceToHost));
-    CBA_HIP(hipMemcpy(angles.data() + at, d_angles, sizeof(double) * n, hipMemcpyDeviceToHost));
-    CBA_HIP(hipMemcpy(flags.data() + at, d_flags, n, hipMemcpyDeviceToHost));
-    if (o.poses) CBA_HIP(hipMemcpy(o.poses + 7 * at, d_poses, sizeof(double) * 7 * n, hipMemcpyDeviceToHost));
-    if (o.iterations) CBA_HIP(hipMemcpy(o.iterations + at, d_iterations, sizeof(int) * n, hipMemcpyDeviceToHost));
-    if (o.candidates_used) CBA_HIP(hipMemcpy(o.candidates_used + at, d_used, sizeof(int) * n, hipMemcpyDeviceToHost));
-    if (o.pixels) CBA_HIP(hipMemcpy(o.pixels + 2 * at * P, d_pixels, sizeof(float) * 2 * ns, hipMemcpyDeviceToHost));
-    if (o.distances) CBA_HIP(hipMemcpy(o.distances + at * P, d_distances, sizeof(float) * ns, hipMemcpyDeviceToHost));
-    if (o.points) CBA_HIP(hipMemcpy(o.points + 3 * at * P, d_points, sizeof(double) * 3 * ns, hipMemcpyDeviceToHost));
-    if (o.bearings) CBA_HIP(hipMemcpy(o.bearings + 3 * at * P, d_bearings, sizeof(double) * 3 * ns, hipMemcpyDeviceToHost));
+    CBA_TRY(d_errors.download(errors.data() + at, n));
+    CBA_TRY(d_angles.download(angles.data() + at, n));
+    CBA_TRY(d_flags.download(flags.data() + at, n));
+    if (o.poses) CBA_TRY(d_poses.download(o.poses + 7 * at, 7 * n));
+    if (o.iterations) CBA_TRY(d_iterations.download(o.iterations + at, n));
+    if (o.candidates_used) CBA_TRY(d_used.download(o.candidates_used + at, n));
+    if (o.pixels) CBA_TRY(d_pixels.download(o.pixels + 2 * at * P, 2 * ns));
+    if (o.distances) CBA_TRY(d_distances.download(o.distances + at * P, ns));
+    if (o.points) CBA_TRY(d_points.download(o.points + 3 * at * P, 3 * ns));
+    if (o.bearings) CBA_TRY(d_bearings.download(o.bearings + 3 * at * P, 3 * ns));
   }
   if (o.errors) std::copy(errors.begin(), errors.end(), o.errors);
   if (o.rotation_angles) std::copy(angles.begin(), angles.end(), o.rotation_angles);

@@ -15,18 +15,6 @@ constexpr int kDefaultMinMatches = 7, kDefaultMinInliers = 4, kDefaultIterations
 
 int fail(const char* what) { set_error(std::string("cba_model_localize_images: ") + what); return CBA_ERR_ARG; }
 
-template <typename T>
-int upload(DevBuf<T>& d, const T* host, size_t n) {
-  CBA_TRY(d.alloc(n));
-  if (n) CBA_HIP(hipMemcpy(d, host, sizeof(T) * n, hipMemcpyHostToDevice));
-  return CBA_OK;
-}
-template <typename T>
-int download(T* host, const T* dev, size_t n) {
-  if (host && n) CBA_HIP(hipMemcpy(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost));
-  return CBA_OK;
-}
-
 }  // namespace
 
 extern "C" int cba_model_localize_images(const cba_localize_images_input* in, const cba_localize_images_options* options,
@@ -67,26 +55,25 @@ extern "C" int cba_model_localize_images(const cba_localize_images_input* in, co
   std::vector<unsigned long long> ids(in->slot_id, in->slot_id + S);
   DevBuf<const CamDev*> d_models; DevBuf<int> d_sizes, d_slot_model, d_start, d_fslot; DevBuf<unsigned long long> d_id;
   DevBuf<float> d_pixels; DevBuf<double> d_points, d_start_poses; DevBuf<uint8_t> d_candidate;
-  CBA_TRY(upload(d_models, cams.data(), cams.size()));
-  CBA_TRY(upload(d_sizes, sizes.data(), sizes.size()));
-  CBA_TRY(upload(d_slot_model, in->slot_model, (size_t)S));
-  CBA_TRY(upload(d_start, in->feature_start, (size_t)S + 1));
-  CBA_TRY(upload(d_fslot, feature_slot.data(), (size_t)F));
-  CBA_TRY(upload(d_id, ids.data(), (size_t)S));
-  CBA_TRY(upload(d_pixels, in->pixels, 2 * (size_t)F));
-  CBA_TRY(upload(d_points, in->points, 3 * (size_t)F));
-  CBA_TRY(upload(d_candidate, in->candidate, (size_t)F));
-  if (in->start_poses) CBA_TRY(upload(d_start_poses, in->start_poses, 12 * (size_t)S));
+  CBA_TRY(d_models.assign(cams));
+  CBA_TRY(d_sizes.assign(sizes));
+  CBA_TRY(d_slot_model.assign(in->slot_model, (size_t)S));
+  CBA_TRY(d_start.assign(in->feature_start, (size_t)S + 1));
+  CBA_TRY(d_fslot.assign(feature_slot));
+  CBA_TRY(d_id.assign(ids));
+  CBA_TRY(d_pixels.assign(in->pixels, 2 * (size_t)F));
+  CBA_TRY(d_points.assign(in->points, 3 * (size_t)F));
+  CBA_TRY(d_candidate.assign(in->candidate, (size_t)F));
+  if (in->start_poses) CBA_TRY(d_start_poses.assign(in->start_poses, 12 * (size_t)S));
 
   DevBuf<double> d_bearings, d_hyp, d_poses, d_cost;
   DevBuf<uint8_t> d_valid, d_in_fit, d_flags;
   DevBuf<int> d_list, d_samples, d_counts;      // d_counts: six per-slot int arrays side by side
-  CBA_TRY(d_bearings.alloc(3 * (size_t)F)); CBA_TRY(d_valid.alloc((size_t)F)); CBA_TRY(d_list.alloc((size_t)F)); CBA_TRY(d_in_fit.alloc((size_t)F));
-  CBA_HIP(hipMemset(d_list, 0xFF, sizeof(int) * (size_t)F));
-  CBA_HIP(hipMemset(d_in_fit, 0, (size_t)F));
+  CBA_TRY(d_bearings.alloc(3 * (size_t)F)); CBA_TRY(d_valid.alloc((size_t)F)); CBA_TRY(d_list.alloc((size_t)F)); CBA_TRY(d_in_fit.alloc_zero((size_t)F));
+  CBA_TRY(d_list.fill_bytes(0xFF, d_list.size()));
   const size_t ns = (size_t)S * (size_t)H * 4;
-  if (o.samples) { CBA_TRY(d_samples.alloc(ns)); CBA_HIP(hipMemset(d_samples, 0xFF, sizeof(int) * ns)); }
-  if (o.hypothesis_poses) { CBA_TRY(d_hyp.alloc(12 * (size_t)S)); CBA_HIP(hipMemset(d_hyp, 0xFF, sizeof(double) * 12 * (size_t)S)); }
+  if (o.samples) { CBA_TRY(d_samples.alloc(ns)); CBA_TRY(d_samples.fill_bytes(0xFF, ns)); }
+  if (o.hypothesis_poses) { CBA_TRY(d_hyp.alloc(12 * (size_t)S)); CBA_TRY(d_hyp.fill_bytes(0xFF, d_hyp.size())); }
   CBA_TRY(d_poses.alloc(7 * (size_t)S)); CBA_TRY(d_cost.alloc((size_t)S)); CBA_TRY(d_flags.alloc((size_t)S)); CBA_TRY(d_counts.alloc(6 * (size_t)S));
 
   LocalizeImagesArgs a{};
@@ -107,19 +94,19 @@ extern "C" int cba_model_localize_images(const cba_localize_images_input* in, co
   CBA_TRY(launch_localize_images(a, nullptr));
   CBA_HIP(hipDeviceSynchronize());
 
-  CBA_TRY(download(o.image_tr_global, (const double*)d_poses, 7 * (size_t)S));
-  CBA_TRY(download(o.flags, (const uint8_t*)d_flags, (size_t)S));
-  CBA_TRY(download(o.match_count, (const int*)a.match_count, (size_t)S));
-  CBA_TRY(download(o.list_length, (const int*)a.list_length, (size_t)S));
-  CBA_TRY(download(o.best_hypothesis, (const int*)a.best_hypothesis, (size_t)S));
-  CBA_TRY(download(o.best_inliers, (const int*)a.best_inliers, (size_t)S));
-  CBA_TRY(download(o.inliers_after_refinement, (const int*)a.inliers_after_refinement, (size_t)S));
-  CBA_TRY(download(o.iterations, (const int*)a.iterations, (size_t)S));
-  CBA_TRY(download(o.final_cost, (const double*)d_cost, (size_t)S));
-  CBA_TRY(download(o.bearings, (const double*)d_bearings, 3 * (size_t)F));
-  CBA_TRY(download(o.valid, (const uint8_t*)d_valid, (size_t)F));
-  CBA_TRY(download(o.list, (const int*)d_list, (size_t)F));
-  CBA_TRY(download(o.samples, (const int*)d_samples, ns));
-  CBA_TRY(download(o.hypothesis_poses, (const double*)d_hyp, 12 * (size_t)S));
-  return CBA_OK;
+  const size_t nS = (size_t)S;
+  CBA_TRY(d_poses.download_optional(o.image_tr_global, 7 * nS));
+  CBA_TRY(d_flags.download_optional(o.flags, nS));
+  CBA_TRY(d_counts.download_optional(o.match_count, nS, 0));
+  CBA_TRY(d_counts.download_optional(o.list_length, nS, nS));
+  CBA_TRY(d_counts.download_optional(o.best_hypothesis, nS, 2 * nS));
+  CBA_TRY(d_counts.download_optional(o.best_inliers, nS, 3 * nS));
+  CBA_TRY(d_counts.download_optional(o.inliers_after_refinement, nS, 4 * nS));
+  CBA_TRY(d_counts.download_optional(o.iterations, nS, 5 * nS));
+  CBA_TRY(d_cost.download_optional(o.final_cost, nS));
+  CBA_TRY(d_bearings.download_optional(o.bearings, 3 * (size_t)F));
+  CBA_TRY(d_valid.download_optional(o.valid, (size_t)F));
+  CBA_TRY(d_list.download_optional(o.list, (size_t)F));
+  CBA_TRY(d_samples.download_optional(o.samples, ns));
+  return d_hyp.download_optional(o.hypothesis_poses, 12 * nS);
 }

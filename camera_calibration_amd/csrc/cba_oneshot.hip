@@ -11,17 +11,13 @@ using namespace cba;
 extern "C" {
 
 // ---- model-level entry points: device-resident camera model -----------------------------------------
-static int model_reserve(cba_model* m, int64_t n) {
-  if (n <= m->cap) return CBA_OK;
-  m->cap = 0;
-  const int64_t cap = n < 256 ? 256 : n;
-  CBA_TRY(m->d_a.alloc(3 * (size_t)cap));     // local points / pixels (in)
-  CBA_TRY(m->d_b.alloc(6 * (size_t)cap));     // pixels / lines (out)
-  CBA_TRY(m->d_c.alloc(2 * (size_t)cap));     // initial pixels
-  CBA_TRY(m->d_j.alloc(12 * (size_t)cap));    // un-projection Jacobians
-  CBA_TRY(m->d_ok.alloc((size_t)cap));
-  m->cap = cap;
-  return CBA_OK;
+static int model_reserve(cba_model* m, int64_t n) {      // scratch, grown on demand
+  const size_t cap = n < 256 ? 256 : (size_t)n;
+  CBA_TRY(m->d_a.reserve(3 * cap));     // local points / pixels (in)
+  CBA_TRY(m->d_b.reserve(6 * cap));     // pixels / lines (out)
+  CBA_TRY(m->d_c.reserve(2 * cap));     // initial pixels
+  CBA_TRY(m->d_j.reserve(12 * cap));    // un-projection Jacobians
+  return m->d_ok.reserve(cap);
 }
 void cba_model_destroy(cba_model* m) {
   if (!m) return;
@@ -32,9 +28,7 @@ void cba_model_destroy(cba_model* m) {
 int cba_model_set_grid(cba_model* m, const double* grid) {
   if (!m || !grid) { set_error("cba_model_set_grid: bad argument"); return CBA_ERR_ARG; }
   CBA_HIP(hipSetDevice(m->device));
-  const size_t G = (size_t)m->cam.grid_w * m->cam.grid_h;
-  CBA_HIP(hipMemcpy(m->d_grid, grid, doubles_per_point(m->cam.model_type) * G * sizeof(double), hipMemcpyHostToDevice));
-  return CBA_OK;
+  return m->d_grid.upload(grid, m->d_grid.size());
 }
 int cba_model_create(const cba_camera* camera, const double* grid, int32_t device, cba_model** out) {
   if (!camera || !grid || !out || !camera_ok(*camera)) { set_error("bad camera / grid"); return CBA_ERR_ARG; }
@@ -45,8 +39,7 @@ int cba_model_create(const cba_camera* camera, const double* grid, int32_t devic
   CBA_TRY(m->d_grid.alloc(doubles_per_point(camera->model_type) * G));
   CBA_TRY(cba_model_set_grid(m.get(), grid));
   CamDev h = make_camdev(*camera, m->d_grid, nullptr, 0);
-  CBA_TRY(m->d_cam.alloc(1));
-  CBA_HIP(hipMemcpy(m->d_cam, &h, sizeof(CamDev), hipMemcpyHostToDevice));
+  CBA_TRY(m->d_cam.assign(&h, 1));
   *out = m.release();
   return CBA_OK;
 }
@@ -55,23 +48,22 @@ int cba_model_project(cba_model* m, int64_t n, const double* local_points, const
   if (n == 0) return CBA_OK;
   CBA_HIP(hipSetDevice(m->device));
   CBA_TRY(model_reserve(m, n));
-  CBA_HIP(hipMemcpy(m->d_a, local_points, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
-  if (init_pixels) CBA_HIP(hipMemcpy(m->d_c, init_pixels, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+  CBA_TRY(m->d_a.upload(local_points, 3 * (size_t)n));
+  if (init_pixels) CBA_TRY(m->d_c.upload(init_pixels, 2 * (size_t)n));
   CBA_TRY(launch_project_points(m->d_cam, m->cam.model_type, n, m->d_a, init_pixels ? (const double*)m->d_c : nullptr, m->d_b, m->d_ok, nullptr));
-  CBA_HIP(hipMemcpy(pixels, m->d_b, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
-  CBA_HIP(hipMemcpy(ok, m->d_ok, (size_t)n, hipMemcpyDeviceToHost));
-  return CBA_OK;
+  CBA_TRY(m->d_b.download(pixels, 2 * (size_t)n));
+  return m->d_ok.download(ok, (size_t)n);
 }
 int cba_model_unproject(cba_model* m, int64_t n, const double* pixels, double* lines, double* jacobians, uint8_t* ok) {
   if (!m || n < 0 || (n > 0 && (!pixels || !lines || !ok))) { set_error("cba_model_unproject: bad argument"); return CBA_ERR_ARG; }
   if (n == 0) return CBA_OK;
   CBA_HIP(hipSetDevice(m->device));
   CBA_TRY(model_reserve(m, n));
-  CBA_HIP(hipMemcpy(m->d_a, pixels, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+  CBA_TRY(m->d_a.upload(pixels, 2 * (size_t)n));
   CBA_TRY(launch_unproject(m->d_cam, m->cam.model_type, n, m->d_a, m->d_b, jacobians ? (double*)m->d_j : nullptr, m->d_ok, nullptr));
-  CBA_HIP(hipMemcpy(lines, m->d_b, sizeof(double) * 6 * n, hipMemcpyDeviceToHost));
-  CBA_HIP(hipMemcpy(ok, m->d_ok, (size_t)n, hipMemcpyDeviceToHost));
-  if (jacobians) CBA_HIP(hipMemcpy(jacobians, m->d_j, sizeof(double) * 12 * n, hipMemcpyDeviceToHost));
+  CBA_TRY(m->d_b.download(lines, 6 * (size_t)n));
+  CBA_TRY(m->d_ok.download(ok, (size_t)n));
+  if (jacobians) CBA_TRY(m->d_j.download(jacobians, 12 * (size_t)n));
   return CBA_OK;
 }
 
@@ -96,6 +88,38 @@ int cba_unproject(const cba_camera* camera, const double* grid, int64_t n, const
   return rc;
 }
 
+// Device copy of a host-supplied system (block_diag_H, off_diag_H, dense_H, block_diag_b, dense_b) in the engine's padded layout, with
+// the buffers of its reduced system S.  Kpad: the rows of B rounded up to k_multiple; everything the uploads leave out is zero.
+struct HostSchurSystem {
+  const int bs, nb, dd, bdof;
+  int n_pad, n_fact, ld, Kpad;
+  DevBuf<double> Dblk, bblk, Dinv, dinvb, B, W, Hdd, bd, S, gws; DevBuf<int> status;
+  HostSchurSystem(int block_size, int n_blocks, int dense_dof, int k_multiple)
+      : bs(block_size), nb(n_blocks), dd(dense_dof), bdof(bs * nb), Kpad(round_up(bdof, k_multiple)) {
+    padded_dims(dd, &n_pad, &n_fact);
+    ld = n_pad;
+  }
+  int load(int gemv_t_doubles, const double* block_diag_H, const double* off_diag_H, const double* dense_H, const double* block_diag_b,
+           const double* dense_b) {
+    CBA_TRY(gws.alloc((size_t)gemv_t_doubles));
+    CBA_TRY(bblk.assign(block_diag_b, (size_t)bdof)); CBA_TRY(Dinv.alloc((size_t)nb * bs * bs));
+    CBA_TRY(dinvb.alloc_zero((size_t)Kpad)); CBA_TRY(B.alloc_zero((size_t)Kpad * ld)); CBA_TRY(W.alloc_zero((size_t)Kpad * ld));
+    CBA_TRY(Hdd.alloc_zero((size_t)ld * ld)); CBA_TRY(bd.alloc_zero((size_t)ld)); CBA_TRY(S.alloc_zero((size_t)ld * ld));
+    CBA_TRY(status.alloc_zero(1));
+    // upper triangles only: the reference fills lower triangles with NaN in its golden test, so copy and scrub
+    std::vector<double> hD(block_diag_H, block_diag_H + (size_t)nb * bs * bs), hH((size_t)dd * dd);
+    for (int b = 0; b < nb; ++b)
+      for (int r = 0; r < bs; ++r)
+        for (int c = 0; c < r; ++c) hD[(size_t)b * bs * bs + r * bs + c] = 0.0;
+    for (int r = 0; r < dd; ++r)
+      for (int c = 0; c < dd; ++c) hH[(size_t)r * dd + c] = (c >= r) ? dense_H[(size_t)r * dd + c] : 0.0;
+    CBA_TRY(Dblk.assign(hD));
+    CBA_HIP(hipMemcpy2D(B, ld * sizeof(double), off_diag_H, dd * sizeof(double), dd * sizeof(double), bdof, hipMemcpyHostToDevice));
+    CBA_HIP(hipMemcpy2D(Hdd, ld * sizeof(double), hH.data(), dd * sizeof(double), dd * sizeof(double), dd, hipMemcpyHostToDevice));
+    return bd.upload(dense_b, (size_t)dd);
+  }
+};
+
 int cba_schur_solve(int32_t block_size, int32_t n_blocks, int32_t dense_dof, const double* block_diag_H,
                     const double* off_diag_H, const double* dense_H, const double* block_diag_b,
                     const double* dense_b, double* x, int32_t device) {
@@ -107,48 +131,28 @@ int cba_schur_solve_opt(int32_t block_size, int32_t n_blocks, int32_t dense_dof,
   if (block_size < 1 || block_size > 6 || n_blocks < 1 || dense_dof < 1 || !block_diag_H || !off_diag_H || !dense_H ||
       !block_diag_b || !dense_b || !x) { set_error("cba_schur_solve: bad argument"); return CBA_ERR_ARG; }
   CBA_TRY(select_device(device, ""));
-  const int bs = block_size, nb = n_blocks, dd = dense_dof, bdof = bs * nb;
-  int n_pad, n_fact; padded_dims(dd, &n_pad, &n_fact);
-  const int ld = n_pad, Kpad = round_up(bdof, 16);
-  DevBuf<double> Dblk, bblk, Dinv, dinvb, B, W, Hdd, bd, S, xd, gws; DevBuf<int> status;
-  CBA_TRY(gws.alloc((size_t)gemv_t_workspace_doubles(dd)));
-  CBA_TRY(Dblk.alloc((size_t)nb * bs * bs)); CBA_TRY(bblk.alloc((size_t)bdof)); CBA_TRY(Dinv.alloc((size_t)nb * bs * bs));
-  CBA_TRY(dinvb.alloc((size_t)Kpad)); CBA_TRY(B.alloc((size_t)Kpad * ld)); CBA_TRY(W.alloc((size_t)Kpad * ld));
-  CBA_TRY(Hdd.alloc((size_t)ld * ld)); CBA_TRY(bd.alloc((size_t)ld)); CBA_TRY(S.alloc((size_t)ld * ld));
-  CBA_TRY(xd.alloc((size_t)bdof + ld)); CBA_TRY(status.alloc(1));
-  CBA_HIP(hipMemset(B, 0, sizeof(double) * (size_t)Kpad * ld)); CBA_HIP(hipMemset(W, 0, sizeof(double) * (size_t)Kpad * ld));
-  CBA_HIP(hipMemset(Hdd, 0, sizeof(double) * (size_t)ld * ld)); CBA_HIP(hipMemset(S, 0, sizeof(double) * (size_t)ld * ld));
-  CBA_HIP(hipMemset(bd, 0, sizeof(double) * ld)); CBA_HIP(hipMemset(status, 0, sizeof(int))); CBA_HIP(hipMemset(dinvb, 0, sizeof(double) * Kpad));
-  CBA_HIP(hipMemset(xd, 0, sizeof(double) * ((size_t)bdof + ld)));
-  // upper triangles only: the reference fills lower triangles with NaN in its golden test, so copy and scrub
-  std::vector<double> hD(block_diag_H, block_diag_H + (size_t)nb * bs * bs), hH((size_t)dd * dd);
-  for (int b = 0; b < nb; ++b)
-    for (int r = 0; r < bs; ++r)
-      for (int c = 0; c < r; ++c) hD[(size_t)b * bs * bs + r * bs + c] = 0.0;
-  for (int r = 0; r < dd; ++r)
-    for (int c = 0; c < dd; ++c) hH[(size_t)r * dd + c] = (c >= r) ? dense_H[(size_t)r * dd + c] : 0.0;
-  CBA_HIP(hipMemcpy(Dblk, hD.data(), sizeof(double) * hD.size(), hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(bblk, block_diag_b, sizeof(double) * bdof, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy2D(B, ld * sizeof(double), off_diag_H, dd * sizeof(double), dd * sizeof(double), bdof, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy2D(Hdd, ld * sizeof(double), hH.data(), dd * sizeof(double), dd * sizeof(double), dd, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(bd, dense_b, sizeof(double) * dd, hipMemcpyHostToDevice));
+  HostSchurSystem y(block_size, n_blocks, dense_dof, 16);
+  const int bs = y.bs, nb = y.nb, dd = y.dd, bdof = y.bdof, n_pad = y.n_pad, n_fact = y.n_fact, ld = y.ld, Kpad = y.Kpad;
+  CBA_TRY(y.load(gemv_t_workspace_doubles(dd), block_diag_H, off_diag_H, dense_H, block_diag_b, dense_b));
+  DevBuf<double> xd;
+  CBA_TRY(xd.alloc_zero((size_t)bdof + ld));
   LdltWorkspace w;
   CBA_TRY(ldlt_workspace_alloc(w, n_pad));
   apply_solver_options(w, options);
-  CBA_HIP(hipMemset(w.status, 0, sizeof(int)));
+  CBA_TRY(w.status.zero());
   hipStream_t s = nullptr;
-  CBA_TRY(launch_block_inverse(Dblk, bblk, 0.0, bs, nb, Dinv, dinvb, status, s));
-  CBA_TRY(launch_dinv_times_B_ld(Dinv, B, bs, nb, dd, ld, W, s));
-  CBA_TRY(schur_gemm(B, W, Kpad, ld, Hdd, S, n_pad, ld, dd, 1, 0.0, nullptr, s, nullptr, -1));
-  CBA_TRY(launch_gemv_t_strided(B, bdof, dd, ld, dinvb, bd, S + (ld - 1), ld, gws, s));
-  CBA_TRY(ldlt_factor(S, n_fact, ld, w, s, nullptr));
-  CBA_TRY(ldlt_back_solve(S, n_fact, ld, ld - 1, w, xd + bdof, s));
-  CBA_TRY(launch_gemv_n(W, bdof, dd, ld, xd + bdof, dinvb, xd, s));
+  CBA_TRY(launch_block_inverse(y.Dblk, y.bblk, 0.0, bs, nb, y.Dinv, y.dinvb, y.status, s));
+  CBA_TRY(launch_dinv_times_B_ld(y.Dinv, y.B, bs, nb, dd, ld, y.W, s));
+  CBA_TRY(schur_gemm(y.B, y.W, Kpad, ld, y.Hdd, y.S, n_pad, ld, dd, 1, 0.0, nullptr, s, nullptr, -1));
+  CBA_TRY(launch_gemv_t_strided(y.B, bdof, dd, ld, y.dinvb, y.bd, y.S + (ld - 1), ld, y.gws, s));
+  CBA_TRY(ldlt_factor(y.S, n_fact, ld, w, s, nullptr));
+  CBA_TRY(ldlt_back_solve(y.S, n_fact, ld, ld - 1, w, xd + bdof, s));
+  CBA_TRY(launch_gemv_n(y.W, bdof, dd, ld, xd + bdof, y.dinvb, xd, s));
   CBA_HIP(hipDeviceSynchronize());
   int st[2];
-  CBA_HIP(hipMemcpy(&st[0], status, sizeof(int), hipMemcpyDeviceToHost));
-  CBA_HIP(hipMemcpy(&st[1], w.status, sizeof(int), hipMemcpyDeviceToHost));
-  CBA_HIP(hipMemcpy(x, xd, sizeof(double) * (bdof + dd), hipMemcpyDeviceToHost));
+  CBA_TRY(y.status.download(&st[0], 1));
+  CBA_TRY(w.status.download(&st[1], 1));
+  CBA_TRY(xd.download(x, (size_t)bdof + dd));
   if (st[1] == 3) { set_error("cba_schur_solve: a dataflow launch of the factorisation timed out"); return CBA_ERR_TIMEOUT; }
   if (st[0] || st[1]) { set_error("cba_schur_solve: zero pivot"); return CBA_ERR_NUMERIC; }
   return CBA_OK;
@@ -161,59 +165,38 @@ int cba_debug_reduced_system(int32_t block_size, int32_t n_blocks, int32_t dense
   if (block_size < 1 || block_size > 6 || n_blocks < 1 || dense_dof < 1 || mode < 0 || mode > 2 || !dims) {
     set_error("cba_debug_reduced_system: bad argument"); return CBA_ERR_ARG;
   }
-  const int bs = block_size, nb = n_blocks, dd = dense_dof, bdof = bs * nb;
-  int n_pad, n_fact; padded_dims(dd, &n_pad, &n_fact);
-  const int ld = n_pad, Kpad = round_up(bdof, 48);          // as cba_create: a multiple of the dense K slab and of the block-sparse one
+  HostSchurSystem y(block_size, n_blocks, dense_dof, 48);    // as cba_create: a multiple of the dense K slab and of the block-sparse one
+  const int bs = y.bs, nb = y.nb, dd = y.dd, bdof = y.bdof, n_pad = y.n_pad, ld = y.ld, Kpad = y.Kpad;
   const int mask_tiles = n_pad / 128, mask_words = schur_mask_words(Kpad), n_chunks = schur_chunk_count(n_pad);
   dims[0] = n_pad; dims[1] = Kpad; dims[2] = mask_words; dims[3] = n_chunks;
   if (!S_out) return CBA_OK;
   if (!block_diag_H || !off_diag_H || !dense_H || !block_diag_b || !dense_b) { set_error("cba_debug_reduced_system: bad argument"); return CBA_ERR_ARG; }
   CBA_TRY(select_device(device, ""));
-  DevBuf<double> Dblk, bblk, Dinv, dinvb, B, W, Hdd, bd, S, gws; DevBuf<int> status, order; DevBuf<unsigned long long> kmask;
-  CBA_TRY(gws.alloc((size_t)gemv_t_workspace_doubles(n_pad)));
-  CBA_TRY(Dblk.alloc((size_t)nb * bs * bs)); CBA_TRY(bblk.alloc((size_t)bdof)); CBA_TRY(Dinv.alloc((size_t)nb * bs * bs));
-  CBA_TRY(dinvb.alloc((size_t)Kpad)); CBA_TRY(B.alloc((size_t)Kpad * ld)); CBA_TRY(W.alloc((size_t)Kpad * ld));
-  CBA_TRY(Hdd.alloc((size_t)ld * ld)); CBA_TRY(bd.alloc((size_t)ld)); CBA_TRY(S.alloc((size_t)ld * ld)); CBA_TRY(status.alloc(1));
-  CBA_TRY(kmask.alloc((size_t)mask_tiles * mask_words));
-  if (n_chunks > 0) CBA_TRY(order.alloc((size_t)n_chunks));
-  CBA_HIP(hipMemset(B, 0, sizeof(double) * (size_t)Kpad * ld)); CBA_HIP(hipMemset(W, 0, sizeof(double) * (size_t)Kpad * ld));
-  CBA_HIP(hipMemset(Hdd, 0, sizeof(double) * (size_t)ld * ld)); CBA_HIP(hipMemset(S, 0, sizeof(double) * (size_t)ld * ld));
-  CBA_HIP(hipMemset(bd, 0, sizeof(double) * ld)); CBA_HIP(hipMemset(status, 0, sizeof(int))); CBA_HIP(hipMemset(dinvb, 0, sizeof(double) * Kpad));
-  CBA_HIP(hipMemset(kmask, 0, sizeof(unsigned long long) * (size_t)mask_tiles * mask_words));
-  // upper triangles only, as cba_schur_solve_opt
-  std::vector<double> hD(block_diag_H, block_diag_H + (size_t)nb * bs * bs), hH((size_t)dd * dd);
-  for (int b = 0; b < nb; ++b)
-    for (int r = 0; r < bs; ++r)
-      for (int c = 0; c < r; ++c) hD[(size_t)b * bs * bs + r * bs + c] = 0.0;
-  for (int r = 0; r < dd; ++r)
-    for (int c = 0; c < dd; ++c) hH[(size_t)r * dd + c] = (c >= r) ? dense_H[(size_t)r * dd + c] : 0.0;
-  CBA_HIP(hipMemcpy(Dblk, hD.data(), sizeof(double) * hD.size(), hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(bblk, block_diag_b, sizeof(double) * bdof, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy2D(B, ld * sizeof(double), off_diag_H, dd * sizeof(double), dd * sizeof(double), bdof, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy2D(Hdd, ld * sizeof(double), hH.data(), dd * sizeof(double), dd * sizeof(double), dd, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(bd, dense_b, sizeof(double) * dd, hipMemcpyHostToDevice));
+  CBA_TRY(y.load(gemv_t_workspace_doubles(n_pad), block_diag_H, off_diag_H, dense_H, block_diag_b, dense_b));
+  DevBuf<int> order; DevBuf<unsigned long long> kmask;
+  CBA_TRY(kmask.alloc_zero((size_t)mask_tiles * mask_words));
   hipStream_t s = nullptr;
-  std::vector<unsigned long long> hmask((size_t)mask_tiles * mask_words, 0ull);
+  std::vector<unsigned long long> hmask(kmask.size(), 0ull);
   const int* chunk_order = nullptr;
   if (mode >= 1) {
-    CBA_TRY(launch_touch_mask(B, Kpad, n_pad, ld, kmask, s));              // (the engine: at the end of the Jacobian pass)
-    CBA_HIP(hipMemcpy(hmask.data(), kmask, sizeof(unsigned long long) * hmask.size(), hipMemcpyDeviceToHost));
+    CBA_TRY(launch_touch_mask(y.B, Kpad, n_pad, ld, kmask, s));              // (the engine: at the end of the Jacobian pass)
+    CBA_TRY(kmask.download(hmask.data(), hmask.size()));
     if (mode == 2 && n_chunks > 0) {                                        // (the engine: posefirst_finish, from the pinned copy of the masks)
       std::vector<int> horder((size_t)n_chunks);
       schur_chunk_order(hmask.data(), n_pad, Kpad, horder.data());
-      CBA_HIP(hipMemcpy(order, horder.data(), sizeof(int) * (size_t)n_chunks, hipMemcpyHostToDevice));
+      CBA_TRY(order.assign(horder));
       chunk_order = order;
     }
   }
-  CBA_TRY(launch_block_inverse(Dblk, bblk, lambda, bs, nb, Dinv, dinvb, status, s));
-  CBA_TRY(launch_gemv_t_partial(B, bdof, dd, ld, dinvb, gws, s));
-  CBA_TRY(launch_gemv_t_final(dd, bd, S + (ld - 1), ld, gws, n_pad, s));
-  CBA_TRY(launch_dinv_times_B_ld(Dinv, B, bs, nb, dd, ld, W, s));
-  CBA_TRY(schur_gemm(B, W, Kpad, ld, Hdd, S, n_pad, ld, dd, 1, lambda, mode >= 1 ? (const unsigned long long*)kmask : nullptr, s, chunk_order, ld - 1));
+  CBA_TRY(launch_block_inverse(y.Dblk, y.bblk, lambda, bs, nb, y.Dinv, y.dinvb, y.status, s));
+  CBA_TRY(launch_gemv_t_partial(y.B, bdof, dd, ld, y.dinvb, y.gws, s));
+  CBA_TRY(launch_gemv_t_final(dd, y.bd, y.S + (ld - 1), ld, y.gws, n_pad, s));
+  CBA_TRY(launch_dinv_times_B_ld(y.Dinv, y.B, bs, nb, dd, ld, y.W, s));
+  CBA_TRY(schur_gemm(y.B, y.W, Kpad, ld, y.Hdd, y.S, n_pad, ld, dd, 1, lambda, mode >= 1 ? (const unsigned long long*)kmask : nullptr, s, chunk_order, ld - 1));
   CBA_HIP(hipDeviceSynchronize());
   int st = 0;
-  CBA_HIP(hipMemcpy(&st, status, sizeof(int), hipMemcpyDeviceToHost));
-  CBA_HIP(hipMemcpy(S_out, S, sizeof(double) * (size_t)ld * ld, hipMemcpyDeviceToHost));
+  CBA_TRY(y.status.download(&st, 1));
+  CBA_TRY(y.S.download(S_out, y.S.size()));
   if (mask_out) std::memcpy(mask_out, hmask.data(), sizeof(unsigned long long) * hmask.size());   // mode 0: no masks are built, zeros
   if (st) { set_error("cba_debug_reduced_system: zero pivot"); return CBA_ERR_NUMERIC; }
   return CBA_OK;
@@ -266,27 +249,17 @@ int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n
   DevBuf<double> g[2], tang, gp, dirs, cost_ref, cost_test, rec, H, b, S, x, partials, red8, scal;
   DevBuf<int> keys, count, start, fill, order, status;
   const size_t nn = (size_t)(n > 0 ? n : 1);
-  CBA_TRY(g[0].alloc(3 * (size_t)G)); CBA_TRY(g[1].alloc(3 * (size_t)G)); CBA_TRY(tang.alloc(6 * (size_t)G));
-  CBA_TRY(gp.alloc(2 * nn)); CBA_TRY(dirs.alloc(3 * nn)); CBA_TRY(cost_ref.alloc(3 * nn)); CBA_TRY(cost_test.alloc(3 * nn));
+  CBA_TRY(g[0].assign(grid, 3 * (size_t)G)); CBA_TRY(g[1].alloc(3 * (size_t)G)); CBA_TRY(tang.alloc(6 * (size_t)G));
+  CBA_TRY(gp.alloc(2 * nn)); CBA_TRY(gp.upload(grid_points, 2 * (size_t)n)); CBA_TRY(dirs.alloc(3 * nn)); CBA_TRY(dirs.upload(directions, 3 * (size_t)n));
+  CBA_TRY(cost_ref.alloc(3 * nn)); CBA_TRY(cost_test.alloc(3 * nn));
   CBA_TRY(rec.alloc(nn * 99)); CBA_TRY(keys.alloc(nn)); CBA_TRY(order.alloc(nn));
   CBA_TRY(count.alloc((size_t)G + 1)); CBA_TRY(start.alloc((size_t)G + 1)); CBA_TRY(fill.alloc((size_t)G + 1));
   CBA_TRY(H.alloc((size_t)ld * ld)); CBA_TRY(b.alloc((size_t)ld)); CBA_TRY(S.alloc((size_t)ld * ld)); CBA_TRY(x.alloc((size_t)ld));
-  CBA_TRY(partials.alloc(256 * 8)); CBA_TRY(red8.alloc(8)); CBA_TRY(scal.alloc(8)); CBA_TRY(status.alloc(1));
-  CBA_HIP(hipMemcpy(g[0], grid, sizeof(double) * 3 * G, hipMemcpyHostToDevice));
-  if (n) {
-    CBA_HIP(hipMemcpy(gp, grid_points, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-    CBA_HIP(hipMemcpy(dirs, directions, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
-  }
-  CBA_HIP(hipMemset(status, 0, sizeof(int)));
+  CBA_TRY(partials.alloc(256 * 8)); CBA_TRY(red8.alloc(8)); CBA_TRY(scal.alloc(8)); CBA_TRY(status.alloc_zero(1));
   LdltWorkspace w;
   CBA_TRY(ldlt_workspace_alloc(w, n_pad));
   hipStream_t s = nullptr;
   CBA_TRY(make_main_stream(&s));
-  auto read = [&](const double* dev, double* host, int k) -> int {
-    CBA_HIP(hipMemcpyAsync(host, dev, sizeof(double) * k, hipMemcpyDeviceToHost, s));
-    CBA_HIP(hipStreamSynchronize(s));
-    return CBA_OK;
-  };
   int cur = 0, rc = CBA_OK;
   double lambda = -1.0, last_cost = 0.0;
   const double init_lambda_factor = (double)0.001f;
@@ -294,14 +267,14 @@ int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n
     double t0 = now_s();
     if ((rc = launch_tangents(g[cur], tang, G, s))) break;
     if ((rc = launch_fit_pass(true, gw, gh, g[cur], tang, n, gp, dirs, cost_ref, rec, keys, status, s))) break;
-    CBA_HIP(hipMemsetAsync(H, 0, sizeof(double) * (size_t)ld * ld, s));
-    CBA_HIP(hipMemsetAsync(b, 0, sizeof(double) * (size_t)ld, s));
+    CBA_TRY(H.zero_async(s));
+    CBA_TRY(b.zero_async(s));
     if ((rc = launch_fit_accumulate(gw, gh, n, rec, keys, count, start, fill, order, H, ld, b, s))) break;
     if ((rc = launch_reduce_costs(cost_ref, nullptr, nullptr, 3 * n, partials, red8, s))) break;
     if ((rc = launch_fit_diag_sum(H, ld, dof, scal, s))) break;
     double h8[8], hsum = 0; int st = 0;
-    if ((rc = read(red8, h8, 8)) || (rc = read(scal, &hsum, 1))) break;
-    CBA_HIP(hipMemcpy(&st, status, sizeof(int), hipMemcpyDeviceToHost));
+    if ((rc = red8.download_sync(h8, 8, s)) || (rc = scal.download_sync(&hsum, 1, s))) break;
+    CBA_TRY(status.download(&st, 1));
     rep.t_pass += now_s() - t0;
     if (st == 3) { set_error("cba_fit_grid_to_directions: a grid point lies outside the grid's 4x4 patches"); rc = CBA_ERR_ARG; break; }
     last_cost = h8[0];
@@ -312,21 +285,20 @@ int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n
     for (int lm = 0; lm < 10 && rc == CBA_OK; ++lm) {
       rep.lm_attempts += 1;
       t0 = now_s();
-      CBA_HIP(hipMemcpyAsync(S, H, sizeof(double) * (size_t)ld * ld, hipMemcpyDeviceToDevice, s));
+      CBA_TRY(S.copy_from_async(H, H.size(), 0, 0, s));
       if ((rc = launch_finish_diag(S, ld, dof, n_pad, lambda, s))) break;
       if ((rc = launch_fit_set_rhs(S, ld, b, dof, s))) break;
-      CBA_HIP(hipMemsetAsync(w.status, 0, sizeof(int), s));
+      CBA_TRY(w.status.zero_async(s));
       if ((rc = ldlt_factor(S, n_fact, ld, w, s, nullptr))) break;
       if ((rc = ldlt_back_solve(S, n_fact, ld, ld - 1, w, x, s))) break;
-      CBA_HIP(hipMemcpyAsync(&st, w.status, sizeof(int), hipMemcpyDeviceToHost, s));
-      CBA_HIP(hipStreamSynchronize(s));
+      CBA_TRY(w.status.download_sync(&st, 1, s));
       rep.t_solve += now_s() - t0;
       if (st != 0) { lambda = 2.f * lambda; continue; }     // zero pivot: treated like the reference's NaN update
       t0 = now_s();
       if ((rc = launch_update_direction_grid(g[cur], x, G, g[cur ^ 1], s))) break;
       if ((rc = launch_fit_pass(false, gw, gh, g[cur ^ 1], tang, n, gp, dirs, cost_test, nullptr, nullptr, status, s))) break;
       if ((rc = launch_reduce_costs(cost_ref, cost_test, nullptr, 3 * n, partials, red8, s))) break;
-      if ((rc = read(red8, h8, 8))) break;
+      if ((rc = red8.download_sync(h8, 8, s))) break;
       rep.t_pass += now_s() - t0;
       if (h8[4] > 0 && h8[3] < h8[2]) {                       // CostIsSmallerThan
         cur ^= 1;
@@ -342,7 +314,7 @@ int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n
   }
   if (rc == CBA_OK) {
     rep.final_cost = last_cost; rep.lambda = lambda;
-    if (hipMemcpy(grid, g[cur], sizeof(double) * 3 * G, hipMemcpyDeviceToHost) != hipSuccess) { set_error("cba_fit_grid_to_directions: copy back failed"); rc = CBA_ERR_HIP; }
+    rc = g[cur].download(grid, 3 * (size_t)G);
     if (report) *report = rep;
   }
   return rc;

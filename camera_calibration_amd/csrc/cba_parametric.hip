@@ -153,12 +153,10 @@ int cba_parametric_project(const cba_parametric_camera* camera, int64_t n, const
   if (n == 0) return CBA_OK;
   CBA_TRY(select_device(device, ""));
   DevBuf<double> in, out; DevBuf<uint8_t> dok;
-  CBA_TRY(in.alloc(3 * (size_t)n)); CBA_TRY(out.alloc(2 * (size_t)n)); CBA_TRY(dok.alloc((size_t)n));
-  CBA_HIP(hipMemcpy(in, local_points, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+  CBA_TRY(in.assign(local_points, 3 * (size_t)n)); CBA_TRY(out.alloc(2 * (size_t)n)); CBA_TRY(dok.alloc((size_t)n));
   CBA_TRY(launch_parametric_project(to_parcam(*camera), n, in, out, dok, nullptr));
-  CBA_HIP(hipMemcpy(pixels, out, sizeof(double) * 2 * n, hipMemcpyDeviceToHost));
-  CBA_HIP(hipMemcpy(ok, dok, (size_t)n, hipMemcpyDeviceToHost));
-  return CBA_OK;
+  CBA_TRY(out.download(pixels, out.size()));
+  return dok.download(ok, dok.size());
 }
 
 int cba_parametric_unproject(const cba_parametric_camera* camera, int64_t n, const double* pixels, double* directions, uint8_t* ok,
@@ -167,12 +165,10 @@ int cba_parametric_unproject(const cba_parametric_camera* camera, int64_t n, con
   if (n == 0) return CBA_OK;
   CBA_TRY(select_device(device, ""));
   DevBuf<double> in, out; DevBuf<uint8_t> dok;
-  CBA_TRY(in.alloc(2 * (size_t)n)); CBA_TRY(out.alloc(3 * (size_t)n)); CBA_TRY(dok.alloc((size_t)n));
-  CBA_HIP(hipMemcpy(in, pixels, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+  CBA_TRY(in.assign(pixels, 2 * (size_t)n)); CBA_TRY(out.alloc(3 * (size_t)n)); CBA_TRY(dok.alloc((size_t)n));
   CBA_TRY(launch_parametric_unproject(to_parcam(*camera), n, in, out, dok, nullptr));
-  CBA_HIP(hipMemcpy(directions, out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-  CBA_HIP(hipMemcpy(ok, dok, (size_t)n, hipMemcpyDeviceToHost));
-  return CBA_OK;
+  CBA_TRY(out.download(directions, out.size()));
+  return dok.download(ok, dok.size());
 }
 
 int cba_parametric_fit_pass(const cba_parametric_camera* camera, const double* rotation, const double* dense, int32_t dense_width,
@@ -183,9 +179,7 @@ int cba_parametric_fit_pass(const cba_parametric_camera* camera, const double* r
   CBA_TRY(select_device(device, ""));
   ParWork w;
   w.dw = dense_width; w.dh = dense_height; w.step = step;
-  const size_t nd = 3 * (size_t)dense_width * dense_height;
-  CBA_TRY(w.dense.alloc(nd));
-  CBA_HIP(hipMemcpy(w.dense, dense, sizeof(double) * nd, hipMemcpyHostToDevice));
+  CBA_TRY(w.dense.assign(dense, 3 * (size_t)dense_width * dense_height));
   w.d_dense = w.dense;
   CBA_TRY(w.alloc_common());
   const ParCam cam = to_parcam(*camera);
@@ -195,20 +189,20 @@ int cba_parametric_fit_pass(const cba_parametric_camera* camera, const double* r
   else CBA_TRY(launch_parametric_cost(a, s));
   CBA_TRY(launch_reduce_costs(w.cost_ref, nullptr, nullptr, 3 * w.n, w.red_partials, w.red8, s));
   double h8[8], sums[240];
-  CBA_HIP(hipMemcpy(h8, w.red8, sizeof(h8), hipMemcpyDeviceToHost));
+  CBA_TRY(w.red8.download(h8, 8));
   if (jacobian) {
-    CBA_HIP(hipMemcpy(sums, w.sums, sizeof(sums), hipMemcpyDeviceToHost));
+    CBA_TRY(w.sums.download(sums, 240));
     double Hh[225], bh[15];
     unpack_system(sums, 15, Hh, bh);
     if (H) std::memcpy(H, Hh, sizeof(Hh));
     if (b) std::memcpy(b, bh, sizeof(bh));
   }
   if (cost) *cost = h8[0];
-  if (cost_vector) CBA_HIP(hipMemcpy(cost_vector, w.cost_ref, sizeof(double) * 3 * w.n, hipMemcpyDeviceToHost));
-  if (flags) CBA_HIP(hipMemcpy(flags, w.flags, (size_t)w.n, hipMemcpyDeviceToHost));
+  if (cost_vector) CBA_TRY(w.cost_ref.download(cost_vector, w.cost_ref.size()));
+  if (flags) CBA_TRY(w.flags.download(flags, w.flags.size()));
   if (linear_sums) {
     CBA_TRY(launch_parametric_linear(w.d_dense, w.dw, w.dh, cam.width, cam.height, cam.equidistant, w.partials, w.sums, s));
-    CBA_HIP(hipMemcpy(linear_sums, w.sums, sizeof(double) * 30, hipMemcpyDeviceToHost));
+    CBA_TRY(w.sums.download(linear_sums, 30));
   }
   return CBA_OK;
 }
@@ -237,9 +231,8 @@ int cba_fit_parametric_to_dense_model(cba_parametric_camera* camera, const doubl
   CBA_TRY(make_main_stream(&s));
   if (dense) {
     w.dw = dense_width; w.dh = dense_height;
-    const size_t nd = 3 * (size_t)w.dw * w.dh;
-    CBA_TRY(w.dense.alloc(nd));
-    CBA_HIP(hipMemcpyAsync(w.dense, dense, sizeof(double) * nd, hipMemcpyHostToDevice, s));
+    CBA_TRY(w.dense.alloc(3 * (size_t)w.dw * w.dh));
+    CBA_TRY(w.dense.upload_async(dense, w.dense.size(), s));
   } else {                                          // CreateObservationDirectionsImage, kept on the device
     w.dw = dense_model->cam.width; w.dh = dense_model->cam.height;
     CBA_TRY(w.dense.alloc(3 * (size_t)w.dw * w.dh)); CBA_TRY(w.rgb.alloc(3 * (size_t)w.dw * w.dh));
@@ -247,15 +240,10 @@ int cba_fit_parametric_to_dense_model(cba_parametric_camera* camera, const doubl
   }
   w.d_dense = w.dense;
   CBA_TRY(w.alloc_common());
-  auto read = [&](const double* dev, double* host, int k) -> int {
-    CBA_HIP(hipMemcpyAsync(host, dev, sizeof(double) * k, hipMemcpyDeviceToHost, s));
-    CBA_HIP(hipStreamSynchronize(s));
-    return CBA_OK;
-  };
   ParCam cam = to_parcam(*camera);
   double sums[240];
   CBA_TRY(launch_parametric_linear(w.d_dense, w.dw, w.dh, cam.width, cam.height, cam.equidistant, w.partials, w.sums, s));
-  CBA_TRY(read(w.sums, sums, 30));
+  CBA_TRY(w.sums.download_sync(sums, 30, s));
   CBA_TRY(linear_start_from_sums(sums, cam.p));
   const bool rot = o.allow_rotation != 0;
   const int dof = rot ? 15 : 12;
@@ -270,8 +258,8 @@ int cba_fit_parametric_to_dense_model(cba_parametric_camera* camera, const doubl
       CBA_TRY(launch_parametric_jacobian(w.args(cam, rot ? R : nullptr, rot, delta, w.cost_ref), w.partials, w.sums, s));
       CBA_TRY(launch_reduce_costs(w.cost_ref, nullptr, nullptr, 3 * w.n, w.red_partials, w.red8, s));
       double h8[8], H[225], b[15];
-      CBA_TRY(read(w.sums, sums, 240));
-      CBA_TRY(read(w.red8, h8, 8));
+      CBA_TRY(w.sums.download_sync(sums, 240, s));
+      CBA_TRY(w.red8.download_sync(h8, 8, s));
       rep.t_pass += now_s() - t0;
       unpack_system(sums, dof, H, b);
       last_cost = h8[0];
@@ -297,7 +285,7 @@ int cba_fit_parametric_to_dense_model(cba_parametric_camera* camera, const doubl
         state_minus(cam.p, R, x, rot, 1.0);
         CBA_TRY(launch_parametric_cost(w.args(cam, rot ? R : nullptr, rot, delta, w.cost_test), s));
         CBA_TRY(launch_reduce_costs(w.cost_ref, w.cost_test, nullptr, 3 * w.n, w.red_partials, w.red8, s));
-        CBA_TRY(read(w.red8, h8, 8));
+        CBA_TRY(w.red8.download_sync(h8, 8, s));
         rep.t_pass += now_s() - t0;
         if (h8[4] > 0 && h8[3] < h8[2]) {             // CostIsSmallerThan
           lambda = 0.5f * lambda;

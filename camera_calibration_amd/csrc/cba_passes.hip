@@ -62,12 +62,6 @@ static PassArgs pass_args(cba_problem* p, int which) {
   return a;
 }
 
-int read_scalars(cba_problem* p, const double* dev, double* host, int n) {
-  CBA_HIP(hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
-  CBA_HIP(hipStreamSynchronize(p->stream));
-  return CBA_OK;
-}
-
 int allreduce(cba_problem* p, double* dev, int64_t count) {
   if (!p->cfg.allreduce) return CBA_OK;
   CBA_HIP(hipStreamSynchronize(p->stream));
@@ -104,7 +98,7 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
     p->pf.mask_pending = false;
   }
   const size_t bs = L.block_size, nb = L.n_blocks;
-  CBA_HIP(hipMemsetAsync(p->fd_redo_count + 2, 0, sizeof(int), p->stream));      // tasks that found a follow-up list full, this pass
+  CBA_TRY(p->fd_redo_count.zero_async(1, p->stream, 2));      // tasks that found a follow-up list full, this pass
   CBA_TRY(launch_base_project(a, p->model_mask, p->cost_ref, p->pixels, p->flags, p->slow_list, p->slow_count, p->slow_cap, p->slow_skip, p->straggler_threshold, p->fd_slow, p->stream));
   // ... and the stragglers of the base projection (long projection chains, see k_base_project_slow) are finished there,
   // followed by their finite-difference tasks, underneath the main finite-difference launch
@@ -123,14 +117,14 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   // got a workgroup slot (profiles/r04_v2_step_timeline_cfg2.txt: base projection 0.25 ms after the tangents); queued behind the
   // VALU-bound FD kernel the fill's workgroups take slots as they come free.
   CBA_HIP(hipStreamWaitEvent(clr, p->ev_aux2, 0));            // behind the base projection of this pass
-  CBA_HIP(hipMemsetAsync(p->Dblk, 0, sizeof(double) * nb * bs * bs, clr));
-  CBA_HIP(hipMemsetAsync(p->bblk, 0, sizeof(double) * nb * bs, clr));
+  CBA_TRY(p->Dblk.zero_async(clr));
+  CBA_TRY(p->bblk.zero_async(clr));
   if (L.eliminate_points)
-    CBA_HIP(hipMemsetAsync(p->B, 0, sizeof(double) * (size_t)p->Kpad * p->n_pad, clr));
-  else if (p->Kpad > L.block_dof)     // padding rows of B (the strips below overwrite everything else, zeros included)
-    CBA_HIP(hipMemsetAsync(p->B + (size_t)L.block_dof * p->n_pad, 0, sizeof(double) * (size_t)(p->Kpad - L.block_dof) * p->n_pad, clr));
-  CBA_HIP(hipMemsetAsync(p->Hdd, 0, sizeof(double) * (size_t)p->n_pad * p->n_pad, clr));
-  CBA_HIP(hipMemsetAsync(p->bd, 0, sizeof(double) * (size_t)p->n_pad, clr));
+    CBA_TRY(p->B.zero_async(clr));
+  else                                // padding rows of B (the strips below overwrite everything else, zeros included)
+    CBA_TRY(p->B.zero_async((size_t)(p->Kpad - L.block_dof) * p->n_pad, clr, (size_t)L.block_dof * p->n_pad));
+  CBA_TRY(p->Hdd.zero_async(clr));
+  CBA_TRY(p->bd.zero_async(clr));
   CBA_HIP(hipEventRecord(p->ev_clear, clr));
   CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_aux1, 0));
   CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_clear, 0));

@@ -9,12 +9,9 @@ int alloc_posefirst_system(cba_problem* p) {
   const size_t bs = p->L.block_size, nb = p->L.n_blocks;
   CBA_TRY(p->pf.ev_mask.create(hipEventDisableTiming));
   CBA_TRY(p->pf.Dinv.alloc(nb * bs * bs));
-  CBA_TRY(p->pf.dinvb.alloc((size_t)p->Kpad));
-  CBA_HIP(hipMemset(p->pf.dinvb, 0, sizeof(double) * (size_t)p->Kpad));
-  CBA_TRY(p->pf.W.alloc((size_t)p->Kpad * p->n_pad));
-  CBA_TRY(p->pf.S.alloc((size_t)p->n_pad * p->n_pad));
-  CBA_HIP(hipMemset(p->pf.S, 0, sizeof(double) * (size_t)p->n_pad * p->n_pad));
-  CBA_HIP(hipMemset(p->pf.W, 0, sizeof(double) * (size_t)p->Kpad * p->n_pad));
+  CBA_TRY(p->pf.dinvb.alloc_zero((size_t)p->Kpad));
+  CBA_TRY(p->pf.W.alloc_zero((size_t)p->Kpad * p->n_pad));
+  CBA_TRY(p->pf.S.alloc_zero((size_t)p->n_pad * p->n_pad));
   CBA_TRY(p->pf.kmask_host.alloc((size_t)(p->n_pad / 128) * schur_mask_words(p->Kpad)));
   CBA_TRY(p->pf.kmask.alloc((size_t)(p->n_pad / 128) * schur_mask_words(p->Kpad)));
   if (schur_chunk_count(p->n_pad) > 0) {
@@ -47,7 +44,6 @@ int posefirst_enqueue(cba_problem* p, double lambda) {
   // Side stream, next to W = D^-1 B and the Schur product (MFMA-bound, bandwidth to spare): the partial sums of the right-hand
   // side B^T D^-1 b (one pass over B), the touch masks on their way to the host, and the control words of the factorisation's first
   // dataflow launch.  Round 3 had all three between the Schur product and the factorisation: 0.15 ms of small launches and gaps.
-  const int mask_tiles = p->n_pad / 128, mask_words = schur_mask_words(p->Kpad);
   {
     hipStream_t side = p->ldlt.far_stream;
     CBA_HIP(hipEventRecord(p->ev_aux0, p->stream));
@@ -56,7 +52,7 @@ int posefirst_enqueue(cba_problem* p, double lambda) {
     CBA_TRY(launch_gemv_t_partial(p->B, L.block_dof, dd, ld, p->pf.dinvb, p->pf.gemv_ws, side));
     CBA_TRY(launch_gemv_t_final(dd, p->bd, p->pf.S + (ld - 1), ld, p->pf.gemv_ws, p->n_pad, side));      // padding rows of the column: zero
     // (algorithmic flops of the Schur launch = K slabs actually multiplied: counted on the host after the solve)
-    CBA_HIP(hipMemcpyAsync(p->pf.kmask_host, p->pf.kmask, (size_t)mask_tiles * mask_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, side));
+    CBA_TRY(p->pf.kmask.download_async(p->pf.kmask_host, p->pf.kmask.size(), side));
     CBA_TRY(ldlt_clear_ctrl(p->ldlt, side));
     CBA_HIP(hipEventRecord(p->ev_aux1, side));
   }
@@ -69,7 +65,7 @@ int posefirst_enqueue(cba_problem* p, double lambda) {
   const bool dist = multi && p->cfg.distributed_solve && p->cfg.world_size >= 1;
   const int* chunk_order = nullptr;
   if (p->pf.chunk_order && p->pf.chunk_order_valid) {
-    CBA_HIP(hipMemcpyAsync(p->pf.chunk_order, p->pf.chunk_order_host, sizeof(int) * schur_chunk_count(p->n_pad), hipMemcpyHostToDevice, p->stream));
+    CBA_TRY(p->pf.chunk_order.upload_async(p->pf.chunk_order_host, p->pf.chunk_order.size(), p->stream));
     chunk_order = p->pf.chunk_order;
   }
   CBA_TRY(schur_gemm(p->B, p->pf.W, p->Kpad, ld, p->Hdd, p->pf.S, p->n_pad, ld, dd, (!multi || (dist && p->cfg.rank == 0)) ? 1 : 0, lambda, p->pf.kmask, p->stream, chunk_order, ld - 1));
@@ -88,7 +84,7 @@ int posefirst_enqueue(cba_problem* p, double lambda) {
     c.rank = p->cfg.rank; c.world = p->cfg.world_size;
     c.collective = p->cfg.collective; c.collective_user = p->cfg.collective_user;
     c.allreduce = p->cfg.allreduce; c.allreduce_user = p->cfg.allreduce_user;
-    c.send = p->P; c.recv = p->P2; c.buf_doubles = p->dist_buf_doubles;
+    c.send = p->P; c.recv = p->P2; c.buf_doubles = p->P2.size();
     int rc = ldlt_factor_distributed(p->pf.S, p->n_fact, ld, p->ldlt, p->stream, c, &gs);
     if (rc == CBA_ERR_STATE) set_error("distributed solve: a collective callback failed");
     CBA_TRY(rc);

@@ -64,7 +64,6 @@ struct GridFirstState {
   DevBuf<int> tile_list; PinnedBuf<int> tile_list_host; bool tile_list_valid = false; unsigned tile_list_age = 0;
   int tile_list_entries = 0;     // slots of the launch (eight interleaved per-XCD lists, padded)
   bool tile_list_dirty = false;  // the host copy was rebuilt since the last upload
-  size_t tile_list_capacity = 0; // ints
 };
 
 // image sharding with the grid-first order: per Gauss-Newton step the shared blocks of H_dd / b_d are
@@ -128,7 +127,7 @@ struct cba_problem {
   int n_pad = 0, n_fact = 0, Kpad = 0;
   DevBuf<double> Dblk, bblk, B, Hdd, bd;
   double* P = nullptr; DevBuf<double> P_own;   // reduce buffer of the multi-rank paths: the caller's cba_config.reduce_buffer, or P_own
-  DevBuf<double> P2; size_t dist_buf_doubles = 0;
+  DevBuf<double> P2;                           // receive buffer of the distributed solve
   int64_t P_cap = 0;                           // doubles of the reduce buffer P
   DevBuf<double> x, scal;
   DevBuf<int> status;
@@ -191,7 +190,6 @@ void order_imagesets(cba_problem* p, int64_t n, const float* xy, const int32_t* 
 int timer_begin(cba_problem* p, int which, hipStream_t s = nullptr);
 int timer_end(cba_problem* p, int which, double flops, double bytes, int launches, hipStream_t s = nullptr);
 int timers_collect(cba_problem* p);
-int read_scalars(cba_problem* p, const double* dev, double* host, int n);
 int allreduce(cba_problem* p, double* dev, int64_t count);
 int residual_pass(cba_problem* p, int which, double* cost_vec, const int* guard = nullptr);
 int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc);

@@ -89,10 +89,9 @@ int cba_model_direction_image(cba_model* m, uint8_t* rgb, double* directions, ui
   if (ok) CBA_TRY(d_ok.alloc(n));
   if (directions) CBA_TRY(d_dirs.alloc(3 * n));
   CBA_TRY(launch_direction_image(m->d_cam, m->cam.model_type, W, H, directions ? (double*)d_dirs : nullptr, ok ? (uint8_t*)d_ok : nullptr, d_rgb, nullptr));
-  CBA_HIP(hipMemcpy(rgb, d_rgb, 3 * n, hipMemcpyDeviceToHost));
-  if (ok) CBA_HIP(hipMemcpy(ok, d_ok, n, hipMemcpyDeviceToHost));
-  if (directions) CBA_HIP(hipMemcpy(directions, d_dirs, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
-  return CBA_OK;
+  if (ok) CBA_TRY(d_ok.download(ok, n));
+  if (directions) CBA_TRY(d_dirs.download(directions, 3 * n));
+  return d_rgb.download(rgb, 3 * n);
 }
 
 int cba_debug_time_direction_image(cba_model* m, int32_t use_stage, int32_t with_directions, int32_t launches, double* seconds) {
@@ -148,29 +147,24 @@ int cba_render_nearest_feature_image(int32_t width, int32_t height, int64_t n_si
     for (int64_t s = 0; s < n_sites; ++s) order[fill[bucket(s)]++] = (int)s;
   }
   DevBuf<int> d_start, d_order, d_xy, d_counts, d_overflow; DevBuf<float> d_col, d_accum; DevBuf<uint8_t> d_rgb; DevBuf<int2> d_list;
-  CBA_TRY(d_start.alloc(nb + 1)); CBA_TRY(d_order.alloc((size_t)n_sites)); CBA_TRY(d_xy.alloc(2 * (size_t)n_sites));
-  CBA_TRY(d_col.alloc(3 * (size_t)n_sites)); CBA_TRY(d_counts.alloc(2)); CBA_TRY(d_overflow.alloc(n_px)); CBA_TRY(d_list.alloc(n_px));
+  CBA_TRY(d_start.assign(start)); CBA_TRY(d_order.assign(order)); CBA_TRY(d_xy.assign(site_xy_quarter_px, 2 * (size_t)n_sites));
+  CBA_TRY(d_col.assign(site_rgb, 3 * (size_t)n_sites)); CBA_TRY(d_counts.alloc_zero(2)); CBA_TRY(d_overflow.alloc(n_px)); CBA_TRY(d_list.alloc(n_px));
   CBA_TRY(d_rgb.alloc(3 * n_px));
   if (accum) CBA_TRY(d_accum.alloc(3 * n_px));
-  CBA_HIP(hipMemcpy(d_start, start.data(), sizeof(int) * (nb + 1), hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(d_order, order.data(), sizeof(int) * (size_t)n_sites, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(d_xy, site_xy_quarter_px, sizeof(int) * 2 * (size_t)n_sites, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(d_col, site_rgb, sizeof(float) * 3 * (size_t)n_sites, hipMemcpyHostToDevice));
-  CBA_HIP(hipMemset(d_counts, 0, 2 * sizeof(int)));
   g.start = d_start; g.order = d_order; g.xy = d_xy; g.rgb = d_col;
   float* acc_dev = accum ? (float*)d_accum : nullptr;
   CBA_TRY(launch_nearest_site(g, W, H, d_rgb, acc_dev, d_list, d_counts, nullptr));
   int counts[2] = {0, 0};
-  CBA_HIP(hipMemcpy(counts, d_counts, sizeof(int), hipMemcpyDeviceToHost));
+  CBA_TRY(d_counts.download(counts, 1));
   if (counts[0] < 0 || (size_t)counts[0] > n_px) { set_error("cba_render_nearest_feature_image: pixel list corrupt"); return CBA_ERR_HIP; }
   CBA_TRY(launch_clip_cells(g, W, H, d_list, counts[0], d_rgb, acc_dev, d_overflow, (int*)d_counts + 1, nullptr));
-  CBA_HIP(hipMemcpy(counts, d_counts, 2 * sizeof(int), hipMemcpyDeviceToHost));
-  CBA_HIP(hipMemcpy(rgb, d_rgb, 3 * n_px, hipMemcpyDeviceToHost));
-  if (accum) CBA_HIP(hipMemcpy(accum, d_accum, sizeof(float) * 3 * n_px, hipMemcpyDeviceToHost));
+  CBA_TRY(d_counts.download(counts, 2));
+  CBA_TRY(d_rgb.download(rgb, 3 * n_px));
+  if (accum) CBA_TRY(d_accum.download(accum, 3 * n_px));
   if (counts[1] > 0) {           // pixels beyond the kernel's candidate capacity: rendered here
     if ((size_t)counts[1] > n_px) { set_error("cba_render_nearest_feature_image: overflow list corrupt"); return CBA_ERR_HIP; }
     std::vector<int> over((size_t)counts[1]);
-    CBA_HIP(hipMemcpy(over.data(), d_overflow, sizeof(int) * over.size(), hipMemcpyDeviceToHost));
+    CBA_TRY(d_overflow.download(over.data(), over.size()));
     for (int pixel : over) {
       float v[3];
       render_pixel_host(pixel % W, pixel / W, n_sites, site_xy_quarter_px, site_rgb, v);
@@ -191,7 +185,7 @@ int cba_model_center_point(cba_model* m, double center[3], int64_t* n_lines) {
   CBA_TRY(partials.alloc((size_t)center_point_partials_doubles())); CBA_TRY(sums.alloc(kCenterSums));
   CBA_TRY(launch_center_point_sums(m->d_cam, partials, sums, nullptr));
   double h[kCenterSums];
-  CBA_HIP(hipMemcpy(h, sums, sizeof(h), hipMemcpyDeviceToHost));
+  CBA_TRY(sums.download(h, kCenterSums));
   if (n_lines) *n_lines = (int64_t)h[10];
   if (!solve_spd3(h, h + 6, center)) { set_error("cba_model_center_point: the lines do not determine a point"); return CBA_ERR_NUMERIC; }
   return CBA_OK;
@@ -209,15 +203,15 @@ int cba_model_line_offsets(cba_model* m, const double center[3], double* offsets
   CBA_TRY(d_off.alloc(3 * n)); CBA_TRY(d_max.alloc((size_t)blocks));
   CBA_TRY(launch_line_offsets(m->d_cam, W, H, center, d_off, d_max, nullptr));
   std::vector<double> bm((size_t)blocks);
-  CBA_HIP(hipMemcpy(bm.data(), d_max, sizeof(double) * bm.size(), hipMemcpyDeviceToHost));
+  CBA_TRY(d_max.download(bm.data(), bm.size()));
   double ext = 0;
   for (double v : bm) ext = std::max(ext, v);
   if (max_extent) *max_extent = ext;
-  if (offsets) CBA_HIP(hipMemcpy(offsets, d_off, sizeof(double) * 3 * n, hipMemcpyDeviceToHost));
+  if (offsets) CBA_TRY(d_off.download(offsets, 3 * n));
   if (rgb) {
     CBA_TRY(d_rgb.alloc(3 * n));
     CBA_TRY(launch_line_offset_colors(d_off, W, H, ext, d_rgb, nullptr));
-    CBA_HIP(hipMemcpy(rgb, d_rgb, 3 * n, hipMemcpyDeviceToHost));
+    CBA_TRY(d_rgb.download(rgb, 3 * n));
   }
   return CBA_OK;
 }

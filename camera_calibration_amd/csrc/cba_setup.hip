@@ -148,8 +148,7 @@ static int build_grid_order(cba_problem* p) {
       for (int tx = 0; tx < gw; tx += tile)
         for (int y = ty; y < std::min(gh, ty + tile); ++y)
           for (int x = tx; x < std::min(gw, tx + tile); ++x) perm[x + (size_t)y * gw] = rank++;
-    CBA_TRY(p->gperm[c].alloc(perm.size()));
-    CBA_HIP(hipMemcpy(p->gperm[c], perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice));
+    CBA_TRY(p->gperm[c].assign(perm));
     for (size_t g = 0; g < perm.size(); ++g)
       for (int d = 0; d < per; ++d)
         p->dense_perm_host[L.intr_offset[c] + per * g + d] = L.intr_offset[c] + per * perm[g] + d;
@@ -161,7 +160,7 @@ static int upload_camdevs(cba_problem* p, int which) {
   std::vector<CamDev> h(p->L.n_cameras);
   for (int c = 0; c < p->L.n_cameras; ++c)
     h[c] = make_camdev(p->cams[c], p->st[which].grids[c], p->tangents[c], p->L.intr_offset[c], p->gperm[c]);
-  CBA_HIP(hipMemcpyAsync(p->cams_dev[which], h.data(), sizeof(CamDev) * h.size(), hipMemcpyHostToDevice, p->stream));
+  CBA_TRY(p->cams_dev[which].upload_async(h.data(), h.size(), p->stream));
   CBA_HIP(hipStreamSynchronize(p->stream));
   return CBA_OK;
 }
@@ -255,19 +254,15 @@ static int upload_pair_tables(cba_problem* p) {
       }
     counts[slot] = e;
   }
-  CBA_TRY(p->pair_tables.alloc(tab.size()));
-  CBA_TRY(p->pair_counts.alloc(2));
-  CBA_HIP(hipMemcpy(p->pair_tables, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  CBA_HIP(hipMemcpy(p->pair_counts, counts, sizeof(counts), hipMemcpyHostToDevice));
-  return CBA_OK;
+  CBA_TRY(p->pair_tables.assign(tab));
+  return p->pair_counts.assign(counts, 2);
 }
 
 // what the passes over the observations need besides the observations: events, state, per-camera arrays, pair tables, cells
 int alloc_pass_buffers(cba_problem* p) {
   const Layout& L = p->L;
   for (Event* e : {&p->ev_aux0, &p->ev_aux1, &p->ev_aux2, &p->ev_clear}) CBA_TRY(e->create(hipEventDisableTiming));
-  CBA_TRY(p->slow_count.alloc(1));
-  CBA_HIP(hipMemset(p->slow_count, 0, sizeof(int)));
+  CBA_TRY(p->slow_count.alloc_zero(1));
   for (int c = 0; c < L.n_cameras; ++c) p->model_mask |= (p->cams[c].model_type == CBA_CENTRAL_GENERIC) ? 1 : 2;
   const int maxKg = L.localize_only ? 0 : ((p->model_mask & 2) ? 80 : 32);
   p->tasks_per_obs = 3 + maxKg;
@@ -285,12 +280,10 @@ int alloc_pass_buffers(cba_problem* p) {
   p->cell_base_host.assign(L.n_cameras + 1, 0);
   for (int c = 0; c < L.n_cameras; ++c) p->cell_base_host[c + 1] = p->cell_base_host[c] + p->cams[c].grid_w * p->cams[c].grid_h;
   const size_t nk = (size_t)p->cell_base_host.back();
-  CBA_TRY(p->cell_base.alloc(p->cell_base_host.size()));
-  CBA_HIP(hipMemcpy(p->cell_base, p->cell_base_host.data(), sizeof(int) * p->cell_base_host.size(), hipMemcpyHostToDevice));
+  CBA_TRY(p->cell_base.assign(p->cell_base_host));
   CBA_TRY(p->cell_count.alloc(nk + 1)); CBA_TRY(p->cell_start.alloc(nk + 1)); CBA_TRY(p->cell_fill.alloc(nk + 1));
   CBA_TRY(p->det_bits.alloc(2)); CBA_TRY(p->det_scale.alloc(2));
-  CBA_TRY(p->fd_redo_count.alloc(4));
-  CBA_HIP(hipMemset(p->fd_redo_count, 0, sizeof(int) * 4));
+  CBA_TRY(p->fd_redo_count.alloc_zero(4));
   CBA_TRY(p->red_partials.alloc(256 * 8));
   CBA_TRY(p->red8.alloc(16));
   return CBA_OK;
@@ -308,8 +301,7 @@ int alloc_system(cba_problem* p) {
   CBA_TRY(p->Hdd.alloc((size_t)p->n_pad * p->n_pad));
   CBA_TRY(p->bd.alloc((size_t)p->n_pad));
   CBA_TRY(p->gridfirst ? alloc_gridfirst_system(p) : alloc_posefirst_system(p));
-  CBA_TRY(p->x.alloc((size_t)L.block_dof + p->n_pad));
-  CBA_HIP(hipMemset(p->x, 0, sizeof(double) * ((size_t)L.block_dof + p->n_pad)));
+  CBA_TRY(p->x.alloc_zero((size_t)L.block_dof + p->n_pad));
   CBA_TRY(p->scal.alloc(16));
   CBA_TRY(p->status.alloc(2));      // [0] block-inverse status, [1] guard word of the solve (k_solve_status)
   CBA_TRY(p->pin_status.alloc(4));
@@ -325,7 +317,6 @@ int alloc_reduce_buffer(cba_problem* p, const cba_config* config) {
   int64_t need = p->gf_sharded ? p->sh.shared.doubles : packed_upper_doubles(p->n_pad);
   if (config->distributed_solve) {       // staging of the reduce-scatter / all-gathers (send: P, receive: P2)
     need = (int64_t)ldlt_dist_buffer_doubles(p->n_pad, config->world_size);
-    p->dist_buf_doubles = (size_t)need;
     CBA_TRY(p->P2.alloc((size_t)need));
   }
   if (config->reduce_buffer) {

@@ -21,8 +21,8 @@ __global__ void k_solve_status(const int* __restrict__ s0, const int* __restrict
 // pass BETWEEN the two on one GPU (PassArgs::guard keeps that pass from running behind a broken solve).
 int solve_enqueue(cba_problem* p, double lambda) {
   CBA_TRY(timer_begin(p, kTimerSolve));
-  CBA_HIP(hipMemsetAsync(p->status, 0, sizeof(int), p->stream));
-  CBA_HIP(hipMemsetAsync(p->ldlt.status, 0, sizeof(int), p->stream));
+  CBA_TRY(p->status.zero_async(1, p->stream));
+  CBA_TRY(p->ldlt.status.zero_async(p->stream));
   CBA_TRY(p->gridfirst ? gridfirst_enqueue(p, lambda) : posefirst_enqueue(p, lambda));
   // the two status words and x[0] reach the host through ONE launch that writes pinned host memory (three device-to-host copies in
   // a row cost 20 us each in front of the host's decision)

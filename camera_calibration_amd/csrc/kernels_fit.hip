@@ -151,11 +151,11 @@ int launch_fit_pass(bool jac, int gw, int gh, const double* grid, const double* 
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
-int launch_fit_accumulate(int gw, int gh, int64_t n, const double* rec, const int* keys, int* count, int* start, int* fill,
+int launch_fit_accumulate(int gw, int gh, int64_t n, const double* rec, const int* keys, DevBuf<int>& count, int* start, DevBuf<int>& fill,
                           int* order, double* H, int ld, double* b, hipStream_t s) {
   const int n_keys = gw * gh;
-  CBA_HIP(hipMemsetAsync(count, 0, sizeof(int) * (size_t)n_keys, s));
-  CBA_HIP(hipMemsetAsync(fill, 0, sizeof(int) * (size_t)n_keys, s));
+  CBA_TRY(count.zero_async((size_t)n_keys, s));
+  CBA_TRY(fill.zero_async((size_t)n_keys, s));
   if (n == 0) return CBA_OK;
   dim3 g((unsigned)((n + 255) / 256)), block(256);
   hipLaunchKernelGGL(k_fit_key_count, g, block, 0, s, keys, n, count);

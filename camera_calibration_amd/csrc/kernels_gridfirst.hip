@@ -224,9 +224,9 @@ __global__ void k_gf_masks(const unsigned long long* __restrict__ act, int n_til
 // the two halves of launch_gf_activity: the touched rows of this process's observations (image sharding: OR-ed over the ranks in
 // between, cba_gridfirst.hip gf_exchange), then their closure and the masks derived from it
 int launch_gf_touch(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
-                    int n_rp, int rig_dof, int n_tiles, int words, int slot0, unsigned long long* act, hipStream_t s) {
+                    int n_rp, int rig_dof, int n_tiles, int words, int slot0, DevBuf<unsigned long long>& act, hipStream_t s) {
   if (words > 16) { set_error("grid-first: more than 1024 grid block rows"); return CBA_ERR_UNSUPPORTED; }
-  CBA_HIP(hipMemsetAsync(act, 0, sizeof(unsigned long long) * (size_t)n_tiles * words, s));
+  CBA_TRY(act.zero_async((size_t)n_tiles * words, s));
   if (pa.n_obs > 0 && n_images > 0) {
     GfTouchArgs a{};
     a.obs_point = pa.obs_point; a.obs_image = pa.obs_image; a.obs_camera = pa.obs_camera; a.flags = flags; a.cells = cells; a.img_start = img_start;
@@ -247,7 +247,7 @@ int launch_gf_close_masks(int n_tiles, int words, int nbg, int nbf, const unsign
   return CBA_OK;
 }
 int launch_gf_activity(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
-                       int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
+                       int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, DevBuf<unsigned long long>& act,
                        unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
                        int mask_words, hipStream_t s) {
   int rc = launch_gf_touch(pa, flags, cells, img_start, n_images, f_of_grid, n_rp, rig_dof, n_tiles, words, 0, act, s);

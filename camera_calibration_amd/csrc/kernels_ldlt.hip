@@ -74,19 +74,15 @@ int ldlt_workspace_alloc(LdltWorkspace& w, int n_pad, int flag_rows_blocks) {
     int rows = ntc < kTailMaxBlockRows ? ntc : kTailMaxBlockRows;
     if (flag_rows_blocks > rows) rows = flag_rows_blocks < ntc ? flag_rows_blocks : ntc;      // block-sparse launch: every grid block row has its flags
     const size_t words = (size_t)rows * ntc + 3 * (size_t)ntc;
-    CBA_TRY(w.tail_flags.alloc(words));
-    CBA_HIP(hipMemset(w.tail_flags, 0, sizeof(unsigned) * words));
-    CBA_TRY(w.tail_ctrl.alloc(kCtrlWords));
-    CBA_HIP(hipMemset(w.tail_ctrl, 0, sizeof(unsigned) * kCtrlWords));
+    CBA_TRY(w.tail_flags.alloc_zero(words));
+    CBA_TRY(w.tail_ctrl.alloc_zero(kCtrlWords));
     w.tail_rows_cap = rows * kInner;
     w.tail_epoch = 0;
     CBA_TRY(w.tail_e0.create());
     CBA_TRY(w.tail_e1.create());
-    CBA_TRY(w.back_xe.alloc(2 * (size_t)n_pad));
-    CBA_HIP(hipMemset(w.back_xe, 0, sizeof(double) * 2 * (size_t)n_pad));
+    CBA_TRY(w.back_xe.alloc_zero(2 * (size_t)n_pad));
     w.back_epoch = 0;
   }
-  w.n_alloc = n_pad;
   return CBA_OK;
 }
 
@@ -175,7 +171,7 @@ int ldlt_tail_rows(const LdltWorkspace& w, int world) {
 // Clears the control words of the NEXT dataflow launch now (on stream s, which must be ordered in front of that launch): the
 // first launch of a factorisation then starts without a memset between it and the Schur product.
 int ldlt_clear_ctrl(LdltWorkspace& w, hipStream_t s) {
-  CBA_HIP(hipMemsetAsync(w.tail_ctrl, 0, sizeof(unsigned) * kCtrlWords, s));
+  CBA_TRY(w.tail_ctrl.zero_async(s));
   w.tail_ctrl_clean = true;
   return CBA_OK;
 }
@@ -197,7 +193,7 @@ static int tail_args_init(TailArgs& t, double* S, int ld, LdltWorkspace& w, hipS
   t.ctrl = w.tail_ctrl;
   t.epoch = ++w.tail_epoch;
   if (w.tail_ctrl_clean) w.tail_ctrl_clean = false;
-  else CBA_HIP(hipMemsetAsync(w.tail_ctrl, 0, sizeof(unsigned) * kCtrlWords, s));
+  else CBA_TRY(w.tail_ctrl.zero_async(s));
   return CBA_OK;
 }
 // The launch.  Its own span (ldlt_tail_last_ms) is a harness statistic: two event records per launch are two bubbles on the

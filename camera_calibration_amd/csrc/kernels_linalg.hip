@@ -614,9 +614,9 @@ void schur_chunk_order(const unsigned long long* mask_host, int n_pad, int Kpad,
   // heavy chunk (~ 18 % of an XCD's share at cfg 2).  Every other octet is dealt in reverse (boustrophedon): the totals even out.
   for (int r = 1; 8 * r + 8 <= nc; r += 2) std::reverse(order + 8 * r, order + 8 * r + 8);
 }
-int launch_touch_mask(const double* B, int Kpad, int n_pad, int ld, unsigned long long* mask, hipStream_t s) {
+int launch_touch_mask(const double* B, int Kpad, int n_pad, int ld, DevBuf<unsigned long long>& mask, hipStream_t s) {
   const int words = schur_mask_words(Kpad);
-  CBA_HIP(hipMemsetAsync(mask, 0, sizeof(unsigned long long) * (size_t)(n_pad / 128) * words, s));
+  CBA_TRY(mask.zero_async((size_t)(n_pad / 128) * words, s));
   hipLaunchKernelGGL(k_touch_mask, dim3(Kpad / kSchurSlab, n_pad / 128), dim3(256), 0, s, B, ld, mask, words);
   CBA_HIP(hipGetLastError());
   return CBA_OK;

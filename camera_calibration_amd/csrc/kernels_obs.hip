@@ -824,13 +824,13 @@ __global__ void __launch_bounds__(256) k_accumulate_cells(PassArgs a, int cam, i
   }
 }
 int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const std::vector<int>& cell_base_host, int ld,
-                            const uint8_t* flags, const int* cells, const int* cell_base, int* count, int* start, int* fill, int* order,
+                            const uint8_t* flags, const int* cells, const int* cell_base, DevBuf<int>& count, int* start, DevBuf<int>& fill, int* order,
                             double* Hdd, int rig_row_first /* dense row of camera 0's rig block, or -1 */, const double* det_scale, double* bd,
                             hipStream_t s) {
   if (a.n_obs == 0) return CBA_OK;
   const int n_keys = cell_base_host.back();
-  CBA_HIP(hipMemsetAsync(count, 0, sizeof(int) * (size_t)n_keys, s));
-  CBA_HIP(hipMemsetAsync(fill, 0, sizeof(int) * (size_t)n_keys, s));
+  CBA_TRY(count.zero_async((size_t)n_keys, s));
+  CBA_TRY(fill.zero_async((size_t)n_keys, s));
   dim3 grid((unsigned)((a.n_obs + 255) / 256)), block(256);
   hipLaunchKernelGGL(k_cell_count, grid, block, 0, s, a, flags, cells, cell_base, count);
   CBA_TRY(launch_exclusive_scan(count, n_keys, start, s));
@@ -1111,8 +1111,8 @@ __global__ void k_det_scale(const unsigned long long* __restrict__ bits, int64_t
     scale[i] = ldexp(1.0, 62 - e);                              // bound * scale < 2^62
   }
 }
-int launch_det_scale(const PassArgs& a, const uint8_t* flags, unsigned long long* bits, double* scale, hipStream_t s) {
-  CBA_HIP(hipMemsetAsync(bits, 0, 2 * sizeof(unsigned long long), s));
+int launch_det_scale(const PassArgs& a, const uint8_t* flags, DevBuf<unsigned long long>& bits, double* scale, hipStream_t s) {
+  CBA_TRY(bits.zero_async(2, s));
   if (a.n_obs > 0)      // (every double of a record counts: the unused tails of mixed-model problems are zero)
     hipLaunchKernelGGL(k_det_bound, dim3(1024), dim3(256), 0, s, a.n_obs, a.rec_doubles, a.rec_doubles, flags, a.jrec, bits);
   hipLaunchKernelGGL(k_det_scale, dim3(1), dim3(1), 0, s, bits, a.n_obs, scale);

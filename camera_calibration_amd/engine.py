@@ -164,22 +164,66 @@ class CbaReport(C.Structure):
                 ("t_accumulate", C.c_double), ("t_gemm", C.c_double), ("t_factor", C.c_double)]
 
 
-# every symbol include/cba.h declares (tests check that the library exports all of them)
-EXPORTED_SYMBOLS = [
-    "cba_last_error", "cba_version", "cba_create", "cba_destroy", "cba_set_observations", "cba_set_state",
-    "cba_get_state", "cba_get_last_projection", "cba_step", "cba_cost", "cba_project", "cba_unproject",
-    "cba_schur_solve", "cba_debug_dump", "cba_debug_accumulate", "cba_set_straggler_threshold", "cba_debug_solve", "cba_debug_apply_update",
-    "cba_total_dof", "cba_dense_dof", "cba_jacobian_record_doubles", "cba_reduce_buffer_doubles",
-    "cba_kernel_stats", "cba_fit_grid_to_directions", "cba_prepare_device",
-    "cba_model_create", "cba_model_destroy", "cba_model_set_grid", "cba_model_project", "cba_model_unproject",
-    "cba_fd_redo_overflow", "cba_debug_fd_redo_counts", "cba_schur_solve_opt", "cba_debug_reduced_system", "cba_set_fd_schedule",
-    "cba_gridfirst_plan_query", "cba_elimination_order",
-    "cba_model_direction_image", "cba_render_nearest_feature_image", "cba_model_center_point", "cba_model_line_offsets",
-    "cba_debug_time_direction_image",
-    "cba_model_compare", "cba_model_direction_moments", "cba_model_localization_accuracy", "cba_model_localize_images",
-    "cba_parametric_project", "cba_parametric_unproject", "cba_parametric_fit_pass", "cba_fit_parametric_to_dense_model",
-    "cba_model_compare_parametric",
-]
+# Prototype of every function include/cba.h declares: name -> (restype, argtypes).  load() applies the table once; the tests check
+# it against the header and that the library exports every name.
+_I, _I32, _I64, _F64, _VP = C.c_int, C.c_int32, C.c_int64, C.c_double, C.c_void_p
+_D, _U8, _I32P, _I64P, _F32P = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)
+_CAM, _PCAM, _CFG = C.POINTER(CbaCamera), C.POINTER(CbaParametricCamera), C.POINTER(CbaConfig)
+PROTOTYPES = {
+    "cba_prepare_device": (_I, [_I32]),
+    "cba_last_error": (C.c_char_p, []),
+    "cba_version": (C.c_char_p, []),
+    "cba_create": (_I, [_CFG, C.POINTER(_VP)]),
+    "cba_destroy": (None, [_VP]),
+    "cba_set_observations": (_I, [_VP, _I64, _F32P, _I32P, _I32P, _I32P, _D]),
+    "cba_set_state": (_I, [_VP, _D, _D, _D, C.POINTER(_D)]),
+    "cba_get_state": (_I, [_VP, _D, _D, _D, C.POINTER(_D)]),
+    "cba_get_last_projection": (_I, [_VP, _D]),
+    "cba_step": (_I, [_VP, _F64, _I32, _F64, C.POINTER(CbaReport)]),
+    "cba_cost": (_I, [_VP, _D, _I64P, _D]),
+    "cba_fd_redo_overflow": (_I64, [_VP]),
+    "cba_debug_fd_redo_counts": (_I, [_VP, _I64P]),
+    "cba_project": (_I, [_CAM, _D, _I64, _D, _D, _D, _U8, _I32]),
+    "cba_unproject": (_I, [_CAM, _D, _I64, _D, _D, _D, _U8, _I32]),
+    "cba_model_create": (_I, [_CAM, _D, _I32, C.POINTER(_VP)]),
+    "cba_model_destroy": (None, [_VP]),
+    "cba_model_set_grid": (_I, [_VP, _D]),
+    "cba_model_project": (_I, [_VP, _I64, _D, _D, _D, _U8]),
+    "cba_model_unproject": (_I, [_VP, _I64, _D, _D, _D, _U8]),
+    "cba_model_direction_image": (_I, [_VP, _U8, _D, _U8]),
+    "cba_render_nearest_feature_image": (_I, [_I32, _I32, _I64, _I32P, _F32P, _I32, _U8, _F32P]),
+    "cba_model_center_point": (_I, [_VP, _D, _I64P]),
+    "cba_model_line_offsets": (_I, [_VP, _D, _D, _U8, _D]),
+    "cba_model_compare": (_I, [_VP, _VP, C.POINTER(CbaCompareOptions), C.POINTER(CbaCompareOutputs), C.POINTER(CbaCompareStats)]),
+    "cba_model_direction_moments": (_I, [_VP, _VP, _I32, _I32, _D, _I64P]),
+    "cba_model_localization_accuracy": (_I, [_VP, _VP, C.POINTER(CbaLocalizationOptions), C.POINTER(CbaLocalizationOutputs),
+                                             C.POINTER(CbaLocalizationStats)]),
+    "cba_model_localize_images": (_I, [C.POINTER(CbaLocalizeImagesInput), C.POINTER(CbaLocalizeImagesOptions), C.POINTER(CbaLocalizeImagesOutputs)]),
+    "cba_schur_solve": (_I, [_I32, _I32, _I32, _D, _D, _D, _D, _D, _D, _I32]),
+    "cba_schur_solve_opt": (_I, [_I32, _I32, _I32, _D, _D, _D, _D, _D, _D, C.POINTER(CbaSolverOptions), _I32]),
+    "cba_debug_reduced_system": (_I, [_I32, _I32, _I32, _D, _D, _D, _D, _D, _F64, _I32, _D, C.POINTER(C.c_uint64), _I32P, _I32]),
+    "cba_fit_grid_to_directions": (_I, [_CAM, _D, _I64, _D, _D, _I32, C.POINTER(CbaFitReport), _I32]),
+    "cba_parametric_project": (_I, [_PCAM, _I64, _D, _D, _U8, _I32]),
+    "cba_parametric_unproject": (_I, [_PCAM, _I64, _D, _D, _U8, _I32]),
+    "cba_parametric_fit_pass": (_I, [_PCAM, _D, _D, _I32, _I32, _I32, _F64, _I32, _D, _U8, _D, _D, _D, _D, _I32]),
+    "cba_fit_parametric_to_dense_model": (_I, [_PCAM, _D, _I32, _I32, _VP, C.POINTER(CbaParametricFitOptions), _D, C.POINTER(CbaFitReport), _I32]),
+    "cba_model_compare_parametric": (_I, [_VP, _PCAM, C.POINTER(CbaCompareOptions), C.POINTER(CbaCompareOutputs), C.POINTER(CbaCompareStats)]),
+    "cba_debug_dump": (_I, [_VP, _I32, _VP, C.c_size_t]),
+    "cba_set_straggler_threshold": (_I, [_VP, _I32]),
+    "cba_set_fd_schedule": (_I, [_VP, _I32]),
+    "cba_debug_accumulate": (_I, [_VP, _D]),
+    "cba_debug_solve": (_I, [_VP, _F64]),
+    "cba_debug_apply_update": (_I, [_VP, _D]),
+    "cba_gridfirst_plan_query": (_I64, [_CAM, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I64]),
+    "cba_debug_time_direction_image": (_I, [_VP, _I32, _I32, _I32, _D]),
+    "cba_elimination_order": (_I32, [_VP, _I32P]),
+    "cba_total_dof": (_I32, [_VP]),
+    "cba_dense_dof": (_I32, [_VP]),
+    "cba_jacobian_record_doubles": (_I32, [_VP]),
+    "cba_reduce_buffer_doubles": (_I64, [_CFG]),
+    "cba_kernel_stats": (_I, [_VP, _I32, _D, _D, _D, _I32P]),
+}
+EXPORTED_SYMBOLS = list(PROTOTYPES)
 
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
 DUMP_BLOCK_DIAG_H, DUMP_BLOCK_DIAG_B, DUMP_OFF_DIAG_H, DUMP_DENSE_H, DUMP_DENSE_B, DUMP_X = 5, 6, 7, 8, 9, 10
@@ -207,58 +251,9 @@ def load() -> C.CDLL:
         raise EngineError(f"{LIB_PATH} is missing -- run `python -c 'import __graft_entry__ as g; g.build()'`; "
                           "the engine has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    dp = C.POINTER(C.c_double)
-    vp = C.c_void_p
-    L.cba_last_error.restype = C.c_char_p
-    L.cba_version.restype = C.c_char_p
-    L.cba_create.argtypes = [C.POINTER(CbaConfig), C.POINTER(vp)]
-    L.cba_destroy.argtypes = [vp]
-    L.cba_destroy.restype = None
-    L.cba_set_observations.argtypes = [vp, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_int32),
-                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp]
-    L.cba_set_state.argtypes = [vp, dp, dp, dp, C.POINTER(dp)]
-    L.cba_get_state.argtypes = [vp, dp, dp, dp, C.POINTER(dp)]
-    L.cba_get_last_projection.argtypes = [vp, dp]
-    L.cba_step.argtypes = [vp, C.c_double, C.c_int32, C.c_double, C.POINTER(CbaReport)]
-    L.cba_cost.argtypes = [vp, dp, C.POINTER(C.c_int64), dp]
-    L.cba_project.argtypes = [C.POINTER(CbaCamera), dp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8), C.c_int32]
-    L.cba_unproject.argtypes = [C.POINTER(CbaCamera), dp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8), C.c_int32]
-    L.cba_schur_solve.argtypes = [C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_int32]
-    L.cba_fit_grid_to_directions.argtypes = [C.POINTER(CbaCamera), dp, C.c_int64, dp, dp, C.c_int32, C.POINTER(CbaFitReport), C.c_int32]
-    L.cba_debug_dump.argtypes = [vp, C.c_int32, vp, C.c_size_t]
-    L.cba_debug_accumulate.argtypes = [vp, dp]
-    L.cba_set_straggler_threshold.argtypes = [vp, C.c_int32]
-    L.cba_set_fd_schedule.argtypes = [vp, C.c_int32]
-    L.cba_debug_solve.argtypes = [vp, C.c_double]
-    L.cba_debug_apply_update.argtypes = [vp, dp]
-    L.cba_total_dof.argtypes = [vp]
-    L.cba_dense_dof.argtypes = [vp]
-    L.cba_jacobian_record_doubles.argtypes = [vp]
-    L.cba_reduce_buffer_doubles.argtypes = [C.POINTER(CbaConfig)]
-    L.cba_reduce_buffer_doubles.restype = C.c_int64
-    L.cba_kernel_stats.argtypes = [vp, C.c_int32, dp, dp, dp, C.POINTER(C.c_int32)]
-    L.cba_prepare_device.argtypes = [C.c_int32]
-    L.cba_model_create.argtypes = [C.POINTER(CbaCamera), dp, C.c_int32, C.POINTER(vp)]
-    L.cba_model_destroy.argtypes = [vp]
-    L.cba_model_destroy.restype = None
-    L.cba_model_set_grid.argtypes = [vp, dp]
-    L.cba_model_project.argtypes = [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8)]
-    L.cba_model_unproject.argtypes = [vp, C.c_int64, dp, dp, dp, C.POINTER(C.c_uint8)]
-    L.cba_gridfirst_plan_query.argtypes = [C.POINTER(CbaCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64]
-    L.cba_gridfirst_plan_query.restype = C.c_int64
-    u8p = C.POINTER(C.c_uint8)
-    L.cba_model_direction_image.argtypes = [vp, u8p, dp, u8p]
-    L.cba_render_nearest_feature_image.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32,
-                                                   u8p, C.POINTER(C.c_float)]
-    L.cba_model_center_point.argtypes = [vp, dp, C.POINTER(C.c_int64)]
-    L.cba_model_line_offsets.argtypes = [vp, dp, dp, u8p, dp]
-    L.cba_debug_time_direction_image.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp]
-    pc = C.POINTER(CbaParametricCamera)
-    L.cba_parametric_project.argtypes = [pc, C.c_int64, dp, dp, u8p, C.c_int32]
-    L.cba_parametric_unproject.argtypes = [pc, C.c_int64, dp, dp, u8p, C.c_int32]
-    L.cba_parametric_fit_pass.argtypes = [pc, dp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, dp, u8p, dp, dp, dp, dp, C.c_int32]
-    L.cba_fit_parametric_to_dense_model.argtypes = [pc, dp, C.c_int32, C.c_int32, vp, C.POINTER(CbaParametricFitOptions), dp,
-                                                    C.POINTER(CbaFitReport), C.c_int32]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -458,8 +453,6 @@ class Engine:
     def elimination_order(self) -> dict:
         """cba_elimination_order: which order this problem uses (cba_solver_options.elimination resolved) and its sizes."""
         out = (C.c_int32 * 4)()
-        self.L.cba_elimination_order.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-        self.L.cba_elimination_order.restype = C.c_int32
         order = int(self.L.cba_elimination_order(self._h, out))
         return dict(order={1: "pose-first", 2: "grid-first"}.get(order, "?"), strips=int(out[0]), dense_rows=int(out[1]), grid_rows=int(out[2]), chains=int(out[3]))
 
@@ -474,14 +467,11 @@ class Engine:
 
     def fd_redo_overflow(self) -> int:
         """cba_fd_redo_overflow: finite-difference tasks of the last Jacobian pass that found the follow-up list full (expected 0)."""
-        self.L.cba_fd_redo_overflow.restype = C.c_int64
-        self.L.cba_fd_redo_overflow.argtypes = [C.c_void_p]
         return int(self.L.cba_fd_redo_overflow(self._h))
 
     def fd_redo_counts(self):
         """cba_debug_fd_redo_counts: (main list, side-stream list, overflow) of the last Jacobian pass."""
         out = (C.c_int64 * 3)()
-        self.L.cba_debug_fd_redo_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         _check(self.L.cba_debug_fd_redo_counts(self._h, out), "cba_debug_fd_redo_counts")
         return int(out[0]), int(out[1]), int(out[2])
 
@@ -613,8 +603,6 @@ class DeviceModel:
         """cba_model_compare_parametric with this model as the base and a ``parametric.ThinPrismFisheye`` as the fitted model: the
         dict of ``compare`` (n_second_launch is 0: the fitted model projects in closed form)."""
         cs = fitted.struct()
-        self.L.cba_model_compare_parametric.argtypes = [C.c_void_p, C.POINTER(CbaParametricCamera), C.POINTER(CbaCompareOptions),
-                                                        C.POINTER(CbaCompareOutputs), C.POINTER(CbaCompareStats)]
         return self._compare(int(fitted.width), int(fitted.height), rotation, border, max_visualization_extent, max_visualization_extent_pixels,
                              INITIAL_ESTIMATE_CENTER, 0, want_arrays, want_images,
                              lambda o, out, st: _check(self.L.cba_model_compare_parametric(self._h, C.byref(cs), o, out, st),
@@ -637,8 +625,6 @@ class DeviceModel:
                 res[name] = np.zeros((H, W, k) if k else (H, W), dtype=np.uint8)
                 setattr(out, name, res[name].ctypes.data)
         st = CbaCompareStats()
-        self.L.cba_model_compare.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CbaCompareOptions), C.POINTER(CbaCompareOutputs),
-                                             C.POINTER(CbaCompareStats)]
         call(C.byref(o), C.byref(out), C.byref(st))
         for name, _ in CbaCompareStats._fields_:
             res[name] = getattr(st, name)
@@ -650,7 +636,6 @@ class DeviceModel:
         """cba_model_direction_moments with this model as the base: (M (3, 3) = sum f a^T, number of pixels summed)."""
         M = np.zeros((3, 3))
         n = C.c_int64(0)
-        self.L.cba_model_direction_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         _check(self.L.cba_model_direction_moments(self._h, fitted._h, int(border[0]), int(border[1]), _dp(M), C.byref(n)),
                "cba_model_direction_moments")
         return M, int(n.value)
@@ -675,8 +660,6 @@ class DeviceModel:
                     res[name] = np.zeros((T,) + tuple(P if d == "P" else d for d in tail), dtype=dt)
                     setattr(out, name, res[name].ctypes.data)
         st = CbaLocalizationStats()
-        self.L.cba_model_localization_accuracy.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CbaLocalizationOptions),
-                                                           C.POINTER(CbaLocalizationOutputs), C.POINTER(CbaLocalizationStats)]
         _check(self.L.cba_model_localization_accuracy(self._h, compared._h, C.byref(o), C.byref(out), C.byref(st)),
                "cba_model_localization_accuracy")
         for name, _ in CbaLocalizationStats._fields_:
@@ -724,8 +707,6 @@ class DeviceModel:
                 if want_debug or name not in LOCALIZE_IMAGES_DEBUG:
                     res[name] = np.zeros((S if per == "slot" else F,) + tuple(H if d == "H" else d for d in tail), dtype=dt)
                     setattr(out, name, res[name].ctypes.data)
-        L.cba_model_localize_images.argtypes = [C.POINTER(CbaLocalizeImagesInput), C.POINTER(CbaLocalizeImagesOptions),
-                                                C.POINTER(CbaLocalizeImagesOutputs)]
         _check(L.cba_model_localize_images(C.byref(inp), C.byref(o), C.byref(out)), "cba_model_localize_images")
         return res
 
@@ -791,7 +772,6 @@ def schur_solve(block_diag_H: np.ndarray, off_diag_H: np.ndarray, dense_H: np.nd
     x = np.zeros(nb * bs + dd)
     if factor_tail_rows or back_substitution_panels:
         opt = CbaSolverOptions(int(factor_tail_rows), int(bool(back_substitution_panels)), 0, 0, 0)
-        L.cba_schur_solve_opt.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.POINTER(C.c_double)] * 6 + [C.POINTER(CbaSolverOptions), C.c_int32]
         _check(L.cba_schur_solve_opt(bs, nb, dd, _dp(bD), _dp(oH), _dp(dH), _dp(bb), _dp(db), _dp(x), C.byref(opt), device), "cba_schur_solve_opt")
     else:
         _check(L.cba_schur_solve(bs, nb, dd, _dp(bD), _dp(oH), _dp(dH), _dp(bb), _dp(db), _dp(x), device), "cba_schur_solve")
@@ -812,8 +792,6 @@ def reduced_system(block_diag_H: np.ndarray, off_diag_H: np.ndarray, dense_H: np
     db = np.ascontiguousarray(dense_b, dtype=np.float64)
     dd = dH.shape[0]
     assert oH.shape == (nb * bs, dd) and dH.shape == (dd, dd) and bb.size == nb * bs and db.size == dd
-    L.cba_debug_reduced_system.argtypes = ([C.c_int32] * 3 + [C.POINTER(C.c_double)] * 5 + [C.c_double, C.c_int32, C.POINTER(C.c_double),
-                                           C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int32])
     dims = np.zeros(4, dtype=np.int32)
     ip = dims.ctypes.data_as(C.POINTER(C.c_int32))
     _check(L.cba_debug_reduced_system(bs, nb, dd, None, None, None, None, None, float(lam), int(mode), None, None, ip, device),

@@ -43,6 +43,29 @@ def test_library_exports_every_symbol_declared_in_header():
     assert b"gfx950" in L.cba_version()
 
 
+def test_loaded_prototypes_match_the_header():
+    # every declaration `type name(params);` of include/cba.h: as many argtypes as parameters, restype of the declared return type
+    hdr = open(os.path.join(ROOT, "include", "cba.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    decls = re.findall(r"^((?:const\s+)?\w+\s*\*?)\s*\b(cba_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr, flags=re.M)
+    assert len(decls) == 51 and len({name for _, name, _ in decls}) == 51, [name for _, name, _ in decls]
+    L = eng.load()
+    for ret, name, params in decls:
+        fn = getattr(L, name)
+        n_params = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        assert fn.argtypes is not None and len(fn.argtypes) == n_params, (name, fn.argtypes, params)
+        ret = " ".join(ret.replace("*", " * ").split())
+        if ret == "void":
+            assert fn.restype is None, name
+        elif ret == "const char *":
+            assert fn.restype is C.c_char_p, name
+        elif ret == "int64_t":
+            assert fn.restype is not None and C.sizeof(fn.restype) == 8 and fn.restype(-1).value == -1, name
+        else:
+            assert ret in ("int", "int32_t"), (name, ret)
+            assert fn.restype is not None and C.sizeof(fn.restype) == C.sizeof(C.c_int) and fn.restype(-1).value == -1, name
+
+
 @pytest.mark.parametrize("compiler,std", [("gcc", "-std=c99"), ("g++", "-std=c++14")])
 def test_public_headers_compile_as_c99_and_cxx14(tmp_path, compiler, std):
     # include/cba.h and include/cba_rccl.h are what a C or C++ host binds: they must stay warning-free plain C

@@ -186,7 +186,6 @@ def test_error_paths_and_null_outputs():
         assert L.cba_model_compare(ma._h, mb._h, C.byref(o), None, None) == -1
         assert L.cba_model_compare(ma._h, mb._h, None, None, C.byref(st)) == -1
         assert L.cba_model_compare(None, mb._h, C.byref(o), None, C.byref(st)) == -1
-        L.cba_model_direction_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         assert L.cba_model_direction_moments(ma._h, mb._h, 0, 0, None, None) == -1
     finally:
         for m in (ma, mb, mn, ms):

@@ -478,6 +478,19 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
       for (size_t j = 0; j < dd; ++j) o[r * dd + j] = tmp[dperm[j]];
     }
   };
+  // grid-first order in one process: the grid columns of the first `rows` rows of `dst` (row stride dd; rows = border columns
+  // col0 ... of F: the pose rows of B, or the point rows of H_dd) are accumulated as S0[row of F][border column], not where the copy
+  // above looked (GfStrips)
+  auto gather_strips = [&](double* dst, size_t rows, size_t col0) -> int {
+    if (!p->gf.S0 || !rows) return CBA_OK;
+    const GfPlan& g = p->gf.plan;
+    const size_t lds = (size_t)(g.n_pad - g.Gf);
+    std::vector<double> s0(p->gf.S0.size());
+    CBA_TRY(p->gf.S0.download(s0.data(), s0.size()));
+    for (size_t r = 0; r < rows; ++r)
+      for (int e = 0; e < g.G; ++e) dst[r * dd + g.n_rp + e] = s0[(size_t)g.f_of_grid[e] * lds + col0 + r];
+    return CBA_OK;
+  };
   switch (what) {
     case CBA_DUMP_COST_VECTOR: return copy(p->cost_ref, n);
     case CBA_DUMP_TEST_COST_VECTOR: return copy(p->cost_test, n);
@@ -488,12 +501,17 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
     case CBA_DUMP_BLOCK_DIAG_B: { int rc = copy(p->bblk, nb * bs); if (rc == CBA_OK) unpermute_rows(1); return rc; }
     case CBA_DUMP_OFF_DIAG_H: {
       int rc = copy2d(p->B, nb * bs, dd);
+      if (rc == CBA_OK) rc = gather_strips(static_cast<double*>(out), nb * bs, (size_t)p->gf.plan.n_rp);
       if (rc == CBA_OK) { unpermute_rows(dd); unpermute_cols(nb * bs, 0); }
       return rc;
     }
     case CBA_DUMP_DENSE_H: {
       int rc = copy2d(p->Hdd, dd, dd);
       if (rc != CBA_OK) return rc;
+      if (p->gf.S0) {      // the point rows
+        const size_t rig = (size_t)p->gf.plan.n_rp - 3 * (size_t)L.n_points;
+        if ((rc = gather_strips(static_cast<double*>(out) + rig * dd, 3 * (size_t)L.n_points, rig)) != CBA_OK) return rc;
+      }
       // upper triangle in the engine order -> upper triangle in the reference order
       std::vector<double> tmp(dd * dd);
       std::memcpy(tmp.data(), out, tmp.size() * sizeof(double));

@@ -13,6 +13,13 @@ int alloc_gridfirst_system(cba_problem* p) {
   const size_t nf = (size_t)g.n_pad, wb = (size_t)(g.n_pad - g.Gf);
   CBA_TRY(p->gf.F.alloc_zero(nf * nf));          // tiles outside the plan's structure stay zero for ever
   CBA_TRY(p->gf.Xb.alloc_zero((size_t)g.Gf * wb));
+  const int rig_dof = g.n_rp - 3 * p->L.n_points;
+  if (!p->gf_sharded) {       // the strips accumulated in F's layout: every block column of the border without a rig column
+    CBA_TRY(p->gf.S0.alloc_zero((size_t)g.Gf * wb));
+    GfDevice& d = p->gf.dev;
+    d.s0 = p->gf.S0; d.s0_ld = (int)wb;
+    d.s0_c0 = g.nbg + (rig_dof + 63) / 64; d.s0_c1 = std::max(g.nbf, d.s0_c0);
+  }
   CBA_TRY(p->gf.xF.alloc(nf));
   CBA_TRY(p->gf.dev.tasks.assign(g.tasks));
   CBA_TRY(p->gf.dev.ivals.assign(g.ivals));
@@ -25,9 +32,14 @@ int alloc_gridfirst_system(cba_problem* p) {
   // Rule: every tile that any launch of a solve WRITES is formed again for the next attempt (a broken solve -- zero pivot, NaN --
   // must not leave anything behind: tests/test_gpu_gridfirst.py).  The dense border launch and the border update also write the
   // padding-only block columns and the block rows behind the factored ones.
+  // The strip tiles that S0 serves are the exception in form only: their task of the block-sparse launch reads S0, which no solve
+  // writes, and overwrites the tile of F -- "formed again" by the task itself, in every attempt.
   std::vector<int> tiles(g.grid_tiles);
   for (int r = 0; r < g.nbg; ++r) {
-    for (int c = g.nbg; c < g.nbf; ++c) { tiles.push_back(r); tiles.push_back(c); }
+    for (int c = g.nbg; c < g.nbf; ++c) {
+      if (c >= p->gf.dev.s0_c0 && c < p->gf.dev.s0_c1) continue;
+      tiles.push_back(r); tiles.push_back(c);
+    }
     tiles.push_back(r); tiles.push_back(g.ntc - 1);
   }
   for (int r = g.nbg; r < g.ntc; ++r)
@@ -271,7 +283,8 @@ int gridfirst_enqueue(cba_problem* p, double lambda) {
   const GfDevice& d = p->gf.dev;
   // (image sharding: H_dd / b_d hold the sums over the ranks, the pose rows of all ranks are in gDblk / gbblk / gB -- gf_exchange)
   const bool sh = p->gf_sharded;
-  CBA_TRY(launch_gf_form(p->gf.F, ld, g.Gf, g.n_rp, g.n_border, p->gf.grid_of_f, p->Hdd, p->n_pad, p->bd, sh ? p->sh.gB : p->B, sh ? p->sh.gDblk : p->Dblk,
+  CBA_TRY(launch_gf_form(p->gf.F, ld, g.Gf, g.n_rp, g.n_border, p->gf.grid_of_f, p->Hdd, p->n_pad, p->bd, sh ? p->sh.gB : p->B, d.s0, d.s0_ld,
+                         g.n_rp - 3 * L.n_points, sh ? p->sh.gDblk : p->Dblk,
                          sh ? p->sh.gbblk : p->bblk, lambda, p->gf.tiles, p->gf.n_tiles, d.act, d.act_words, p->stream));
   GemmStats gs;
   CBA_TRY(timer_begin(p, kTimerFactor));

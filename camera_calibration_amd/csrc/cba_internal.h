@@ -159,8 +159,15 @@ int launch_fd_tasks(const PassArgs& a, int model_mask, int tasks_per_obs, int lo
 // ---- kernels_obs.hip (stage B: Jacobian records and their accumulation; the records are a.jrec, a.rec_doubles apart) ----
 int launch_assemble(const PassArgs& a, const Layout& L, const DevState& st, int tasks_per_obs, const double* pixels, uint8_t* flags,
                     const double* fd_out, const uint8_t* fd_ok, int* cells, uint8_t* fd_slow, hipStream_t s);
+// Grid-first order, one process: the grid rows x (point | pose) columns of F are accumulated where the
+// factorisation reads them -- S0[f_of_grid[grid column - n_rp]][border column], leading dimension ld, cleared before the pass --
+// not as the grid columns of B's pose rows and of H_dd's point rows.  S0 = null: those rows (every other order and path).
+struct GfStrips {
+  double* S0; int ld; const int* f_of_grid; int n_rp;
+};
 struct AccumTargets {
   double* Dblk; double* bblk; double* B; double* Hdd; double* bd;
+  GfStrips gf;
 };
 static_assert(std::is_trivially_copyable_v<AccumTargets>);
 int launch_accumulate(const PassArgs& a, const Layout& L, const uint8_t* flags, const int* cells, const uint32_t* pair_tables,
@@ -172,7 +179,8 @@ int launch_accumulate_points(const PassArgs& a, const Layout& L, const std::vect
 int launch_det_scale(const PassArgs& a, const uint8_t* flags, DevBuf<unsigned long long>& bits, double* scale, hipStream_t s);
 int launch_det_convert(double* p, size_t n, const double* det_scale, hipStream_t s);
 int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, const uint8_t* flags, const int* cells,
-                             unsigned long long* band_mask, const int64_t* img_start, double* B, int ld, const double* det_scale, hipStream_t s);
+                             unsigned long long* band_mask, const int64_t* img_start, double* B, int ld, const GfStrips& gf,
+                             const double* det_scale, hipStream_t s);
 int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const std::vector<int>& cell_base_host, int ld,
                             const uint8_t* flags, const int* cells, const int* cell_base, DevBuf<int>& count, int* start, DevBuf<int>& fill, int* order,
                             double* Hdd, int rig_row_first, const double* det_scale, double* bd, hipStream_t s);
@@ -410,6 +418,10 @@ struct GfDevice {
   DevBuf<unsigned long long> gridrow;          // [nbg][act_words]: structure of the grid x grid factor's rows (closure of the activity)
   DevBuf<unsigned long long> kmask; int kmask_words = 0;      // border update: [absolute 128-column tile][words], bit = 16-row K slab
   DevBuf<unsigned long long> rowmask_dyn;      // back substitution: rowmask with the border bits of the grid rows from `act`
+  // pristine strips (GfStrips; null = none): the block-sparse launch takes the input of its border tiles in block columns
+  // s0_c0 ... s0_c1 - 1 of F (point and pose columns only; a block with a rig column or the right-hand side is formed in F) from
+  // s0[row of F][column of F - 64 nbg], leading dimension s0_ld
+  const double* s0 = nullptr; int s0_ld = 0, s0_c0 = 0, s0_c1 = 0;
 };
 // F = [grid | border] in the plan's order, ld = its n_pad; Xb: (rows of the grid part) x (ld - Gf) panel buffer (zero outside the
 // tiles the launch writes); kmask: optional block-sparsity of the border update (null = dense); tile_list: optional order of its
@@ -443,8 +455,8 @@ int ldlt_factor_distributed(double* S, int n, int ld, LdltWorkspace& w, hipStrea
 
 // ---- kernels_gridfirst.hip ----
 int launch_gf_form(double* F, int ldf, int Gf, int n_rp, int n_border, const int* grid_of_f, const double* Hdd, int ldh, const double* bd,
-                   const double* B, const double* Dblk, const double* bblk, double lambda, const int* tiles, int n_tiles,
-                   const unsigned long long* act, int act_words, hipStream_t s);
+                   const double* B, const double* S0, int lds0, int rig_dof, const double* Dblk, const double* bblk, double lambda,
+                   const int* tiles, int n_tiles, const unsigned long long* act, int act_words, hipStream_t s);
 int launch_gf_activity(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
                        int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, DevBuf<unsigned long long>& act,
                        unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,

@@ -125,6 +125,7 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
     CBA_TRY(p->B.zero_async((size_t)(p->Kpad - L.block_dof) * p->n_pad, clr, (size_t)L.block_dof * p->n_pad));
   CBA_TRY(p->Hdd.zero_async(clr));
   CBA_TRY(p->bd.zero_async(clr));
+  if (p->gf.S0) CBA_TRY(p->gf.S0.zero_async(clr));      // grid-first order: the strips of F (the accumulation stores only what it reaches)
   CBA_HIP(hipEventRecord(p->ev_clear, clr));
   CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_aux1, 0));
   CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_clear, 0));
@@ -141,6 +142,11 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   const double* det = p->cfg.deterministic ? (const double*)p->det_scale : nullptr;
   if (det) CBA_TRY(launch_det_scale(a, p->flags, p->det_bits, p->det_scale, p->stream));
   const int points_separate = (!L.eliminate_points && p->pt_start) ? 1 : 0;
+  // grid-first order, one process: grid rows x (point | pose) columns go straight to the strips of F (GfStrips)
+  if (p->gf.S0) {
+    if (!points_separate && p->n_obs > 0) { set_error("grid-first order: no per-point observation lists"); return CBA_ERR_STATE; }
+    T.gf = GfStrips{p->gf.S0, p->gf.plan.n_pad - p->gf.plan.Gf, p->gf.f_of_grid, p->gf.plan.n_rp};
+  }
   // The four accumulation kernels write disjoint parts of the system (or add atomically).  The per-cell kernel runs on the side
   // stream next to the others; the per-point kernel (120 KB of LDS per workgroup, one per CU) goes FIRST on the main stream, alone:
   // next to the strips kernel its workgroups rarely find a CU with that much LDS free and the launch takes 3.9 ms instead of
@@ -157,7 +163,7 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   if (points_separate)
     CBA_TRY(launch_accumulate_points(a, Lp, p->cams, p->flags, p->cells, p->pt_start, p->pt_obs, T, det, p->stream));
   if (!L.eliminate_points)   // B strips (plain stores), the remaining terms are added on top atomically
-    CBA_TRY(launch_accumulate_strips(a, Lp, L.n_images, p->flags, p->cells, p->band_mask, p->img_start, p->B, p->n_pad, det, p->stream));
+    CBA_TRY(launch_accumulate_strips(a, Lp, L.n_images, p->flags, p->cells, p->band_mask, p->img_start, p->B, p->n_pad, T.gf, det, p->stream));
   CBA_TRY(launch_accumulate(a, Lp, p->flags, p->cells, p->pair_tables, p->pair_counts, T, det, points_separate, p->stream));
   if (side) CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_aux1, 0));
   if (det) {   // fixed point -> fp64, in place
@@ -166,6 +172,7 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
     CBA_TRY(launch_det_convert(p->Hdd, (size_t)L.dense_dof * p->n_pad, det, p->stream));
     CBA_TRY(launch_det_convert(p->bd, (size_t)p->n_pad, det + 1, p->stream));
     CBA_TRY(launch_det_convert(p->B, (size_t)L.block_dof * p->n_pad, det, p->stream));   // strips store integers, the pose x rig atomics add to them
+    if (p->gf.S0) CBA_TRY(launch_det_convert(p->gf.S0, p->gf.S0.size(), det, p->stream));
   }
   CBA_TRY(timer_end(p, kTimerAccumulate, 0, 0, 1));
   if (t_acc) *t_acc += now_s() - t0;

@@ -48,12 +48,17 @@ struct PoseFirstState {
 };
 
 // Grid-first elimination order (cba_solver_options.elimination; gridfirst_plan.h; cba_gridfirst.hip): the full normal matrix F = [grid |
-// rig | points | poses] is formed from Dblk / B / Hdd per LM attempt and factored in place; nothing of PoseFirstState is allocated
+// rig | points | poses] is formed from Dblk / B / Hdd (/ S0) per LM attempt and factored in place; nothing of PoseFirstState is allocated
 struct GridFirstState {
   GfPlan plan;
   GfDevice dev;
   DevBuf<double> F;               // plan.n_pad x plan.n_pad, upper triangle, row-major
   DevBuf<double> Xb;              // plan.Gf x (plan.n_pad - plan.Gf): X = D L of the border columns (B operand of the border update)
+  // Xb's geometry: the grid rows x border columns of F as the Jacobian pass accumulates them (GfStrips; cleared per pass, never written
+  // by a solve).  The block-sparse launch reads its strip tiles from here and writes L over the same tiles of F, so these tiles
+  // are not formed (GfDevice::s0_c0 / s0_c1: the block columns it serves).  Empty with image sharding (the pose rows of the other
+  // ranks arrive as rows of B).
+  DevBuf<double> S0;
   DevBuf<double> xF;              // plan.n_fact: solution in the order of F
   DevBuf<int> tiles; int n_tiles = 0;        // tiles of F the forming kernel writes
   DevBuf<int> grid_of_f, f_of_grid;

@@ -3,7 +3,9 @@
 //                 the right-hand side in the last column) from what the accumulation kernels wrote: the pose blocks D_i / b_i, the
 //                 strips B (pose rows x dense columns) and the dense part H_dd / b_d (lm_optimizer_update_accumulator.h:108-155 is
 //                 the reference's layout of the same four parts).  The factorisation works in place, so F is formed once per LM
-//                 attempt (the pose-first path pays D^-1 B and the C read of the Schur product at the same point);
+//                 attempt (the pose-first path pays D^-1 B and the C read of the Schur product at the same point) -- except, in a
+//                 single process, the grid rows x (point | pose) columns: the accumulation writes them in F's layout into a buffer
+//                 of their own (S0, GfStrips) that the block-sparse launch reads in F's place, so nothing is formed for them;
 //   k_gf_scatter  takes the solution of F x = b back to the engine's x = [poses in slot order | dense columns].
 // F keeps its upper triangle in row-major order like every symmetric matrix of the engine (kernels_linalg.hip).  Entries whose
 // source is stored "the other way round" -- grid rows against rig / point / pose columns, rig / point rows against pose columns:
@@ -23,6 +25,8 @@ struct GfFormArgs {
   const double* Hdd; int ldh;    // engine dense order [rig | points | grid], upper, row-major
   const double* bd;
   const double* B;               // rows 6 slot + k, columns = engine dense order, row stride ldh
+  const double* S0; int lds0;    // optional (GfStrips): grid rows x (point | pose) columns in F's layout, [row of F][column of F - Gf]
+  int rig_dof;                   // rig columns at the head of the border (S0 does not hold them: H_dd does)
   const double* Dblk; const double* bblk;
   double lambda;
   const int2* tiles;             // 64 x 64 tiles (block row, block column) of F to form
@@ -51,6 +55,9 @@ __global__ void __launch_bounds__(256) k_gf_form(GfFormArgs a) {
   else if (tid < 128) s_cj[tid - 64] = gf_class(a, j0 + tid - 64);
   __syncthreads();
   const bool rhs_tile = j0 + 64 == a.ldf;
+  // grid rows x border columns with S0: the point and pose columns are there, in place (of the strips only the block columns with
+  // a rig column or the right-hand side are formed at all: alloc_gridfirst_system)
+  const bool s0_tile = a.S0 && i0 < a.Gf && j0 >= a.Gf;
   // ---- transposed sources: one column of the tile per wavefront and step, lanes along the rows ----
   const int ci = s_ci[lane];
   for (int jj = wv; jj < 64; jj += 4) {
@@ -58,6 +65,7 @@ __global__ void __launch_bounds__(256) k_gf_form(GfFormArgs a) {
     if (rhs_tile && jj == 63) continue;
     double v = 0.0;
     bool t = false;
+    if (s0_tile && (cj <= -2 || cj >= a.rig_dof)) continue;
     if (ci >= 0) {
       if (cj <= -2) { t = true; v = a.B[(size_t)(-2 - cj) * a.ldh + ci]; }                    // dense row x pose column
       else if (cj >= 0 && cj < ci) { t = true; v = a.Hdd[(size_t)cj * a.ldh + ci]; }            // grid row x rig / point column
@@ -77,7 +85,8 @@ __global__ void __launch_bounds__(256) k_gf_form(GfFormArgs a) {
       else if (cr <= -2) v = a.bblk[-2 - cr];
     } else if (cr == -1 || cj == -1) v = (fi == fj) ? 1.0 : 0.0;  // padding rows / columns: identity
     else if (cr >= 0) {
-      if (cj <= -2 || cj < cr) v = sT[lane][ii];
+      if (s0_tile && (cj <= -2 || cj >= a.rig_dof)) v = a.S0[(size_t)fi * a.lds0 + (fj - a.Gf)];
+      else if (cj <= -2 || cj < cr) v = sT[lane][ii];
       else v = a.Hdd[(size_t)cr * a.ldh + cj] + (fi == fj ? a.lambda : 0.0);
     } else {                                                      // pose row: pose column of the same imageset, or zero
       const int pr = -2 - cr, pc = -2 - cj;
@@ -88,10 +97,11 @@ __global__ void __launch_bounds__(256) k_gf_form(GfFormArgs a) {
 }
 
 int launch_gf_form(double* F, int ldf, int Gf, int n_rp, int n_border, const int* grid_of_f, const double* Hdd, int ldh, const double* bd,
-                   const double* B, const double* Dblk, const double* bblk, double lambda, const int* tiles, int n_tiles,
-                   const unsigned long long* act, int act_words, hipStream_t s) {
+                   const double* B, const double* S0, int lds0, int rig_dof, const double* Dblk, const double* bblk, double lambda,
+                   const int* tiles, int n_tiles, const unsigned long long* act, int act_words, hipStream_t s) {
   if (n_tiles <= 0) return CBA_OK;
   GfFormArgs a{};
+  a.S0 = S0; a.lds0 = lds0; a.rig_dof = rig_dof;
   a.act = act; a.act_words = act_words; a.nbg = Gf / 64;
   a.F = F; a.ldf = ldf; a.Gf = Gf; a.n_rp = n_rp; a.n_border = n_border; a.grid_of_f = grid_of_f;
   a.Hdd = Hdd; a.ldh = ldh; a.bd = bd; a.B = B; a.Dblk = Dblk; a.bblk = bblk; a.lambda = lambda;

@@ -281,6 +281,7 @@ static int ldlt_sparse(double* F, int ld, const GfDevice& g, LdltWorkspace& w, h
   t.rt0 = 0; t.nr = g.nbg;
   t.tasks = g.tasks; t.ivals = g.ivals; t.chains = g.chains; t.n_chains = g.n_chains;
   t.act = g.act; t.act_words = g.act_words;
+  t.S0 = g.s0; t.lds0 = g.s0_ld; t.s0_c0 = g.s0_c0; t.s0_c1 = g.s0_c1;
   t.ntasks_x[0] = g.n_tasks0; t.ntasks_x[1] = g.n_tasks1;
   t.ntasks = g.n_tasks0 + g.n_tasks1;
   t.evict = 1;

@@ -476,7 +476,8 @@ __global__ void __launch_bounds__(256) k_accumulate_poses(PassArgs a, AccumLayou
 // and one workgroup per bucket and column chunk
 //   * sums the 6 + 3 (+ 18) dense entries in registers -> one atomic per entry (several cameras share a point),
 //   * sums the three point rows over the camera's grid columns in LDS (3 x chunk_cols doubles, LDS atomics) and writes
-//     them out with plain coalesced stores: (point rows) x (grid columns of this camera) belong to this bucket alone.
+//     them out with plain coalesced stores: (point rows) x (grid columns of this camera) belong to this bucket alone
+//     (grid-first order in one process: as the point columns of the grid rows of F instead, GfStrips).
 // That replaces 9 + 3 K_g global atomics per observation (105 / 249 of them, 456-way contended on the point entries at
 // BASELINE configs[1]) by K_g LDS atomics and 3 x (grid columns) stores per point.
 // ------------------------------------------------------------------------------------------------
@@ -558,10 +559,26 @@ __global__ void __launch_bounds__(kPointThreads) k_accumulate_points(PassArgs a,
       }
     }
     __syncthreads();
+    if (T.gf.S0) {
+      // grid-first order: the three entries of a column side by side in the column's row of F (24-byte pieces at a row stride), and
+      // only the columns an observation reached -- S0 is cleared before the pass like H_dd, and a sum that starts at +0 never ends
+      // at -0, so a column whose three sums have no bit set is exactly what the clear left there
+      const int* __restrict__ fog = T.gf.f_of_grid + (cd.intr_offset - T.gf.n_rp + c0);
+      double* out = T.gf.S0 + (point_idx - L.block_dof);
+      for (int i = tid; i < 3 * (c1 - c0); i += NT) {
+        const int c = i / 3, r = i - 3 * c;
+        const unsigned long long* s = reinterpret_cast<const unsigned long long*>(s_rows) + c;
+        const unsigned long long v0 = s[0], v1 = s[chunk_cols], v2 = s[2 * chunk_cols];
+        if ((v0 | v1 | v2) == 0ull) continue;
+        const unsigned long long v = r == 0 ? v0 : (r == 1 ? v1 : v2);
+        reinterpret_cast<unsigned long long*>(out)[(size_t)fog[c] * T.gf.ld + r] = v;
+      }
+    } else {
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      double* out = T.Hdd + (size_t)(point_idx - L.block_dof + r) * L.dense_dof + cd.intr_offset + c0;
-      for (int c = tid; c < c1 - c0; c += NT) out[c] = s_rows[r * chunk_cols + c];
+      for (int r = 0; r < 3; ++r) {
+        double* out = T.Hdd + (size_t)(point_idx - L.block_dof + r) * L.dense_dof + cd.intr_offset + c0;
+        for (int c = tid; c < c1 - c0; c += NT) out[c] = s_rows[r * chunk_cols + c];
+      }
     }
   }
   if (chunk != 0) return;
@@ -858,6 +875,9 @@ int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& ca
 // sums the 6 x (3 + K_cell) products that fall into its band in LDS (ds_add_f64) and writes the band of
 // the six rows with plain coalesced stores -- zeros included, so B needs no memset and receives no
 // global atomics from these terms (210 of the ~350 per observation).
+// Grid-first order in one process (GfStrips): the rig / point columns still go to B like that, but the grid columns are stored
+// transposed, as the pose columns of the grid rows of F (S0), and only where an observation reached -- the pass clears S0, the
+// factorisation reads it in place, and nothing re-forms these entries per LM attempt (kernels_gridfirst.hip).
 //
 // The wavefronts are filled per kind of column:
 //   * point columns: one lane per (observation, point column), kStripPointGroup = 21 observations of the imageset per
@@ -904,7 +924,7 @@ __global__ void __launch_bounds__(64 * kStripWaves) k_accumulate_strips(PassArgs
                                                             const double* __restrict__ jrec, const int* __restrict__ cells,
                                                             const unsigned long long* __restrict__ band_mask,
                                                             const int64_t* __restrict__ img_start, double* __restrict__ B, int ld,
-                                                            const double* __restrict__ det_scale) {
+                                                            GfStrips gf, const double* __restrict__ det_scale) {
   constexpr int U = kStripUnroll, G = kStripPointGroup;
   __shared__ double acc[6][kStripBand];      // DET: the same 8-byte slots hold fixed-point integers (zero bits = 0 in both)
   __shared__ int s_per[kMaxCameras], s_gw[kMaxCameras], s_off[kMaxCameras];      // per camera: parameters per control point, grid width, first column
@@ -1041,15 +1061,39 @@ __global__ void __launch_bounds__(64 * kStripWaves) k_accumulate_strips(PassArgs
   }
   __syncthreads();
   const int slot = a.pose_slot ? a.pose_slot[img] : img;
+  // grid-first order: only the rig / point columns go to B, zeros included (the pose x rig-pose atomics add to them)
+  const int b_cols = (gf.S0 ? min(col_hi, gf.n_rp) : col_hi) - col_lo;
   for (int k = 0; k < 6; ++k) {
     double* row = B + (size_t)(6 * slot + k) * ld + col_lo;
     // DET: the fixed-point integers as they are -- k_accumulate adds integer atomics on top (pose x rig-pose entries) and
     // the whole of B is converted afterwards (launch_det_convert)
-    for (int c = threadIdx.x; c < col_hi - col_lo; c += 64 * kStripWaves) row[c] = acc[k][c];
+    for (int c = threadIdx.x; c < b_cols; c += 64 * kStripWaves) row[c] = acc[k][c];
+  }
+  if (!gf.S0 || col_hi <= gf.n_rp) return;      // (uniform)
+  // ... and the grid columns to S0: the six pose entries of a column side by side in the column's row of F (48-byte pieces at a row
+  // stride), and only the columns an observation reached -- one bit per column; the clear of the pass supplies every other entry
+  // (a sum that starts at +0 never ends at -0: a column whose six sums have no bit set is what the clear left there)
+  __shared__ unsigned long long s_reach[kStripBand / 64];
+  const unsigned long long* accb = reinterpret_cast<const unsigned long long*>(&acc[0][0]);
+  for (int c = threadIdx.x; c < kStripBand; c += 64 * kStripWaves) {      // (c >> 6 is uniform in a wavefront)
+    unsigned long long any = 0ull;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) any |= accb[k * kStripBand + c];
+    const unsigned long long word = __ballot(any != 0ull && col_lo + c >= gf.n_rp && col_lo + c < col_hi);
+    if (lane == 0) s_reach[c >> 6] = word;
+  }
+  __syncthreads();
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(gf.S0) + gf.n_rp + 6 * slot;
+  const int* __restrict__ fog = gf.f_of_grid + (col_lo - gf.n_rp);
+  for (int i = threadIdx.x; i < 6 * kStripBand; i += 64 * kStripWaves) {
+    const int c = i / 6, k = i - 6 * c;
+    if (!((s_reach[c >> 6] >> (c & 63)) & 1ull)) continue;
+    out[(size_t)fog[c] * gf.ld + k] = accb[k * kStripBand + c];
   }
 }
 int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, const uint8_t* flags, const int* cells,
-                             unsigned long long* band_mask, const int64_t* img_start, double* B, int ld, const double* det_scale, hipStream_t s) {
+                             unsigned long long* band_mask, const int64_t* img_start, double* B, int ld, const GfStrips& gf,
+                             const double* det_scale, hipStream_t s) {
   if (n_images == 0) return CBA_OK;
   const AccumLayout al = accum_layout(L);
   const int bands = (ld + kStripBand - 1) / kStripBand;
@@ -1057,7 +1101,7 @@ int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, c
     hipLaunchKernelGGL(k_strip_band_mask, dim3((unsigned)((a.n_obs + 255) / 256)), dim3(256), 0, s, a, flags, cells, band_mask, bands);
   by_flag(det_scale != nullptr, [&](auto det) {
     hipLaunchKernelGGL(k_accumulate_strips<decltype(det)::value>, dim3((unsigned)n_images, (unsigned)bands), dim3(64 * kStripWaves), 0, s, a, al, L.n_points,
-                       a.rec_doubles, flags, a.jrec, cells, band_mask, img_start, B, ld, det_scale);
+                       a.rec_doubles, flags, a.jrec, cells, band_mask, img_start, B, ld, gf, det_scale);
   });
   CBA_HIP(hipGetLastError());
   return CBA_OK;

@@ -86,7 +86,20 @@ struct TailArgs {
   int n_critical;                   // helper workgroups (roles n_chains ... n_chains + n_critical - 1) that serve list 0 first
   const unsigned long long* act;    // optional activity of the border tiles: [(c - x_c0) / 2][act_words], bit r = block row r of the 128-column
   int act_words;                    // tile can be non-zero (kernels_gridfirst.hip: k_gf_touch / k_gf_close); inactive tiles are neither computed nor read
+  // block-sparse launch only: the input A_rc of a border tile in block columns s0_c0 ... s0_c1 - 1 is S0[64 r + p][64 (c - x_c0) + q]
+  // (leading dimension lds0; written by the Jacobian pass, by no solve), not the tile of S, which only receives L_rc; null = all from S
+  const double* S0; int lds0, s0_c0, s0_c1;
 };
+// where a REG / REG2 task of the block-sparse launch fetches its tile (r, c) from: base and leading dimension (uniform)
+template <bool SPARSE>
+__device__ __forceinline__ const double* tail_tile_input(const TailArgs& t, int r, int c, int* ld_in) {
+  if (SPARSE && t.S0 && c >= t.s0_c0 && c < t.s0_c1) {
+    *ld_in = t.lds0;
+    return t.S0 + (size_t)r * kInner * t.lds0 + (size_t)(c - t.x_c0) * kInner;
+  }
+  *ld_in = t.ld;
+  return t.S + (size_t)r * kInner * t.ld + (size_t)c * kInner;
+}
 static_assert(std::is_trivially_copyable_v<TailArgs>);
 // first block row >= k (< kend) whose bit is set / clear in `bits`; kend if there is none
 __device__ __forceinline__ int bits_next(const unsigned long long* bits, int k, int kend, bool want_set) {
@@ -873,16 +886,19 @@ __device__ __forceinline__ bool tail_helper_pair(const TailArgs& t, double* sV, 
   const int wm0 = (wv >> 1) * 32, half = wv & 1;
   {
     // U = A_rc - acc, straight into the accumulator registers (the tiles were written before this launch: fetched now, one round trip
-    // per task; prefetching them underneath the K loop would cost 64 more live registers)
-    const __amdgpu_buffer_rsrc_t rt = tail_rsrc(t.S + (size_t)r * kInner * ld + (size_t)(c + half) * kInner);
-    const int voff = ((wm0 + lk) * ld + li) * 8;
+    // per task; prefetching them underneath the K loop would cost 64 more live registers) -- or, the point and pose columns, into
+    // the pristine strips S0 by the Jacobian pass: read there, in every attempt, and never formed in S (this function serves the
+    // block-sparse launch only)
+    int ldi;
+    const __amdgpu_buffer_rsrc_t rt = tail_rsrc(tail_tile_input<true>(t, r, c + __builtin_amdgcn_readfirstlane(half), &ldi));
+    const int voff = ((wm0 + lk) * ldi + li) * 8;
     double a[2][4][4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) a[i][j][r4] = tail_ld1(rt, voff, ((16 * i + 4 * r4) * ld + 16 * j) * 8);
+        for (int r4 = 0; r4 < 4; ++r4) a[i][j][r4] = tail_ld1(rt, voff, ((16 * i + 4 * r4) * ldi + 16 * j) * 8);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1048,12 +1064,24 @@ __device__ __forceinline__ void tail_helper(const TailArgs& t, double* sV, doubl
     const __amdgpu_buffer_rsrc_t rt = tail_rsrc(t.S + (size_t)row0 * ld + (size_t)c * kInner);
     const int acc_voff = ((wm0 + lk) * ld + wn0 + li) * 8;
     double a_rc[2][2][4];
+    if (SPARSE && kind == 2 && t.S0 && c >= t.s0_c0 && c < t.s0_c1) {      // a border tile of the pristine strips (tail_tile_input)
+      int ldi;
+      const __amdgpu_buffer_rsrc_t ri = tail_rsrc(tail_tile_input<true>(t, r, c, &ldi));
+      const int voff = ((wm0 + lk) * ldi + wn0 + li) * 8;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int jj = 0; jj < 2; ++jj)
+        for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) a_rc[i][jj][r4] = tail_ld1(rt, acc_voff, ((16 * i + 4 * r4) * ld + 16 * jj) * 8);
+          for (int r4 = 0; r4 < 4; ++r4) a_rc[i][jj][r4] = tail_ld1(ri, voff, ((16 * i + 4 * r4) * ldi + 16 * jj) * 8);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+          for (int r4 = 0; r4 < 4; ++r4) a_rc[i][jj][r4] = tail_ld1(rt, acc_voff, ((16 * i + 4 * r4) * ld + 16 * jj) * 8);
+    }
     for (int iv = 0; iv < n_iv; ++iv) {
       int k = t.rt0, kend = r;
       if (SPARSE) {

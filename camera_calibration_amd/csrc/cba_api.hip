@@ -531,6 +531,13 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
       unpermute_cols(1, L.block_dof);
       return CBA_OK;
     }
+    case CBA_DUMP_CELLS: return copy(p->cells, 2 * n);
+    case CBA_DUMP_POSE_SLOT: {
+      if (bytes < (size_t)L.n_images * sizeof(int32_t)) { set_error("cba_debug_dump: buffer too small"); return CBA_ERR_ARG; }
+      int32_t* o = static_cast<int32_t*>(out);
+      for (int i = 0; i < L.n_images; ++i) o[i] = p->pose_slot_host.empty() ? i : p->pose_slot_host[i];
+      return CBA_OK;
+    }
     default: set_error("cba_debug_dump: unknown item"); return CBA_ERR_ARG;
   }
 }

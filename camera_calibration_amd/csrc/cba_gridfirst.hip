@@ -2,6 +2,7 @@
 // the per-pass activity masks, the exchange between ranks, the tile order of the border update, the solve.
 #include <algorithm>
 #include <cstring>
+#include <limits>
 
 #include "cba_problem.h"
 
@@ -275,7 +276,8 @@ static void gf_build_tile_list(cba_problem* p, int nt, int n_slabs, Weight weigh
 // Grid-first order: F formed from the accumulated parts, block-sparse launch of the grid rows, border update, dense border,
 // masked back substitution, x back in the engine's layout -- between the status words and the status launch of solve_enqueue.
 // Timers: kTimerProduct = the border update (the K = Gf product), kTimerFactor = the whole factorisation.
-int gridfirst_enqueue(cba_problem* p, double lambda) {
+// last_stage (GfStage): the launches up to and including that stage; a solve runs all of them, cba_debug_gridfirst stops in between.
+int gridfirst_enqueue(cba_problem* p, double lambda, int last_stage) {
   const Layout& L = p->L;
   const GfPlan& g = p->gf.plan;
   const int ld = g.n_pad;
@@ -286,6 +288,7 @@ int gridfirst_enqueue(cba_problem* p, double lambda) {
   CBA_TRY(launch_gf_form(p->gf.F, ld, g.Gf, g.n_rp, g.n_border, p->gf.grid_of_f, p->Hdd, p->n_pad, p->bd, sh ? p->sh.gB : p->B, d.s0, d.s0_ld,
                          g.n_rp - 3 * L.n_points, sh ? p->sh.gDblk : p->Dblk,
                          sh ? p->sh.gbblk : p->bblk, lambda, p->gf.tiles, p->gf.n_tiles, d.act, d.act_words, p->stream));
+  if (last_stage <= kGfStageForm) return CBA_OK;
   GemmStats gs;
   CBA_TRY(timer_begin(p, kTimerFactor));
   const int* tile_list = nullptr;
@@ -297,8 +300,9 @@ int gridfirst_enqueue(cba_problem* p, double lambda) {
     tile_list = p->gf.tile_list;
   }
   CBA_TRY(ldlt_factor_gridfirst(p->gf.F, g.n_fact, ld, d, p->gf.Xb, ld - g.Gf, p->ldlt, p->stream, &gs, d.kmask, d.kmask_words, tile_list,
-                                tile_list ? p->gf.tile_list_entries : 0));
+                                tile_list ? p->gf.tile_list_entries : 0, std::min(last_stage, (int)kGfStageBorder) - kGfStageGridRows));
   CBA_TRY(timer_end(p, kTimerFactor, gs.flops, 0, gs.launches));
+  if (last_stage < kGfStageBack) return CBA_OK;
   CBA_TRY(ldlt_back_solve(p->gf.F, g.n_fact, ld, ld - 1, p->ldlt, p->gf.xF, p->stream, d.rowmask_dyn, d.mask_words));
   CBA_TRY(launch_gf_scatter(p->gf.xF, g.Gf, g.n_rp, L.block_dof, g.G, p->gf.f_of_grid, sh ? 6 * p->sh.img0 : 0, p->x, p->stream));
   return CBA_OK;
@@ -336,6 +340,127 @@ void gridfirst_finish(cba_problem* p) {
       return 0;
     });
 }
+
+// ---- cba_debug_gridfirst: the stages of a solve one by one, on the problem's own buffers (tests/test_gpu_gridfirst_stages.py) ----
+// Fills the 64 x 128 grid x border tiles whose activity bit is off: M = F (col0 = Gf) or S0 (col0 = 0), one workgroup per (block row,
+// border tile).  Rows < 64 nbg, columns < col0 + 128 n_act_tiles = the width of M: inside both buffers.
+__global__ void __launch_bounds__(256) k_gf_debug_fill(double* __restrict__ M, size_t ld, int col0, const unsigned long long* __restrict__ act,
+                                                       int act_words, double v) {
+  const int r = blockIdx.x, t = blockIdx.y;
+  if ((act[(size_t)t * act_words + (r >> 6)] >> (r & 63)) & 1ull) return;
+  for (int i = threadIdx.x; i < 64 * 128; i += 256) M[(size_t)(64 * r + (i >> 7)) * ld + col0 + 128 * t + (i & 127)] = v;
+}
+static int gf_debug_fill(cba_problem* p, double v) {
+  const GfPlan& g = p->gf.plan;
+  const GfDevice& d = p->gf.dev;
+  if (g.nbg <= 0 || d.n_act_tiles <= 0) return CBA_OK;
+  const dim3 grid((unsigned)g.nbg, (unsigned)d.n_act_tiles);
+  hipLaunchKernelGGL(k_gf_debug_fill, grid, dim3(256), 0, p->stream, (double*)p->gf.F, (size_t)g.n_pad, g.Gf, (const unsigned long long*)d.act, d.act_words, v);
+  if (p->gf.S0)
+    hipLaunchKernelGGL(k_gf_debug_fill, grid, dim3(256), 0, p->stream, (double*)p->gf.S0, (size_t)(g.n_pad - g.Gf), 0, (const unsigned long long*)d.act, d.act_words, v);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+}  // namespace cba
+
+extern "C" int cba_debug_gridfirst(cba_problem* p, double lambda, int32_t stage, int32_t poison, int32_t what, void* out, size_t bytes) {
+  if (!p || !out || stage < -1 || stage > kGfStageBack) { set_error("cba_debug_gridfirst: bad argument"); return CBA_ERR_ARG; }
+  if (!p->gridfirst || p->gf_sharded) { set_error("cba_debug_gridfirst: not the grid-first order in one process"); return CBA_ERR_UNSUPPORTED; }
+  if (!p->have_system) { set_error("cba_debug_gridfirst: no accumulated system"); return CBA_ERR_STATE; }
+  CBA_HIP(hipSetDevice(p->device));
+  const Layout& L = p->L;
+  const GfPlan& g = p->gf.plan;
+  const GfDevice& d = p->gf.dev;
+  hipStream_t s = p->stream;
+  CBA_HIP(hipStreamSynchronize(s));
+  int rc = CBA_OK;
+  if (stage >= 0) {
+    if (poison) CBA_TRY(gf_debug_fill(p, std::numeric_limits<double>::quiet_NaN()));
+    CBA_TRY(p->status.zero_async(1, s));
+    CBA_TRY(p->ldlt.status.zero_async(s));
+    rc = gridfirst_enqueue(p, lambda, stage);
+    CBA_HIP(hipStreamSynchronize(s));
+    if (poison) {        // the poisoned tiles back to what the passes leave in them
+      CBA_TRY(gf_debug_fill(p, 0.0));
+      CBA_HIP(hipStreamSynchronize(s));
+    }
+    if (rc != CBA_OK) return rc;
+    int st[2] = {0, 0};
+    CBA_TRY(p->status.download(&st[0], 1));
+    CBA_TRY(p->ldlt.status.download(&st[1], 1));
+    if (st[1] == 3) { set_error("cba_debug_gridfirst: a dataflow launch timed out waiting for another workgroup"); return CBA_ERR_TIMEOUT; }
+    if (st[0] || st[1]) { set_error("cba_debug_gridfirst: zero pivot or non-finite value"); rc = CBA_ERR_NUMERIC; }      // (the item is still returned)
+  }
+  auto need = [&](size_t n) -> int {
+    if (bytes < n) { set_error("cba_debug_gridfirst: buffer too small"); return CBA_ERR_ARG; }
+    return CBA_OK;
+  };
+  using u64 = unsigned long long;
+  const size_t nf = (size_t)g.n_pad, wb = (size_t)(g.n_pad - g.Gf);
+  switch (what) {
+    case CBA_GF_DIMS: {
+      const int32_t v[12] = {d.act_words, d.n_act_tiles, d.kmask_words, g.n_pad / 128, d.mask_words, g.nbf, d.s0_c0, d.s0_c1,
+                             p->gf.n_tiles, g.nbg, g.ntc, p->gf.S0 ? 1 : 0};
+      CBA_TRY(need(sizeof(v)));
+      std::memcpy(out, v, sizeof(v));
+      break;
+    }
+    case CBA_GF_FORM_TILES:
+      CBA_TRY(need(sizeof(int) * 2 * (size_t)p->gf.n_tiles));
+      CBA_TRY(p->gf.tiles.download(static_cast<int*>(out), 2 * (size_t)p->gf.n_tiles));
+      break;
+    case CBA_GF_TOUCHED: {
+      const size_t n = (size_t)d.n_act_tiles * d.act_words;
+      CBA_TRY(need(sizeof(u64) * n));
+      DevBuf<u64> tmp;
+      CBA_TRY(tmp.alloc(n));
+      PassArgs a{};
+      a.n_obs = p->n_obs; a.n_cameras = L.n_cameras;
+      a.obs_point = p->obs_point; a.obs_image = p->obs_image; a.obs_camera = p->obs_camera;
+      a.cams = p->cams_dev[p->cur]; a.pose_slot = p->pose_slot;
+      CBA_TRY(launch_gf_touch(a, p->flags, p->cells, p->img_start, L.n_images, p->gf.f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
+                              d.n_act_tiles, d.act_words, 0, tmp, s));
+      CBA_TRY(tmp.download_sync(static_cast<u64*>(out), n, s));
+      break;
+    }
+    case CBA_GF_ACT:
+      CBA_TRY(need(sizeof(u64) * (size_t)d.n_act_tiles * d.act_words));
+      CBA_TRY(d.act.download(static_cast<u64*>(out), (size_t)d.n_act_tiles * d.act_words));
+      break;
+    case CBA_GF_KMASK:
+      CBA_TRY(need(sizeof(u64) * d.kmask.size()));
+      CBA_TRY(d.kmask.download(static_cast<u64*>(out), d.kmask.size()));
+      break;
+    case CBA_GF_ROWMASK:
+      CBA_TRY(need(sizeof(u64) * d.rowmask_dyn.size()));
+      CBA_TRY(d.rowmask_dyn.download(static_cast<u64*>(out), d.rowmask_dyn.size()));
+      break;
+    case CBA_GF_F: {
+      CBA_TRY(need(sizeof(double) * nf * nf));
+      CBA_TRY(p->gf.F.download(static_cast<double*>(out), nf * nf));
+      // behind the forming kernel the strip tiles that S0 serves are not in F yet: the block-sparse launch reads them in S0
+      if (stage == kGfStageForm && p->gf.S0 && d.s0_c1 > d.s0_c0) {
+        const size_t c0 = 64 * (size_t)(d.s0_c0 - g.nbg), c1 = 64 * (size_t)(d.s0_c1 - g.nbg);
+        CBA_HIP(hipMemcpy2D(static_cast<double*>(out) + g.Gf + c0, nf * sizeof(double), (const double*)p->gf.S0 + c0, wb * sizeof(double),
+                            (c1 - c0) * sizeof(double), (size_t)g.Gf, hipMemcpyDeviceToHost));
+      }
+      break;
+    }
+    case CBA_GF_BORDER:      // rows and columns Gf ... n_pad - 1 of F
+      CBA_TRY(need(sizeof(double) * wb * wb));
+      CBA_HIP(hipMemcpy2D(out, wb * sizeof(double), (const double*)p->gf.F + (size_t)g.Gf * nf + g.Gf, nf * sizeof(double), wb * sizeof(double), wb,
+                          hipMemcpyDeviceToHost));
+      break;
+    case CBA_GF_XF:
+      CBA_TRY(need(sizeof(double) * (size_t)g.n_fact));
+      CBA_TRY(p->gf.xF.download(static_cast<double*>(out), (size_t)g.n_fact));
+      break;
+    default: set_error("cba_debug_gridfirst: unknown item"); return CBA_ERR_ARG;
+  }
+  return rc;
+}
+
+namespace cba {
 
 // ---- block order of the imagesets (cba_set_observations): refinement of the Z-order `order` (order_imagesets) ----
 // Grid-first order: the pose columns of F are empty in the grid block rows the imageset does not reach (per-pass activity,

@@ -217,7 +217,9 @@ int alloc_gridfirst_system(cba_problem* p);
 int setup_gf_sharding(cba_problem* p);
 int gridfirst_pass_activity(cba_problem* p, const PassArgs& a, hipStream_t aux);
 int gridfirst_pass_end(cba_problem* p);
-int gridfirst_enqueue(cba_problem* p, double lambda);
+// the launches of one grid-first solve in their order (cba_debug_gridfirst's `stage`)
+enum GfStage { kGfStageForm = 0, kGfStageGridRows = 1, kGfStageUpdate = 2, kGfStageBorder = 3, kGfStageBack = 4 };
+int gridfirst_enqueue(cba_problem* p, double lambda, int last_stage = kGfStageBack);
 void gridfirst_finish(cba_problem* p);
 void order_imagesets_gridfirst(cba_problem* p, int64_t n, const float* xy, const int32_t* image_index, const int32_t* camera_index,
                                std::vector<int>& order);

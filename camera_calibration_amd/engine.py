@@ -214,6 +214,7 @@ PROTOTYPES = {
     "cba_debug_accumulate": (_I, [_VP, _D]),
     "cba_debug_solve": (_I, [_VP, _F64]),
     "cba_debug_apply_update": (_I, [_VP, _D]),
+    "cba_debug_gridfirst": (_I, [_VP, _F64, _I32, _I32, _I32, _VP, C.c_size_t]),
     "cba_gridfirst_plan_query": (_I64, [_CAM, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I64]),
     "cba_debug_time_direction_image": (_I, [_VP, _I32, _I32, _I32, _D]),
     "cba_elimination_order": (_I32, [_VP, _I32P]),
@@ -228,6 +229,11 @@ EXPORTED_SYMBOLS = list(PROTOTYPES)
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
 DUMP_BLOCK_DIAG_H, DUMP_BLOCK_DIAG_B, DUMP_OFF_DIAG_H, DUMP_DENSE_H, DUMP_DENSE_B, DUMP_X = 5, 6, 7, 8, 9, 10
 DUMP_TEST_COST_VECTOR = 11
+DUMP_CELLS, DUMP_POSE_SLOT = 12, 13
+# items of cba_debug_gridfirst
+GF_TOUCHED, GF_ACT, GF_KMASK, GF_ROWMASK, GF_F, GF_XF, GF_DIMS, GF_FORM_TILES, GF_BORDER = range(9)
+GF_DIM_NAMES = ("act_words", "n_act_tiles", "kmask_words", "kmask_tiles", "mask_words", "nbf", "s0_c0", "s0_c1", "n_form_tiles", "nbg", "ntc",
+                "strips_in_place")
 
 _lib: Optional[C.CDLL] = None
 
@@ -500,10 +506,36 @@ class Engine:
             DUMP_BLOCK_DIAG_H: ((nb, bs, bs), np.float64), DUMP_BLOCK_DIAG_B: ((nb * bs,), np.float64),
             DUMP_OFF_DIAG_H: ((nb * bs, dd), np.float64), DUMP_DENSE_H: ((dd, dd), np.float64),
             DUMP_DENSE_B: ((dd,), np.float64), DUMP_X: ((p.total_dof,), np.float64),
+            DUMP_CELLS: ((n, 2), np.int32), DUMP_POSE_SLOT: ((p.n_images,), np.int32),
         }
         shape, dt = shapes[what]
         out = np.zeros(shape, dtype=dt)
         _check(self.L.cba_debug_dump(self._h, what, out.ctypes.data_as(C.c_void_p), out.nbytes), "cba_debug_dump")
+        return out
+
+    def gridfirst_dims(self) -> dict:
+        """cba_debug_gridfirst(CBA_GF_DIMS): the sizes of the grid-first system's masks and tile lists (GF_DIM_NAMES)."""
+        out = np.zeros(len(GF_DIM_NAMES), dtype=np.int32)
+        _check(self.L.cba_debug_gridfirst(self._h, 0.0, -1, 0, GF_DIMS, out.ctypes.data_as(C.c_void_p), out.nbytes), "cba_debug_gridfirst")
+        return {k: int(v) for k, v in zip(GF_DIM_NAMES, out)}
+
+    def debug_gridfirst(self, lam: float, stage: int, what: int, poison: bool = False) -> np.ndarray:
+        """cba_debug_gridfirst: after debug_accumulate(), the launches of a grid-first solve for `lam` up to and including `stage`
+        (0 forming kernel, 1 block-sparse launch of the grid rows, 2 border update, 3 border factorisation, 4 back substitution and
+        scatter; -1 none) on the problem's own buffers, then item `what` (GF_*).  poison: the grid x border tiles whose activity bit
+        is off hold quiet NaNs while the stages run."""
+        d = self.gridfirst_dims()
+        n_pad, nbg = 64 * d["ntc"], d["nbg"]
+        shapes = {
+            GF_TOUCHED: ((d["n_act_tiles"], d["act_words"]), np.uint64), GF_ACT: ((d["n_act_tiles"], d["act_words"]), np.uint64),
+            GF_KMASK: ((d["kmask_tiles"], d["kmask_words"]), np.uint64), GF_ROWMASK: ((d["nbf"], d["mask_words"]), np.uint64),
+            GF_F: ((n_pad, n_pad), np.float64), GF_XF: ((64 * d["nbf"],), np.float64), GF_DIMS: ((len(GF_DIM_NAMES),), np.int32),
+            GF_FORM_TILES: ((d["n_form_tiles"], 2), np.int32), GF_BORDER: ((n_pad - 64 * nbg, n_pad - 64 * nbg), np.float64),
+        }
+        shape, dt = shapes[what]
+        out = np.zeros(shape, dtype=dt)
+        _check(self.L.cba_debug_gridfirst(self._h, float(lam), int(stage), int(bool(poison)), int(what), out.ctypes.data_as(C.c_void_p), out.nbytes),
+               "cba_debug_gridfirst")
         return out
 
 

@@ -564,7 +564,9 @@ enum {
   CBA_DUMP_DENSE_H = 8,          /* dense_dof x dense_dof row-major, upper triangle, WITHOUT lambda */
   CBA_DUMP_DENSE_B = 9,
   CBA_DUMP_X = 10,               /* total_dof doubles: last update vector */
-  CBA_DUMP_TEST_COST_VECTOR = 11 /* n doubles: cost vector of the last cost-only pass */
+  CBA_DUMP_TEST_COST_VECTOR = 11,/* n doubles: cost vector of the last cost-only pass */
+  CBA_DUMP_CELLS = 12,           /* 2n int32: origin (cx, cy) of the 4 x 4 control patch under the projected pixel of the Jacobian pass */
+  CBA_DUMP_POSE_SLOT = 13        /* n_images int32: position of every imageset's 6 x 6 block in the engine's pose order */
 };
 int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes);
 /* Tuning knob of the base projection (AddReprojectionResidual's ProjectWithInitialEstimate, joint_optimization.cc:325-343).
@@ -603,6 +605,29 @@ int cba_debug_apply_update(cba_problem* p, const double* x);
  * error code.  (No reference counterpart: LV/lm_optimizer.h:1247-1369 has one elimination order.) */
 int64_t cba_gridfirst_plan_query(const cba_camera* cameras, int32_t n_cameras, int32_t n_images, int32_t n_points, int32_t strips,
                                  int32_t single_tile_tasks, int32_t what, void* out, int64_t capacity_bytes);
+
+/* Debug: the grid-first solve stage by stage, on the problem's own buffers (tests/test_gpu_gridfirst_stages.py).  After a
+ * cba_debug_accumulate: runs the launches of a solve for `lambda` up to and including `stage` -- 0 = the forming kernel, 1 = the
+ * block-sparse launch of the grid rows, 2 = the border update, 3 = the border factorisation, 4 = back substitution and scatter;
+ * -1 = none -- waits for them and copies item `what` to out.  poison != 0: before stage 0 every 64-row x 128-column grid x border tile
+ * of F (and of the strips accumulated in F's layout) whose activity bit of this pass is off is filled with quiet NaNs, nothing else;
+ * behind the stages those tiles are cleared to zero, so the problem stays usable (a following cba_debug_solve forms F as usual).
+ * A zero pivot / NaN status is CBA_ERR_NUMERIC (the item is copied all the same).  CBA_ERR_UNSUPPORTED unless the problem uses the
+ * grid-first order in one process.  (No reference counterpart.) */
+enum {
+  CBA_GF_TOUCHED = 0,     /* uint64 x tiles x words: activity words BEFORE the closure (the touch kernel run again into a scratch buffer) */
+  CBA_GF_ACT = 1,         /* uint64 x tiles x words: activity words after the closure; bit r of 128-column border tile t = block row r */
+  CBA_GF_KMASK = 2,       /* uint64 x (n_pad / 128) x K words: 16-row K slabs of the border update per absolute 128-column tile */
+  CBA_GF_ROWMASK = 3,     /* uint64 x nbf x mask words: row masks of the back substitution */
+  CBA_GF_F = 4,           /* double x n_pad x n_pad: F, row-major, upper; with stage 0 the grid x (point | pose) block columns that the
+                             block-sparse launch reads from the strips are taken from there */
+  CBA_GF_XF = 5,          /* double x n_fact: the solution in the order of F */
+  CBA_GF_DIMS = 6,        /* int32 x 12: activity words, border tiles, K words, n_pad / 128, mask words, nbf, first / end block column served
+                             by the strips, tiles of the forming kernel, nbg, ntc, strips allocated */
+  CBA_GF_FORM_TILES = 7,  /* int32 x 2 x tiles: (block row, block column) of the 64 x 64 tiles the forming kernel writes */
+  CBA_GF_BORDER = 8       /* double x (n_pad - Gf)^2: the border x border block of F */
+};
+int cba_debug_gridfirst(cba_problem* p, double lambda, int32_t stage, int32_t poison, int32_t what, void* out, size_t bytes);
 
 /* Measurement of k_direction_image alone (tools/bench_report.py): seconds per launch over `launches` launches between two events on
  * device buffers, no copies.  use_stage = 0 sends every tile down the gather path (the control points read through L1 / L2 instead

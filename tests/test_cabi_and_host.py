@@ -48,7 +48,7 @@ def test_loaded_prototypes_match_the_header():
     hdr = open(os.path.join(ROOT, "include", "cba.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     decls = re.findall(r"^((?:const\s+)?\w+\s*\*?)\s*\b(cba_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr, flags=re.M)
-    assert len(decls) == 51 and len({name for _, name, _ in decls}) == 51, [name for _, name, _ in decls]
+    assert len(decls) == 52 and len({name for _, name, _ in decls}) == 52, [name for _, name, _ in decls]
     L = eng.load()
     for ret, name, params in decls:
         fn = getattr(L, name)

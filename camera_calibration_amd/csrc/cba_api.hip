@@ -245,7 +245,7 @@ int cba_cost(cba_problem* p, double* cost, int64_t* n_valid, double* cost_vector
 }
 
 int cba_set_fd_schedule(cba_problem* p, int32_t schedule) {
-  if (!p || schedule < -1 || schedule > 1) { set_error("cba_set_fd_schedule: bad argument"); return CBA_ERR_ARG; }
+  if (!p || schedule < -1 || schedule > 2) { set_error("cba_set_fd_schedule: bad argument"); return CBA_ERR_ARG; }
   p->fd_schedule = schedule;
   return CBA_OK;
 }

@@ -150,7 +150,8 @@ int launch_unproject(const CamDev* cam_dev, int model, int64_t n, const double* 
 // ---- kernels_fd.hip (finite-difference tasks of the Jacobian pass) ----
 // redo / redo_count: device work list (redo_cap entries / one int) for the tasks that leave their staged patch; tasks that find
 // the list full are counted in *redo_overflow
-// schedule: 0 = pooled (workgroup task pool, one LM attempt per trip), 1 = one task per lane; same expressions in the same order,
+// schedule: 0 = pooled (workgroup task pool, one LM attempt per trip), 1 = one task per lane, lanes ordered by predicted iteration count,
+// 2 = one task per lane in (observation, task) order (the same kernel as 1, bit-identical); same expressions in the same order,
 // flags identical, Jacobian entries agree to ~1e-12 (0.004 % of them differ: the compiler contracts one multiply-add of the damped
 // 2 x 2 solve differently in the two kernels; include/cba.h: cba_set_fd_schedule, tests/test_gpu_stragglers.py)
 int launch_fd_tasks(const PassArgs& a, int model_mask, int tasks_per_obs, int localize_only, const double* pixels,

@@ -40,10 +40,12 @@ int timers_collect(cba_problem* p) {
 }
 
 // -1 (default): pooled wherever the projections of one wavefront differ in length -- the non-central model (83 tasks per observation) and
-// rigs: 9 - 11 % faster in the bench trajectories of BASELINE configs[3] / [2] -- and one task per lane for a single central-generic
-// camera, where after the first iteration every task of an observation takes the same two outer iterations and the pool's bookkeeping
-// costs 4 % (configs[1]; in the FIRST iteration from the perturbed state the pool wins there too, 1.46 -> 1.29 ms).
-// profiles/r05_fd_schedules.txt, r05_fd_schedules_bench.txt
+// rigs: 9 - 11 % faster in the bench trajectories of BASELINE configs[3] / [2] -- and one task per lane, the lanes ordered by the
+// predicted iteration count of their tasks (kernels_fd.hip: k_fd_tasks), for a single central-generic camera: the tasks of an
+// observation take one or two outer iterations depending on their control point's weight, which is known before the loop starts,
+// and the pool's bookkeeping inside the loop costs more than it balances (configs[1]: pooled 4 % slower than the unordered lanes,
+// which the ordered ones beat by 0.37 ms of 1.72).  profiles/r05_fd_schedules.txt, r05_fd_schedules_bench.txt, fd_lane_order.json
+// (the ordered lanes also beat the pool at the two-camera rig now: 29.5 against 30.7 ms per step; that default has not been switched)
 static int fd_schedule_of(const cba_problem* p) {
   if (p->fd_schedule >= 0) return p->fd_schedule;
   return (p->L.n_cameras == 1 && p->model_mask == 1) ? 1 : 0;

@@ -117,7 +117,7 @@ struct cba_problem {
   DevBuf<uint8_t> slow_skip, fd_slow; DevBuf<int> slow_list, slow_count;
   int slow_cap = kSlowCapMin;
   int straggler_threshold = 8;    // outer projection iterations before an observation goes to the straggler kernel
-  int fd_schedule = -1;           // finite-difference kernel: -1 = automatic (default), 0 = pooled tasks, 1 = one task per lane (cba_set_fd_schedule)
+  int fd_schedule = -1;           // finite-difference kernel: -1 = automatic (default), 0 = pooled tasks, 1 = one task per lane, lanes sorted by predicted length, 2 = one task per lane, consecutive (cba_set_fd_schedule)
   DevBuf<int64_t> img_start;             // first observation of every imageset (+ end), for the strip accumulation
   DevBuf<unsigned long long> band_mask;      // per observation: column bands of B it touches
   // the side stream is the factorisation's far stream (idle during the Jacobian pass): the process must stay

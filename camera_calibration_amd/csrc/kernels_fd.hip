@@ -3,7 +3,10 @@
 //  k_fd_tasks        the 3 + K finite-difference re-projections, one task per lane   (joint_optimization.cc:357-372,
 //                                                                                      central_grid.h:187-245,
 //                                                                                      noncentral_generic.h:224-283)
-//  k_fd_pool         the same tasks taken from a workgroup pool, one LM attempt per trip (the default schedule)
+//                    a workgroup owns a group of 64 / 32 observations and orders the lanes of its wavefronts by the
+//                    predicted iteration count of their tasks (schedule 1, the default of one central-generic camera) or
+//                    leaves them in (observation, task) order (schedule 2)
+//  k_fd_pool         the same tasks taken from a workgroup pool, one LM attempt per trip (schedule 0: non-central cameras, rigs)
 //  k_fd_tasks_gather localize_only: three tasks per observation on the gather path
 //  k_fd_redo         the tasks whose iterates left their staged patch, on the gather path
 //
@@ -21,11 +24,12 @@ namespace cba {
 // ------------------------------------------------------------------------------------------------
 // The task lanes of an observation (35 central / 83 non-central) evaluate the B-spline on ONE 4x4 control patch, a few
 // times each (about two LM iterations of one UnprojectWithJacobian + one Unproject).  The workgroup stages the patches of
-// the observations it covers (at most 256 / tasks + 2) in LDS once; every evaluation then reads its 16 control points
-// with ds_read instead of 48 / 96 gathers through L1, and the kernel is built for 4 (central) / 3 (non-central)
+// the observations it covers in LDS once; every evaluation then reads its 16 control points
+// with ds_read instead of 48 / 96 gathers through L1, and the kernel is built for 3 (central) / 2 (non-central)
 // wavefronts per SIMD instead of 2 / 1 (the gathers of the whole patch in flight cost ~100 / ~190 VGPRs).  A lane whose
 // pixel crosses into a neighbouring cell repeats its projection on the gather path after the staged attempt.
-constexpr int kFdMaxObsPerBlock = 10;
+// Fewer tasks per observation than this (localize_only: 3) and the observations of a workgroup share nothing worth staging.
+constexpr int kFdMinStagedTasks = 29;
 // Row stride of a staged control patch in LDS: 16 control points + 2 doubles of padding.  Without the padding a row is 96 (central) /
 // 192 (non-central) dwords, i.e. every observation's patch starts on the same bank, and the compiler reads a control point with
 // ds_read2_b64 / ds_read_b128 (bank modulus 32 / 64 dwords, lane groups of 16): whenever the lanes of a group belong to different
@@ -124,86 +128,166 @@ __device__ __forceinline__ bool fd_task(const PassArgs& a, const CamDev& c, int 
   return true;
 }
 
-// The task lanes of an observation (35 central / 83 non-central) evaluate the B-spline on ONE 4x4 control patch, a few
-// times each (about two LM iterations of one UnprojectWithJacobian + one Unproject).  The workgroup stages the patches of
-// the observations it covers (at most 256 / tasks + 2) in LDS once; every evaluation then reads its 16 control points
-// with ds_read instead of 48 / 96 gathers through L1, which also takes the ~100 / ~190 VGPRs of a whole patch in flight
-// out of the kernel.  A lane whose pixel crosses into a neighbouring cell appends its task to `redo` and the follow-up
-// launch k_fd_redo repeats it on the gather path (the same arithmetic on the same control points).
+// One task per lane.  A workgroup owns a GROUP of G consecutive observation slots: it stages their control patches in LDS once
+// (every evaluation then reads its 16 control points with ds_read instead of 48 / 96 gathers through L1, which also takes the
+// ~100 / ~190 VGPRs of a whole patch in flight out of the kernel), builds the list of the group's live (slot, task) pairs in
+// LDS, and its wavefronts take chunks of 64 consecutive list entries until the list is used up.  A lane whose pixel crosses
+// into a neighbouring cell appends its task to `redo` and the follow-up launch k_fd_redo repeats it on the gather path (the
+// same arithmetic on the same control points).
+//
+// The ORDER of the list decides which tasks share a wavefront, and a wavefront runs as long as its slowest lane.  How long a
+// task runs is known before it starts: project_target returns after its first accepted step iff the cost before that step was
+// below 1e-12, and for a grid task of the central model that cost is (w * fd_delta)^2 with w = wx[q] * wy[r] the B-spline
+// weight of the perturbed control point at the base pixel -- one outer iteration for the corner control points of the patch
+// (w ~ 1e-3), two for the centre ones, and two or more for the three point tasks.  `order` (a kernel argument: both orders are
+// the same machine code):
+//   0  (slot, task) ascending: 64 consecutive tasks per wavefront, 35 of them one observation's
+//   1  three classes one after the other -- point tasks, grid tasks predicted heavy, grid tasks predicted light -- and (slot,
+//      task) ascending inside a class, so that the lanes of a wavefront still store into few records
+// The predictor is a scheduling hint: any permutation of the list computes the same results.  The non-central model has no
+// predictor (its origin and depth-scaled direction parameters need their own rule): all its grid tasks are one class.
+#ifndef CBA_FD_GROUP_CENTRAL
+#define CBA_FD_GROUP_CENTRAL 64         // observations per workgroup (at most 64: one lane of a wavefront classifies one slot)
+#endif
+#ifndef CBA_FD_GROUP_NONCENTRAL
+#define CBA_FD_GROUP_NONCENTRAL 32      // 48-double patches, 83 tasks per observation
+#endif
+template <int MODEL> struct FdGroup { static constexpr int kObs = (MODEL == kCentral) ? CBA_FD_GROUP_CENTRAL : CBA_FD_GROUP_NONCENTRAL; };
+// A grid task is predicted heavy (two or more outer iterations) when w * fd_delta >= kFdHeavyMargin * sqrt(1e-12): slightly
+// below 1, so that a doubtful task counts as heavy (a light task among heavy ones costs nothing, a heavy one among light ones
+// costs its wavefront an iteration).
+constexpr double kFdHeavyMargin = 0.95;
+constexpr int kFdListGroup = 8;         // observations per workgroup of a list launch (8 x 35 tasks: four to five chunks)
 template <int MODEL>
 __global__ void __launch_bounds__(256, MODEL == kCentral ? CBA_FD_WAVES_CENTRAL : CBA_FD_WAVES_NONCENTRAL)
-k_fd_tasks(PassArgs a, int tasks_per_obs, int localize_only, const double* __restrict__ pixels, const uint8_t* __restrict__ flags,
+k_fd_tasks(PassArgs a, int tasks_per_obs, int localize_only, int order, int group, const double* __restrict__ pixels, const uint8_t* __restrict__ flags,
            double* __restrict__ fd_out, uint8_t* __restrict__ fd_ok, int64_t* __restrict__ redo, int* __restrict__ redo_count, int redo_cap,
            int* __restrict__ redo_overflow) {
   constexpr int PER = (MODEL == kCentral) ? 2 : 5;
   constexpr int DIM = (MODEL == kCentral) ? 3 : 6;
-  __shared__ double sPatch[kFdMaxObsPerBlock][FdPatchRow<DIM>::kStride];
+  constexpr int G = FdGroup<MODEL>::kObs;
+  constexpr int kTasks = 3 + PER * 16;
+  static_assert(G <= 64 && kTasks <= 128, "a list entry is (slot << 7 | task) in 16 bits, and one lane classifies one slot");
+  __shared__ double sPatch[G][FdPatchRow<DIM>::kStride];
   __shared__ double sSub[256][DIM];             // per lane: its substituted control point
-  __shared__ int sOrigin[kFdMaxObsPerBlock][2];
-  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x;
-  const int64_t slot_first = t0 / tasks_per_obs;              // first observation slot of this workgroup
-  // ---- stage the patches ----
-  {
-    const int64_t slot_last = (t0 + blockDim.x - 1) / tasks_per_obs;
-    const int n_slots = (int)(slot_last - slot_first) + 1;    // <= 256 / 35 + 2 = 9 <= kFdMaxObsPerBlock
-    const int64_t limit = a.obs_list ? (int64_t)min(*a.obs_count, a.obs_list_cap) : a.n_obs;
-    for (int e = threadIdx.x; e < n_slots * 16; e += blockDim.x) {
-      const int j = e >> 4, pt = e & 15;
-      const int64_t slot = slot_first + j;
-      bool live = slot < limit;
-      int64_t o = 0;
-      if (live) { o = a.obs_list ? (int64_t)a.obs_list[slot] : slot; live = (flags[o] & 1) != 0; }
-      int fx = -(1 << 20), fy = -(1 << 20);
-      if (live) {
-        const CamDev c = a.cams[a.obs_camera[o]];
-        if (c.model_type == MODEL) {
-          double gx, gy;
-          pixel_to_grid(c, pixels[2 * o], pixels[2 * o + 1], gx, gy);
-          fx = (int)floor(gx + 2) - 3; fy = (int)floor(gy + 2) - 3;      // as unproject_jac places its patch
-          const int cx = fx + (pt & 3), cy = fy + (pt >> 2);
-          if (cx >= 0 && cy >= 0 && cx < c.gw && cy < c.gh) {
-            const double* g = c.grid + 3 * ((size_t)cx + (size_t)cy * c.gw);
-            sPatch[j][pt * DIM + 0] = g[0]; sPatch[j][pt * DIM + 1] = g[1]; sPatch[j][pt * DIM + 2] = g[2];
-            if (MODEL == kNoncentral) {
-              const double* p = g + 3 * (size_t)c.gw * c.gh;
-              sPatch[j][pt * DIM + 3] = p[0]; sPatch[j][pt * DIM + 4] = p[1]; sPatch[j][pt * DIM + 5] = p[2];
-            }
-          } else {
-            fx = -(1 << 20);                                             // never matches: such a patch is never evaluated
-          }
+  __shared__ int sOrigin[G][2];
+  __shared__ uint16_t sList[G * kTasks];        // the group's live tasks, slot << 7 | task
+  __shared__ int sNextChunk;
+  const int64_t slot_first = (int64_t)blockIdx.x * group;    // first observation slot of this workgroup; group <= G (launch_fd_tasks)
+  const int64_t limit = a.obs_list ? (int64_t)min(*a.obs_count, a.obs_list_cap) : a.n_obs;
+  if (slot_first >= limit) return;                            // (uniform) list launches are sized by the list's capacity
+  const int n_slots = (int)((limit - slot_first < group) ? limit - slot_first : group);
+  // ---- classify the slots ----
+  // Every wavefront looks at all slots of the group, lane = slot (one chain of dependent loads -- observation, camera, pixel -- a
+  // division and eight cubic weights: cheaper than handing the results from one wavefront to the others through LDS and a second
+  // barrier): where the slot's patch lies, whether its tasks go on the list, and which of its control points are heavy.
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n_cells = localize_only ? 0 : 16;
+  constexpr int kNoPatch = -(1 << 20);           // origin of a slot without a staged patch: never matches, such a patch is never evaluated
+  bool live = false;                             // the slot's tasks go on the list
+  unsigned heavy = 0xffffu;                      // bit (r * 4 + q): the grid tasks of control point (q, r) of the patch are predicted heavy
+  int fx = kNoPatch, fy = kNoPatch, gw = 0, plane = 0;
+  const double* grid = nullptr;
+  if (lane < n_slots) {
+    const int64_t o = a.obs_list ? (int64_t)a.obs_list[slot_first + lane] : slot_first + lane;
+    if (flags[o] & 1) {
+      const CamDev c = a.cams[a.obs_camera[o]];
+      if (c.model_type == MODEL) {
+        live = !(!a.obs_list && a.skip && a.skip[o]);
+        double gx, gy;
+        pixel_to_grid(c, pixels[2 * o], pixels[2 * o + 1], gx, gy);
+        gx += 2; gy += 2;
+        const int ix = (int)floor(gx), iy = (int)floor(gy);      // the patch placed as fd_task_setup / unproject_jac place it
+        if (ix >= 3 && iy >= 3 && ix < c.gw && iy < c.gh) {      // (always, for a base pixel inside the calibrated area)
+          fx = ix - 3; fy = iy - 3; gw = c.gw; plane = 3 * c.gw * c.gh; grid = c.grid;
+        }
+        if (MODEL == kCentral) {
+          double wx[4], wy[4];
+          weights_value(gx - (ix - 3), wx);
+          weights_value(gy - (iy - 3), wy);
+          const double bound = kFdHeavyMargin * 1e-6;
+          heavy = 0;
+#pragma unroll
+          for (int b = 0; b < 16; ++b) heavy |= (wx[b & 3] * wy[b >> 2] * a.fd_delta >= bound) ? (1u << b) : 0u;
         }
       }
-      if (pt == 0) { sOrigin[j][0] = fx; sOrigin[j][1] = fy; }
     }
-    __syncthreads();
   }
-  int64_t t = t0 + threadIdx.x;
-  int64_t o = t / tasks_per_obs;
-  int k = (int)(t - o * tasks_per_obs);
-  const int j = (int)(o - slot_first);
-  if (a.obs_list) {
-    const int cnt = min(*a.obs_count, a.obs_list_cap);
-    if (o >= cnt) return;
-    o = a.obs_list[o];
-    t = o * tasks_per_obs + k;          // results are indexed by (observation, task)
-  } else {
-    if (o >= a.n_obs) return;
-    if (a.skip && a.skip[o]) return;
+  // ---- stage the patches: a wavefront takes G / 4 slots, four at a time (16 lanes = the 16 control points of a patch) ----
+  // The slot's origin and grid come from its lane by shuffles and the loads are unconditional (a slot without a patch reads the
+  // camera table), so that the loads of all trips are in flight together.
+  if (wave == 0 && lane < n_slots) { sOrigin[lane][0] = fx; sOrigin[lane][1] = fy; }
+  static_assert(G % 16 == 0, "four wavefronts stage four slots per trip");
+#pragma unroll
+  for (int trip = 0; trip < G / 16; ++trip) {
+    const int j = wave * (G / 4) + trip * 4 + (lane >> 4), pt = lane & 15;
+    const int jfx = __shfl(fx, j), jfy = __shfl(fy, j), jgw = __shfl(gw, j), jplane = __shfl(plane, j);
+    const double* jgrid = (const double*)__shfl((long long)grid, j);
+    const bool staged = jfx != kNoPatch;
+    const double* g = staged ? jgrid + 3 * ((size_t)(jfx + (pt & 3)) + (size_t)(jfy + (pt >> 2)) * jgw) : (const double*)a.cams;
+    const double g0 = g[0], g1 = g[1], g2 = g[2];
+    double p0 = 0, p1 = 0, p2 = 0;
+    if (MODEL == kNoncentral) { const double* q = g + (staged ? jplane : 0); p0 = q[0]; p1 = q[1]; p2 = q[2]; }
+    if (staged) {
+      sPatch[j][pt * DIM + 0] = g0; sPatch[j][pt * DIM + 1] = g1; sPatch[j][pt * DIM + 2] = g2;
+      if (MODEL == kNoncentral) { sPatch[j][pt * DIM + 3] = p0; sPatch[j][pt * DIM + 4] = p1; sPatch[j][pt * DIM + 5] = p2; }
+    }
   }
-  if (!(flags[o] & 1)) return;
-  int cam = a.obs_camera[o];
-  const CamDev c = a.cams[cam];
-  if (c.model_type != MODEL) return;
-  const int n_tasks = 3 + (localize_only ? 0 : PER * 16);
-  if (k >= n_tasks) return;
-  StagedPatch<MODEL> st;
-  st.p = (lds_cdouble_ptr)&sPatch[j][0];
-  st.sub = (lds_cdouble_ptr)&sSub[threadIdx.x][0];
-  st.fx = sOrigin[j][0]; st.fy = sOrigin[j][1];
-  if (!fd_task<MODEL, true>(a, c, cam, o, k, t, pixels, fd_out, fd_ok, &st, &sSub[threadIdx.x][0])) {
-    const int slot = atomicAdd(redo_count, 1);
-    if (slot < redo_cap) redo[slot] = t;
-    else { fd_ok[t] = 0; atomicAdd(redo_overflow, 1); }     // list full: dropped Jacobian, as a failed projection, and counted
+  // ---- the list of live tasks ----
+  // Ballots give every slot the number of live slots and of heavy control points in front of it, and each wavefront writes the
+  // entries of one patch row.
+  if (order == 0) heavy = 0xffffu;               // one class: with the point tasks in front of each slot's grid tasks below, today's order
+  const unsigned long long before = (1ull << lane) - 1;
+  const unsigned long long m_live = __ballot(live);
+  const int n_live = __popcll(m_live), live_before = __popcll(m_live & before);
+  int n_heavy = 0, heavy_before = 0;
+  for (int b = 0; b < 16; ++b) {
+    const unsigned long long m = __ballot(live && ((heavy >> b) & 1u));
+    n_heavy += __popcll(m); heavy_before += __popcll(m & before);
+  }
+  const int n_tasks = 3 + n_cells * PER;
+  const int n_list = n_live * n_tasks;
+  if (live) {
+    // order 1: [point tasks of all slots][heavy grid tasks][light grid tasks]; order 0: slot after slot
+    const int point_at = (order == 0) ? n_tasks * live_before : 3 * live_before;
+    const int heavy_at = (order == 0) ? point_at + 3 : 3 * n_live + PER * heavy_before;
+    const int light_at = 3 * n_live + PER * (n_heavy + 16 * live_before - heavy_before);
+    if (wave == 0)
+      for (int k = 0; k < 3; ++k) sList[point_at + k] = (uint16_t)(lane << 7 | k);
+    for (int b = 4 * wave; b < 4 * wave + 4 && b < n_cells; ++b) {
+      const unsigned below = (1u << b) - 1;
+      const bool h = (heavy >> b) & 1u;
+      const int at = h ? heavy_at + PER * __popc(heavy & below) : light_at + PER * __popc(~heavy & below);
+      for (int d = 0; d < PER; ++d) sList[at + d] = (uint16_t)(lane << 7 | (3 + b * PER + d));
+    }
+  }
+  if (threadIdx.x == 0) sNextChunk = 0;
+  __syncthreads();
+  // ---- the tasks: a wavefront draws the next chunk of 64 list entries from the workgroup's counter until the list is used up ----
+  // (the heavy classes stand in front, so the wavefronts end on the short chunks; handing out chunks w, w + 4, ... to wavefront w
+  // measured 0.11 ms slower at the headline workload, profiles/fd_lane_order.json)
+  for (;;) {
+    int chunk = 0;
+    if (lane == 0) chunk = atomicAdd(&sNextChunk, 1);
+    chunk = __shfl(chunk, 0);
+    if (chunk * 64 >= n_list) break;
+    const int idx = chunk * 64 + lane;
+    if (idx >= n_list) continue;                  // the last chunk may be a partial one
+    const unsigned e = sList[idx];
+    const int j = (int)(e >> 7), k = (int)(e & 127u);
+    const int64_t o = a.obs_list ? (int64_t)a.obs_list[slot_first + j] : slot_first + j;
+    const int64_t t = o * tasks_per_obs + k;          // results are indexed by (observation, task)
+    const int cam = a.obs_camera[o];
+    const CamDev c = a.cams[cam];
+    StagedPatch<MODEL> st;
+    st.p = (lds_cdouble_ptr)&sPatch[j][0];
+    st.sub = (lds_cdouble_ptr)&sSub[threadIdx.x][0];
+    st.fx = sOrigin[j][0]; st.fy = sOrigin[j][1];
+    if (!fd_task<MODEL, true>(a, c, cam, o, k, t, pixels, fd_out, fd_ok, &st, &sSub[threadIdx.x][0])) {
+      const int slot = atomicAdd(redo_count, 1);
+      if (slot < redo_cap) redo[slot] = t;
+      else { fd_ok[t] = 0; atomicAdd(redo_overflow, 1); }     // list full: dropped Jacobian, as a failed projection, and counted
+    }
   }
 }
 // ---- pooled schedule (round 5): lanes take tasks from a workgroup pool, one LM attempt per trip ----
@@ -411,7 +495,7 @@ int launch_fd_tasks(const PassArgs& a, int model_mask, int tasks_per_obs, int lo
   if (a.n_obs == 0) return CBA_OK;
   int64_t total = (a.obs_list ? (int64_t)a.obs_list_cap : a.n_obs) * tasks_per_obs;
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (256 / tasks_per_obs + 2 > kFdMaxObsPerBlock) {      // localize_only: 3 tasks per observation
+  if (tasks_per_obs < kFdMinStagedTasks) {      // localize_only: 3 tasks per observation
     if (model_mask & 1) hipLaunchKernelGGL(k_fd_tasks_gather<kCentral>, grid, block, 0, s, a, tasks_per_obs, 3, pixels, flags, fd_out, fd_ok);
     if (model_mask & 2) hipLaunchKernelGGL(k_fd_tasks_gather<kNoncentral>, grid, block, 0, s, a, tasks_per_obs, 3, pixels, flags, fd_out, fd_ok);
     CBA_HIP(hipGetLastError());
@@ -419,7 +503,7 @@ int launch_fd_tasks(const PassArgs& a, int model_mask, int tasks_per_obs, int lo
   }
   CBA_HIP(hipMemsetAsync(redo_count, 0, sizeof(int), s));
   if (schedule == 0) {
-    // pooled schedule (default): a workgroup takes `pool` consecutive tasks; the pool is capped by the patches a workgroup can stage
+    // pooled schedule: a workgroup takes `pool` consecutive tasks; the pool is capped by the patches a workgroup can stage
     auto launch_pool = [&](auto kernel, int max_obs) {
       int pool = kFdPoolFactor * 256;
       const int cap = (max_obs - 2) * tasks_per_obs;
@@ -430,11 +514,18 @@ int launch_fd_tasks(const PassArgs& a, int model_mask, int tasks_per_obs, int lo
     if (model_mask & 1) launch_pool(k_fd_pool<kCentral>, FdPool<kCentral>::kMaxObs);
     if (model_mask & 2) launch_pool(k_fd_pool<kNoncentral>, FdPool<kNoncentral>::kMaxObs);
   } else {
-    if (model_mask & 1)
-      hipLaunchKernelGGL(k_fd_tasks<kCentral>, grid, block, 0, s, a, tasks_per_obs, localize_only, pixels, flags, fd_out, fd_ok, redo, redo_count, redo_cap, redo_overflow);
-    if (model_mask & 2)
-      hipLaunchKernelGGL(k_fd_tasks<kNoncentral>, grid, block, 0, s, a, tasks_per_obs, localize_only, pixels, flags, fd_out, fd_ok, redo, redo_count, redo_cap,
-                         redo_overflow);
+    // one task per lane: a workgroup per group of observation slots; schedule 1 = lanes ordered by predicted iteration count, 2 = consecutive.
+    // A list launch (the stragglers of the base projection, on the side stream) holds a few observations whose launch the pass
+    // waits for: small groups, so that they spread over as many workgroups as the launch of 256 consecutive tasks gave them.
+    const int order = (schedule == 1) ? 1 : 0;
+    const int64_t slots = a.obs_list ? (int64_t)a.obs_list_cap : a.n_obs;
+    auto launch_groups = [&](auto kernel, int max_group) {
+      const int group = a.obs_list ? min(kFdListGroup, max_group) : max_group;
+      const dim3 ggrid((unsigned)((slots + group - 1) / group));
+      hipLaunchKernelGGL(kernel, ggrid, block, 0, s, a, tasks_per_obs, localize_only, order, group, pixels, flags, fd_out, fd_ok, redo, redo_count, redo_cap, redo_overflow);
+    };
+    if (model_mask & 1) launch_groups(k_fd_tasks<kCentral>, FdGroup<kCentral>::kObs);
+    if (model_mask & 2) launch_groups(k_fd_tasks<kNoncentral>, FdGroup<kNoncentral>::kObs);
   }
   // gather-path follow-up for the (rare) tasks that left their staged patch: fixed grid over the list capacity, the count
   // stays on the device (workgroups past it exit at once)

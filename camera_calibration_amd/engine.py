@@ -464,7 +464,8 @@ class Engine:
 
     # -- parity / debug ----------------------------------------------------------------------------
     def set_fd_schedule(self, schedule: int) -> None:
-        """cba_set_fd_schedule: -1 = automatic (default), 0 = pooled finite-difference tasks, 1 = one task per lane."""
+        """cba_set_fd_schedule: -1 = automatic (default), 0 = pooled finite-difference tasks, 1 = one task per lane with the lanes
+        ordered by predicted iteration count, 2 = one task per lane in consecutive order (bit-identical to 1; A/B runs and tests)."""
         _check(self.L.cba_set_fd_schedule(self._h, int(schedule)), "cba_set_fd_schedule")
 
     def set_straggler_threshold(self, outer_iterations: int) -> None:

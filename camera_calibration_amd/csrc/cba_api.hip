@@ -28,8 +28,8 @@ static GpermView gperm_view(const cba_problem* p) {
 // pass (guard: PassArgs::guard), both cost vectors reduced into red8
 static int enqueue_candidate_cost(cba_problem* p, int cand, const int* guard) {
   CBA_TRY(launch_apply_update(p->L, p->cams, p->st[p->cur], p->x, p->st[cand], p->pose_slot, gperm_view(p).v, p->stream));
-  CBA_TRY(residual_pass(p, cand, p->cost_test, guard));
-  return launch_reduce_costs(p->cost_ref, p->cost_test, nullptr, p->n_obs, p->red_partials, p->red8, p->stream);
+  CBA_TRY(residual_pass(p, cand, guard));
+  return launch_reduce_costs(p->out.cost_ref, p->out.cost_test, nullptr, p->obs.n, p->red_partials, p->red8, p->stream);
 }
 // cba_step: the cost is already zero (lm_optimizer.h:755-760) -- the step ends here with `lambda` unchanged
 static int finish_zero_cost_step(cba_problem* p, cba_report* report, double lambda) {
@@ -61,7 +61,7 @@ int32_t cba_elimination_order(const cba_problem* p, int32_t out[4]) {
 }
 int32_t cba_total_dof(const cba_problem* p) { return p ? p->L.total_dof : 0; }
 int32_t cba_dense_dof(const cba_problem* p) { return p ? p->L.dense_dof : 0; }
-int32_t cba_jacobian_record_doubles(const cba_problem* p) { return p ? p->rec_doubles : 0; }
+int32_t cba_jacobian_record_doubles(const cba_problem* p) { return p ? p->out.rec_doubles : 0; }
 
 int64_t cba_reduce_buffer_doubles(const cba_config* config) {
   if (!config || !config->cameras) return 0;
@@ -128,32 +128,32 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
   CBA_HIP(hipSetDevice(p->device));
   // no observations until the upload below is complete: after a failed re-upload cba_step returns CBA_ERR_STATE
   p->have_obs = false; p->have_system = false;
-  p->n_obs = n;
-  CBA_TRY(p->obs_xy.alloc(2 * (size_t)n)); CBA_TRY(p->obs_point.alloc((size_t)n));
-  CBA_TRY(p->obs_image.alloc((size_t)n)); CBA_TRY(p->obs_camera.alloc((size_t)n));
-  CBA_TRY(p->last_projection.alloc(2 * (size_t)n));
-  CBA_TRY(p->cost_ref.alloc((size_t)n)); CBA_TRY(p->cost_test.alloc((size_t)n));
-  CBA_TRY(p->pixels.alloc(2 * (size_t)n)); CBA_TRY(p->flags.alloc((size_t)n));
-  CBA_TRY(p->fd_out.alloc(2 * (size_t)n * p->tasks_per_obs)); CBA_TRY(p->fd_ok.alloc((size_t)n * p->tasks_per_obs));
+  p->obs.n = n;
+  CBA_TRY(p->obs.xy.alloc(2 * (size_t)n)); CBA_TRY(p->obs.point.alloc((size_t)n));
+  CBA_TRY(p->obs.image.alloc((size_t)n)); CBA_TRY(p->obs.camera.alloc((size_t)n));
+  CBA_TRY(p->obs.last_projection.alloc(2 * (size_t)n));
+  CBA_TRY(p->out.cost_ref.alloc((size_t)n)); CBA_TRY(p->out.cost_test.alloc((size_t)n));
+  CBA_TRY(p->out.pixels.alloc(2 * (size_t)n)); CBA_TRY(p->out.flags.alloc((size_t)n));
+  CBA_TRY(p->out.fd_out.alloc(2 * (size_t)n * p->out.tasks_per_obs)); CBA_TRY(p->out.fd_ok.alloc((size_t)n * p->out.tasks_per_obs));
   // (jrec is cleared: records of mixed-model problems have unused tails)
-  CBA_TRY(p->jrec.alloc_zero((size_t)n * p->rec_doubles)); CBA_TRY(p->cells.alloc(2 * (size_t)n));
+  CBA_TRY(p->out.jrec.alloc_zero((size_t)n * p->out.rec_doubles)); CBA_TRY(p->out.cells.alloc(2 * (size_t)n));
   {
     // gather-path follow-up lists of the finite-difference kernel: a quarter of all tasks (the share of tasks whose iterate
     // crosses a cell boundary is a few per cent) + 65 536
-    const size_t cap = (size_t)n * p->tasks_per_obs / 4 + 65536;
-    p->fd_redo_cap = (int)(cap > 0x7fffff00u ? 0x7fffff00u : cap);
-    for (int i = 0; i < 2; ++i) CBA_TRY(p->fd_redo[i].alloc((size_t)p->fd_redo_cap));
+    const size_t cap = (size_t)n * p->out.tasks_per_obs / 4 + 65536;
+    p->fd.redo_cap = (int)(cap > 0x7fffff00u ? 0x7fffff00u : cap);
+    for (int i = 0; i < 2; ++i) CBA_TRY(p->fd.redo[i].alloc((size_t)p->fd.redo_cap));
   }
-  CBA_TRY(p->cell_order.alloc((size_t)n));
-  CBA_TRY(p->band_mask.alloc((size_t)(n > 0 ? n : 1)));
+  CBA_TRY(p->cell.order.alloc((size_t)n));
+  CBA_TRY(p->cell.band_mask.alloc((size_t)(n > 0 ? n : 1)));
   {
     std::vector<int64_t> is((size_t)L.n_images + 1, 0);
     for (int64_t i = 0; i < n; ++i) is[image_index[i] + 1] += 1;
     for (int i = 0; i < L.n_images; ++i) is[i + 1] += is[i];
-    CBA_TRY(p->img_start.assign(is));
+    CBA_TRY(p->obs.img_start.assign(is));
   }
   // observations of each (camera, pattern point), for the per-point accumulation (static: the point of an observation is data)
-  p->pt_start.reset(); p->pt_obs.reset();
+  p->obs.pt_start.reset(); p->obs.pt_obs.reset();
   if (!L.eliminate_points && n > 0 && n < 0x7fffffff && (int64_t)L.n_cameras * L.n_points < 0x7fffffff) {
     const size_t nk = (size_t)L.n_cameras * L.n_points;
     std::vector<int> ks(nk + 1, 0), ko((size_t)n);
@@ -161,20 +161,20 @@ int cba_set_observations(cba_problem* p, int64_t n, const float* xy, const int32
     for (size_t k = 0; k < nk; ++k) ks[k + 1] += ks[k];
     std::vector<int> fill(ks.begin(), ks.end() - 1);
     for (int64_t i = 0; i < n; ++i) ko[(size_t)fill[(size_t)camera_index[i] * L.n_points + point_index[i]]++] = (int)i;
-    CBA_TRY(p->pt_start.assign(ks)); CBA_TRY(p->pt_obs.assign(ko));
+    CBA_TRY(p->obs.pt_start.assign(ks)); CBA_TRY(p->obs.pt_obs.assign(ko));
   }
-  p->slow_cap = (int)std::min<int64_t>(std::max<int64_t>(kSlowCapMin, n / 8), 1 << 24);
-  CBA_TRY(p->slow_list.alloc((size_t)p->slow_cap));
-  CBA_TRY(p->slow_skip.alloc_zero((size_t)(n > 0 ? n : 1)));
-  CBA_TRY(p->fd_slow.alloc_zero((size_t)(n > 0 ? n : 1)));
-  CBA_TRY(p->slow_count.zero());
-  CBA_TRY(p->obs_xy.upload(xy, 2 * (size_t)n));
-  CBA_TRY(p->obs_point.upload(point_index, (size_t)n));
-  CBA_TRY(p->obs_image.upload(image_index, (size_t)n));
-  CBA_TRY(p->obs_camera.upload(camera_index, (size_t)n));
-  if (last_projection) CBA_TRY(p->last_projection.upload(last_projection, 2 * (size_t)n));
-  else CBA_TRY(p->last_projection.zero());
-  CBA_TRY(p->flags.zero());
+  p->slow.cap = (int)std::min<int64_t>(std::max<int64_t>(kSlowCapMin, n / 8), 1 << 24);
+  CBA_TRY(p->slow.list.alloc((size_t)p->slow.cap));
+  CBA_TRY(p->slow.skip.alloc_zero((size_t)(n > 0 ? n : 1)));
+  CBA_TRY(p->slow.fd_slow.alloc_zero((size_t)(n > 0 ? n : 1)));
+  CBA_TRY(p->slow.count.zero());
+  CBA_TRY(p->obs.xy.upload(xy, 2 * (size_t)n));
+  CBA_TRY(p->obs.point.upload(point_index, (size_t)n));
+  CBA_TRY(p->obs.image.upload(image_index, (size_t)n));
+  CBA_TRY(p->obs.camera.upload(camera_index, (size_t)n));
+  if (last_projection) CBA_TRY(p->obs.last_projection.upload(last_projection, 2 * (size_t)n));
+  else CBA_TRY(p->obs.last_projection.zero());
+  CBA_TRY(p->out.flags.zero());
   // block order of the imagesets (eliminate_points = 0 only: the pose blocks are the Schur blocks)
   p->pose_slot.reset();
   p->pose_slot_host.clear();
@@ -226,32 +226,32 @@ int cba_get_last_projection(cba_problem* p, double* out) {
   if (!p || !out || !p->have_obs) { set_error("cba_get_last_projection: bad argument"); return CBA_ERR_ARG; }
   CBA_HIP(hipSetDevice(p->device));
   CBA_HIP(hipStreamSynchronize(p->stream));
-  return p->last_projection.download(out, p->last_projection.size());
+  return p->obs.last_projection.download(out, p->obs.last_projection.size());
 }
 
 int cba_cost(cba_problem* p, double* cost, int64_t* n_valid, double* cost_vector) {
   if (!p || !p->have_obs || !p->have_state) { set_error("cba_cost: observations/state missing"); return CBA_ERR_STATE; }
   CBA_HIP(hipSetDevice(p->device));
   // (the device-side camera descriptions hold pointers and constants only: uploaded once, by cba_create)
-  CBA_TRY(residual_pass(p, p->cur, p->cost_test));
-  CBA_TRY(launch_reduce_costs(nullptr, p->cost_test, nullptr, p->n_obs, p->red_partials, p->red8, p->stream));
+  CBA_TRY(residual_pass(p, p->cur));
+  CBA_TRY(launch_reduce_costs(nullptr, p->out.cost_test, nullptr, p->obs.n, p->red_partials, p->red8, p->stream));
   CBA_TRY(allreduce(p, p->red8, 8));
   double h[8];
   CBA_TRY(p->red8.download_sync(h, 8, p->stream));
   if (cost) *cost = h[1];
   if (n_valid) *n_valid = (int64_t)h[6];
-  if (cost_vector) CBA_TRY(p->cost_test.download(cost_vector, (size_t)p->n_obs));
+  if (cost_vector) CBA_TRY(p->out.cost_test.download(cost_vector, (size_t)p->obs.n));
   return CBA_OK;
 }
 
 int cba_set_fd_schedule(cba_problem* p, int32_t schedule) {
   if (!p || schedule < -1 || schedule > 2) { set_error("cba_set_fd_schedule: bad argument"); return CBA_ERR_ARG; }
-  p->fd_schedule = schedule;
+  p->fd.schedule = schedule;
   return CBA_OK;
 }
 int cba_set_straggler_threshold(cba_problem* p, int32_t outer_iterations) {
   if (!p || outer_iterations < 0) { set_error("cba_set_straggler_threshold: bad argument"); return CBA_ERR_ARG; }
-  p->straggler_threshold = outer_iterations > 100 ? 100 : outer_iterations;
+  p->slow.threshold = outer_iterations > 100 ? 100 : outer_iterations;
   return CBA_OK;
 }
 
@@ -260,7 +260,7 @@ int cba_debug_accumulate(cba_problem* p, double* cost) {
   CBA_HIP(hipSetDevice(p->device));
   // (the device-side camera descriptions hold pointers and constants only: uploaded once, by cba_create)
   CBA_TRY(jacobian_pass_and_accumulate(p, nullptr));
-  CBA_TRY(launch_reduce_costs(p->cost_ref, nullptr, p->flags, p->n_obs, p->red_partials, p->red8, p->stream));
+  CBA_TRY(launch_reduce_costs(p->out.cost_ref, nullptr, p->out.flags, p->obs.n, p->red_partials, p->red8, p->stream));
   double h[8];
   CBA_TRY(p->red8.download_sync(h, 8, p->stream));
   if (cost) *cost = h[0];
@@ -305,7 +305,7 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
   // (the device-side camera descriptions hold pointers and constants only: uploaded once, by cba_create)
   CBA_TRY(timer_begin(p, kTimerJacobianPass));
   CBA_TRY(jacobian_pass_and_accumulate(p, &report->t_accumulate));
-  CBA_TRY(launch_reduce_costs(p->cost_ref, nullptr, p->flags, p->n_obs, p->red_partials, p->red8, p->stream));
+  CBA_TRY(launch_reduce_costs(p->out.cost_ref, nullptr, p->out.flags, p->obs.n, p->red_partials, p->red8, p->stream));
   CBA_TRY(timer_end(p, kTimerJacobianPass, 0, 0, 1));
   // One GPU and a given lambda: nothing the host does before the first solve depends on the pass's scalars, so their read rides
   // on the solve's own wait (one host wait per LM attempt fewer: the device does not idle between the pass and the solve).  The
@@ -332,9 +332,9 @@ int cba_step(cba_problem* p, double init_lambda, int32_t max_lm_attempts, double
     lambda = init_lambda;
   } else {  // lm_optimizer.h:766-781
     if (p->gf_sharded) {       // the exchange of the pass has summed H_dd and gathered every pose block: the whole diagonal is here
-      CBA_TRY(launch_diag_sum(p->sh.gDblk, L.block_size, p->gf.plan.n_images, p->Hdd, p->n_pad, L.dense_dof, p->scal, p->stream));
+      CBA_TRY(launch_diag_sum(p->sh.gDblk, L.block_size, p->gf.plan.n_images, p->sys.Hdd, p->sys.n_pad, L.dense_dof, p->scal, p->stream));
     } else {
-      CBA_TRY(launch_diag_sum(p->Dblk, L.block_size, L.n_blocks, p->Hdd, p->n_pad, L.dense_dof, p->scal, p->stream));
+      CBA_TRY(launch_diag_sum(p->sys.Dblk, L.block_size, L.n_blocks, p->sys.Hdd, p->sys.n_pad, L.dense_dof, p->scal, p->stream));
       CBA_TRY(allreduce(p, p->scal, 1));
     }
     double sum;
@@ -447,7 +447,7 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
   CBA_HIP(hipSetDevice(p->device));
   CBA_HIP(hipStreamSynchronize(p->stream));
   const Layout& L = p->L;
-  const size_t n = (size_t)p->n_obs, bs = L.block_size, nb = L.n_blocks, dd = L.dense_dof, ld = p->n_pad;
+  const size_t n = (size_t)p->obs.n, bs = L.block_size, nb = L.n_blocks, dd = L.dense_dof, ld = p->sys.n_pad;
   auto copy = [&](const auto& buf, size_t count) -> int {      // the first `count` elements of a device buffer
     using T = typename std::decay_t<decltype(buf)>::value_type;
     if (bytes < count * sizeof(T)) { set_error("cba_debug_dump: buffer too small"); return CBA_ERR_ARG; }
@@ -492,21 +492,21 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
     return CBA_OK;
   };
   switch (what) {
-    case CBA_DUMP_COST_VECTOR: return copy(p->cost_ref, n);
-    case CBA_DUMP_TEST_COST_VECTOR: return copy(p->cost_test, n);
-    case CBA_DUMP_PIXELS: return copy(p->pixels, 2 * n);
-    case CBA_DUMP_FLAGS: return copy(p->flags, n);
-    case CBA_DUMP_JACOBIANS: return copy(p->jrec, n * p->rec_doubles);
-    case CBA_DUMP_BLOCK_DIAG_H: { int rc = copy(p->Dblk, nb * bs * bs); if (rc == CBA_OK) unpermute_rows(bs); return rc; }
-    case CBA_DUMP_BLOCK_DIAG_B: { int rc = copy(p->bblk, nb * bs); if (rc == CBA_OK) unpermute_rows(1); return rc; }
+    case CBA_DUMP_COST_VECTOR: return copy(p->out.cost_ref, n);
+    case CBA_DUMP_TEST_COST_VECTOR: return copy(p->out.cost_test, n);
+    case CBA_DUMP_PIXELS: return copy(p->out.pixels, 2 * n);
+    case CBA_DUMP_FLAGS: return copy(p->out.flags, n);
+    case CBA_DUMP_JACOBIANS: return copy(p->out.jrec, n * p->out.rec_doubles);
+    case CBA_DUMP_BLOCK_DIAG_H: { int rc = copy(p->sys.Dblk, nb * bs * bs); if (rc == CBA_OK) unpermute_rows(bs); return rc; }
+    case CBA_DUMP_BLOCK_DIAG_B: { int rc = copy(p->sys.bblk, nb * bs); if (rc == CBA_OK) unpermute_rows(1); return rc; }
     case CBA_DUMP_OFF_DIAG_H: {
-      int rc = copy2d(p->B, nb * bs, dd);
+      int rc = copy2d(p->sys.B, nb * bs, dd);
       if (rc == CBA_OK) rc = gather_strips(static_cast<double*>(out), nb * bs, (size_t)p->gf.plan.n_rp);
       if (rc == CBA_OK) { unpermute_rows(dd); unpermute_cols(nb * bs, 0); }
       return rc;
     }
     case CBA_DUMP_DENSE_H: {
-      int rc = copy2d(p->Hdd, dd, dd);
+      int rc = copy2d(p->sys.Hdd, dd, dd);
       if (rc != CBA_OK) return rc;
       if (p->gf.S0) {      // the point rows
         const size_t rig = (size_t)p->gf.plan.n_rp - 3 * (size_t)L.n_points;
@@ -524,14 +524,14 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
         }
       return CBA_OK;
     }
-    case CBA_DUMP_DENSE_B: { int rc = copy(p->bd, dd); if (rc == CBA_OK) unpermute_cols(1, 0); return rc; }
+    case CBA_DUMP_DENSE_B: { int rc = copy(p->sys.bd, dd); if (rc == CBA_OK) unpermute_cols(1, 0); return rc; }
     case CBA_DUMP_X: {
       CBA_TRY(copy(p->x, (size_t)L.total_dof));
       if (!p->pose_slot_host.empty()) unpermute_rows(1);   // the block part comes first in x (eliminate_points = 0)
       unpermute_cols(1, L.block_dof);
       return CBA_OK;
     }
-    case CBA_DUMP_CELLS: return copy(p->cells, 2 * n);
+    case CBA_DUMP_CELLS: return copy(p->out.cells, 2 * n);
     case CBA_DUMP_POSE_SLOT: {
       if (bytes < (size_t)L.n_images * sizeof(int32_t)) { set_error("cba_debug_dump: buffer too small"); return CBA_ERR_ARG; }
       int32_t* o = static_cast<int32_t*>(out);
@@ -543,18 +543,18 @@ int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes) {
 }
 
 int64_t cba_fd_redo_overflow(cba_problem* p) {
-  if (!p || !p->fd_redo_count) return -1;
+  if (!p || !p->fd.redo_count) return -1;
   int v = 0;
   if (hipSetDevice(p->device) != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess ||
-      p->fd_redo_count.download(&v, 1, 2) != CBA_OK) return -1;
+      p->fd.redo_count.download(&v, 1, 2) != CBA_OK) return -1;
   return v;
 }
 int cba_debug_fd_redo_counts(cba_problem* p, int64_t out[3]) {
-  if (!p || !out || !p->fd_redo_count) { set_error("cba_debug_fd_redo_counts: bad argument"); return CBA_ERR_ARG; }
+  if (!p || !out || !p->fd.redo_count) { set_error("cba_debug_fd_redo_counts: bad argument"); return CBA_ERR_ARG; }
   int v[3] = {0, 0, 0};
   CBA_HIP(hipSetDevice(p->device));
   CBA_HIP(hipStreamSynchronize(p->stream));
-  CBA_TRY(p->fd_redo_count.download(v, 3));
+  CBA_TRY(p->fd.redo_count.download(v, 3));
   for (int i = 0; i < 3; ++i) out[i] = v[i];
   return CBA_OK;
 }

@@ -14,12 +14,13 @@ int alloc_gridfirst_system(cba_problem* p) {
   const size_t nf = (size_t)g.n_pad, wb = (size_t)(g.n_pad - g.Gf);
   CBA_TRY(p->gf.F.alloc_zero(nf * nf));          // tiles outside the plan's structure stay zero for ever
   CBA_TRY(p->gf.Xb.alloc_zero((size_t)g.Gf * wb));
-  const int rig_dof = g.n_rp - 3 * p->L.n_points;
+  GfDevice& d = p->gf.dev;
+  d.n_pad = g.n_pad; d.n_fact = g.n_fact; d.Gf = g.Gf; d.G = g.G; d.n_rp = g.n_rp; d.n_border = g.n_border;
+  d.rig_dof = g.n_rp - 3 * p->L.n_points;
   if (!p->gf_sharded) {       // the strips accumulated in F's layout: every block column of the border without a rig column
     CBA_TRY(p->gf.S0.alloc_zero((size_t)g.Gf * wb));
-    GfDevice& d = p->gf.dev;
     d.s0 = p->gf.S0; d.s0_ld = (int)wb;
-    d.s0_c0 = g.nbg + (rig_dof + 63) / 64; d.s0_c1 = std::max(g.nbf, d.s0_c0);
+    d.s0_c0 = g.nbg + (d.rig_dof + 63) / 64; d.s0_c1 = std::max(g.nbf, d.s0_c0);
   }
   CBA_TRY(p->gf.xF.alloc(nf));
   CBA_TRY(p->gf.dev.tasks.assign(g.tasks));
@@ -45,13 +46,12 @@ int alloc_gridfirst_system(cba_problem* p) {
   }
   for (int r = g.nbg; r < g.ntc; ++r)
     for (int c = r; c < g.ntc; ++c) { tiles.push_back(r); tiles.push_back(c); }
-  p->gf.n_tiles = (int)(tiles.size() / 2);
-  CBA_TRY(p->gf.tiles.assign(tiles));
-  CBA_TRY(p->gf.grid_of_f.assign(g.grid_of_f));
-  CBA_TRY(p->gf.f_of_grid.assign(g.f_of_grid));
+  p->gf.dev.n_tiles = (int)(tiles.size() / 2);
+  CBA_TRY(p->gf.dev.tiles.assign(tiles));
+  CBA_TRY(p->gf.dev.grid_of_f.assign(g.grid_of_f));
+  CBA_TRY(p->gf.dev.f_of_grid.assign(g.f_of_grid));
   // activity of the row strips (per pass): bit sets over the grid block rows per 128-column border tile, and what is derived
   {
-    GfDevice& d = p->gf.dev;
     d.act_words = (g.nbg + 63) / 64;
     d.n_act_tiles = (g.n_pad - g.Gf) / 128;
     d.kmask_words = (g.Gf / 16 + 63) / 64;
@@ -108,19 +108,18 @@ static int gf_allgather(cba_problem* p) {
 //   3. closure and masks of the union (the single-process masks up to the order of the pose columns), their host copy.
 static int gf_exchange(cba_problem* p) {
   const Layout& L = p->L;
-  const GfPlan& g = p->gf.plan;
   GfDevice& d = p->gf.dev;
   hipStream_t s = p->stream;
-  const int ld = p->n_pad;
-  CBA_TRY(launch_gf_shared(p->sh.shared, p->sh.shared_col, p->Hdd, ld, p->bd, p->P, 0, s));
+  const int ld = p->sys.n_pad;
+  CBA_TRY(launch_gf_shared(p->sh.shared, p->sh.shared_col, p->sys.view(), p->P, 0, s));
   CBA_TRY(gf_sum(p, p->sh.shared.doubles));
-  CBA_TRY(launch_gf_shared(p->sh.shared, p->sh.shared_col, p->Hdd, ld, p->bd, p->P, 1, s));
+  CBA_TRY(launch_gf_shared(p->sh.shared, p->sh.shared_col, p->sys.view(), p->P, 1, s));
   const int nw = d.n_act_tiles * d.act_words, M = p->sh.max_local, nloc = L.n_images;
   const int64_t oD = 2 * (int64_t)nw, ob = oD + 36 * (int64_t)M, oB = ob + 6 * (int64_t)M;
   CBA_TRY(launch_gf_words_to_doubles(d.act, nw, p->sh.gsend, s));
-  CBA_TRY(p->sh.gsend.copy_from_async(p->Dblk, 36 * (size_t)nloc, oD, 0, s));
-  CBA_TRY(p->sh.gsend.copy_from_async(p->bblk, 6 * (size_t)nloc, ob, 0, s));
-  CBA_TRY(p->sh.gsend.copy_from_async(p->B, 6 * (size_t)nloc * ld, oB, 0, s));
+  CBA_TRY(p->sh.gsend.copy_from_async(p->sys.Dblk, 36 * (size_t)nloc, oD, 0, s));
+  CBA_TRY(p->sh.gsend.copy_from_async(p->sys.bblk, 6 * (size_t)nloc, ob, 0, s));
+  CBA_TRY(p->sh.gsend.copy_from_async(p->sys.B, 6 * (size_t)nloc * ld, oB, 0, s));
   CBA_TRY(gf_allgather(p));
   for (int r = 0; r < p->sh.world; ++r) {
     const size_t cnt = (size_t)p->sh.counts[r], off = (size_t)p->sh.offsets[r];
@@ -131,8 +130,7 @@ static int gf_exchange(cba_problem* p) {
     CBA_TRY(p->sh.gB.copy_from_async(p->sh.grecv, 6 * cnt * ld, 6 * off * ld, src + oB, s));
   }
   CBA_TRY(launch_gf_or_words(p->sh.grecv, p->sh.world, p->sh.gblk, nw, d.act, s));
-  CBA_TRY(launch_gf_close_masks(d.n_act_tiles, d.act_words, g.nbg, g.nbf, d.gridrow, d.act, d.kmask, d.kmask_words, g.Gf / 128, d.rowmask,
-                                d.rowmask_dyn, d.mask_words, s));
+  CBA_TRY(launch_gf_close_masks(d, s));
   CBA_TRY(d.kmask.download_async(p->gf.kmask_host, d.kmask.size(), s));
   return CBA_OK;
 }
@@ -159,7 +157,7 @@ int setup_gf_sharding(cba_problem* p) {
     set_error("cba_create: grid-first sharding: the imagesets of the ranks do not add up to n_images_global"); return CBA_ERR_ARG;
   }
   p->sh.img0 = p->sh.offsets[p->sh.rank];
-  const size_t Ng = (size_t)total, ld = (size_t)p->n_pad;
+  const size_t Ng = (size_t)total, ld = (size_t)p->sys.n_pad;
   CBA_TRY(p->sh.gDblk.alloc(36 * Ng));
   CBA_TRY(p->sh.gbblk.alloc(6 * Ng));
   CBA_TRY(p->sh.gB.alloc(6 * Ng * ld));
@@ -177,16 +175,11 @@ int setup_gf_sharding(cba_problem* p) {
 // observation sits under its projected pixel), closed under the fill of the grid factor, and the masks derived from it -- on
 // the side stream behind the per-cell accumulation, underneath the strips kernel of the main stream (waited for at the end of the pass)
 int gridfirst_pass_activity(cba_problem* p, const PassArgs& a, hipStream_t aux) {
-  const Layout& L = p->L;
-  const GfPlan& g = p->gf.plan;
   GfDevice& d = p->gf.dev;
   if (p->gf_sharded) {        // this rank's rows only (pose columns at their global tiles): the union and the masks follow the exchange
-    CBA_TRY(launch_gf_touch(a, p->flags, p->cells, p->img_start, L.n_images, p->gf.f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
-                            d.n_act_tiles, d.act_words, p->sh.img0, d.act, aux));
+    CBA_TRY(launch_gf_touch(a, p->obs, p->out, d, p->sh.img0, aux));
   } else {
-    CBA_TRY(launch_gf_activity(a, p->flags, p->cells, p->img_start, L.n_images, p->gf.f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
-                               d.n_act_tiles, d.act_words, g.nbg, g.nbf, d.gridrow, d.act, d.kmask, d.kmask_words, g.Gf / 128, d.rowmask, d.rowmask_dyn,
-                               d.mask_words, aux));
+    CBA_TRY(launch_gf_activity(a, p->obs, p->out, d, aux));
     CBA_TRY(d.kmask.download_async(p->gf.kmask_host, d.kmask.size(), aux));
   }
   return CBA_OK;
@@ -285,9 +278,9 @@ int gridfirst_enqueue(cba_problem* p, double lambda, int last_stage) {
   const GfDevice& d = p->gf.dev;
   // (image sharding: H_dd / b_d hold the sums over the ranks, the pose rows of all ranks are in gDblk / gbblk / gB -- gf_exchange)
   const bool sh = p->gf_sharded;
-  CBA_TRY(launch_gf_form(p->gf.F, ld, g.Gf, g.n_rp, g.n_border, p->gf.grid_of_f, p->Hdd, p->n_pad, p->bd, sh ? p->sh.gB : p->B, d.s0, d.s0_ld,
-                         g.n_rp - 3 * L.n_points, sh ? p->sh.gDblk : p->Dblk,
-                         sh ? p->sh.gbblk : p->bblk, lambda, p->gf.tiles, p->gf.n_tiles, d.act, d.act_words, p->stream));
+  SystemView from = p->sys.view();
+  if (sh) { from.t.Dblk = p->sh.gDblk; from.t.bblk = p->sh.gbblk; from.t.B = p->sh.gB; }
+  CBA_TRY(launch_gf_form(p->gf.F, d, from, lambda, p->stream));
   if (last_stage <= kGfStageForm) return CBA_OK;
   GemmStats gs;
   CBA_TRY(timer_begin(p, kTimerFactor));
@@ -299,12 +292,12 @@ int gridfirst_enqueue(cba_problem* p, double lambda, int last_stage) {
     }
     tile_list = p->gf.tile_list;
   }
-  CBA_TRY(ldlt_factor_gridfirst(p->gf.F, g.n_fact, ld, d, p->gf.Xb, ld - g.Gf, p->ldlt, p->stream, &gs, d.kmask, d.kmask_words, tile_list,
-                                tile_list ? p->gf.tile_list_entries : 0, std::min(last_stage, (int)kGfStageBorder) - kGfStageGridRows));
+  CBA_TRY(ldlt_factor_gridfirst(p->gf.F, d, p->gf.Xb, p->ldlt, p->stream, &gs, tile_list, tile_list ? p->gf.tile_list_entries : 0,
+                                std::min(last_stage, (int)kGfStageBorder) - kGfStageGridRows));
   CBA_TRY(timer_end(p, kTimerFactor, gs.flops, 0, gs.launches));
   if (last_stage < kGfStageBack) return CBA_OK;
   CBA_TRY(ldlt_back_solve(p->gf.F, g.n_fact, ld, ld - 1, p->ldlt, p->gf.xF, p->stream, d.rowmask_dyn, d.mask_words));
-  CBA_TRY(launch_gf_scatter(p->gf.xF, g.Gf, g.n_rp, L.block_dof, g.G, p->gf.f_of_grid, sh ? 6 * p->sh.img0 : 0, p->x, p->stream));
+  CBA_TRY(launch_gf_scatter(p->gf.xF, d, L.block_dof, sh ? 6 * p->sh.img0 : 0, p->x, p->stream));
   return CBA_OK;
 }
 
@@ -370,7 +363,7 @@ extern "C" int cba_debug_gridfirst(cba_problem* p, double lambda, int32_t stage,
   CBA_HIP(hipSetDevice(p->device));
   const Layout& L = p->L;
   const GfPlan& g = p->gf.plan;
-  const GfDevice& d = p->gf.dev;
+  GfDevice& d = p->gf.dev;
   hipStream_t s = p->stream;
   CBA_HIP(hipStreamSynchronize(s));
   int rc = CBA_OK;
@@ -400,14 +393,14 @@ extern "C" int cba_debug_gridfirst(cba_problem* p, double lambda, int32_t stage,
   switch (what) {
     case CBA_GF_DIMS: {
       const int32_t v[12] = {d.act_words, d.n_act_tiles, d.kmask_words, g.n_pad / 128, d.mask_words, g.nbf, d.s0_c0, d.s0_c1,
-                             p->gf.n_tiles, g.nbg, g.ntc, p->gf.S0 ? 1 : 0};
+                             p->gf.dev.n_tiles, g.nbg, g.ntc, p->gf.S0 ? 1 : 0};
       CBA_TRY(need(sizeof(v)));
       std::memcpy(out, v, sizeof(v));
       break;
     }
     case CBA_GF_FORM_TILES:
-      CBA_TRY(need(sizeof(int) * 2 * (size_t)p->gf.n_tiles));
-      CBA_TRY(p->gf.tiles.download(static_cast<int*>(out), 2 * (size_t)p->gf.n_tiles));
+      CBA_TRY(need(sizeof(int) * 2 * (size_t)p->gf.dev.n_tiles));
+      CBA_TRY(p->gf.dev.tiles.download(static_cast<int*>(out), 2 * (size_t)p->gf.dev.n_tiles));
       break;
     case CBA_GF_TOUCHED: {
       const size_t n = (size_t)d.n_act_tiles * d.act_words;
@@ -415,11 +408,10 @@ extern "C" int cba_debug_gridfirst(cba_problem* p, double lambda, int32_t stage,
       DevBuf<u64> tmp;
       CBA_TRY(tmp.alloc(n));
       PassArgs a{};
-      a.n_obs = p->n_obs; a.n_cameras = L.n_cameras;
-      a.obs_point = p->obs_point; a.obs_image = p->obs_image; a.obs_camera = p->obs_camera;
+      a.n_obs = p->obs.n; a.n_cameras = L.n_cameras;
+      a.obs_point = p->obs.point; a.obs_image = p->obs.image; a.obs_camera = p->obs.camera;
       a.cams = p->cams_dev[p->cur]; a.pose_slot = p->pose_slot;
-      CBA_TRY(launch_gf_touch(a, p->flags, p->cells, p->img_start, L.n_images, p->gf.f_of_grid, g.n_rp, L.rig_in_state ? 6 * L.n_cameras : 0,
-                              d.n_act_tiles, d.act_words, 0, tmp, s));
+      CBA_TRY(launch_gf_touch(a, p->obs, p->out, d, 0, s, &tmp));
       CBA_TRY(tmp.download_sync(static_cast<u64*>(out), n, s));
       break;
     }

@@ -107,6 +107,63 @@ struct PassArgs {
 };
 static_assert(std::is_trivially_copyable_v<PassArgs>);
 
+// ---- what the passes over the observations own (members of cba_problem; the launchers below take them by reference) ----
+// The observations, in block order of their imagesets: set by cba_set_observations, constant afterwards (last_projection: the warm starts)
+struct Observations {
+  int64_t n = 0;
+  DevBuf<float> xy; DevBuf<int> point, image, camera;
+  DevBuf<double> last_projection;
+  DevBuf<int64_t> img_start;      // first observation of every imageset (+ end), for the strip accumulation
+  DevBuf<int> pt_start, pt_obs;   // observations bucketed by (camera, pattern point): k_accumulate_points
+};
+// What a pass writes per observation
+struct PassOutputs {
+  DevBuf<double> cost_ref, cost_test, pixels; DevBuf<uint8_t> flags; DevBuf<int> cells;
+  DevBuf<double> jrec; int rec_doubles = 0;      // Jacobian records (layout above)
+  DevBuf<double> fd_out; DevBuf<uint8_t> fd_ok; int tasks_per_obs = 0;
+};
+// Straggler split (see PassArgs)
+constexpr int kSlowCapMin = 16384;
+struct StragglerSplit {
+  DevBuf<uint8_t> skip, fd_slow; DevBuf<int> list, count;
+  int cap = kSlowCapMin;          // capacity of the list: max(this, n_obs / 8), set with the observations
+  int threshold = 8;              // outer projection iterations before an observation goes to the straggler kernel
+};
+// Finite-difference kernel: work lists of the tasks that leave their staged patch, and the schedule
+enum FdList { kFdMainList = 0, kFdSideList = 1 };      // main launch / side-stream launch
+struct FdWork {
+  DevBuf<int64_t> redo[2]; int redo_cap = 0;
+  DevBuf<int> redo_count;         // [0] main list, [1] side-stream list, [2] tasks that found a list full
+  int schedule = -1;              // -1 = automatic (default), 0 = pooled tasks, 1 = one task per lane, lanes sorted by predicted length, 2 = one task per lane, consecutive (cba_set_fd_schedule)
+};
+// Counting sort of the observations by (camera, grid cell), and the per-observation tables of the accumulation kernels
+struct CellSort {
+  std::vector<int> base_host; DevBuf<int> base, count, start, fill, order;
+  DevBuf<unsigned long long> band_mask;      // per observation: column bands of B it touches
+  DevBuf<uint32_t> pair_tables; DevBuf<int> pair_counts;
+};
+// deterministic mode (cba_config.deterministic): fixed-point scale of the current pass
+struct DetMode { DevBuf<unsigned long long> bits; DevBuf<double> scale; };
+// Grid-first order, one process (DESIGN.md section 3a): the grid rows x (point | pose) columns of F are accumulated where the
+// factorisation reads them -- S0[f_of_grid[grid column - n_rp]][border column], leading dimension ld, cleared before the pass --
+// not as the grid columns of B's pose rows and of H_dd's point rows.  S0 = null: those rows (every other order and path).
+struct GfStrips {
+  double* S0; int ld; const int* f_of_grid; int n_rp;
+};
+struct AccumTargets {
+  double* Dblk; double* bblk; double* B; double* Hdd; double* bd;
+  GfStrips gf;
+};
+static_assert(std::is_trivially_copyable_v<AccumTargets>);
+// The normal equations as the kernels address them: the arrays and the row stride of B and H_dd
+struct SystemView { AccumTargets t; int ld; };
+// The accumulated normal equations (both elimination orders read them)
+struct NormalSystem {
+  int n_pad = 0, n_fact = 0, Kpad = 0;
+  DevBuf<double> Dblk, bblk, B, Hdd, bd;
+  SystemView view() const { return SystemView{AccumTargets{Dblk, bblk, B, Hdd, bd, GfStrips{}}, n_pad}; }
+};
+
 // ---- small host helpers ----
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double now_s() {
@@ -138,53 +195,39 @@ int make_main_stream(hipStream_t* s);
 // ---- kernels_project.hip (pose composition, base projection, stateless model-level kernels) ----
 int launch_compose_poses(const DevState& st, int N, int C, double* itg, hipStream_t s);
 int launch_tangents(const double* dir_grid, double* tang, int G, hipStream_t s);
-// base projection of every observation; lanes that exceed the iteration cap are appended to defer_list (and marked in
-// defer_skip) for launch_base_project_slow, which takes the list through PassArgs::obs_list / obs_count / obs_list_cap
-int launch_base_project(const PassArgs& a, int model_mask, double* cost_vec, double* pixels, uint8_t* flags, int* defer_list,
-                        DevBuf<int>& defer_count, int defer_cap, uint8_t* defer_skip, int outer_cap, const uint8_t* fd_slow, hipStream_t s);
-int launch_base_project_slow(const PassArgs& a, int model_mask, double* cost_vec, double* pixels, uint8_t* flags, hipStream_t s);
+// base projection of every observation into out.pixels / flags and the cost vector out.cost_test (test_cost) or out.cost_ref; lanes
+// that exceed slow.threshold iterations are appended to slow.list (and marked in slow.skip) for launch_base_project_slow, which takes
+// the list through PassArgs::obs_list / obs_count / obs_list_cap.  use_fd_slow (Jacobian pass): the observations marked in
+// slow.fd_slow go to the list as well
+int launch_base_project(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, StragglerSplit& slow, bool use_fd_slow,
+                        hipStream_t s);
+int launch_base_project_slow(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, hipStream_t s);
 int launch_project_points(const CamDev* cam_dev, int model, int64_t n, const double* local, const double* init,
                           double* pixels, uint8_t* ok, hipStream_t s);
 int launch_unproject(const CamDev* cam_dev, int model, int64_t n, const double* pixels, double* lines, double* jac,
                      uint8_t* ok, hipStream_t s);
 // ---- kernels_fd.hip (finite-difference tasks of the Jacobian pass) ----
-// redo / redo_count: device work list (redo_cap entries / one int) for the tasks that leave their staged patch; tasks that find
-// the list full are counted in *redo_overflow
-// schedule: 0 = pooled (workgroup task pool, one LM attempt per trip), 1 = one task per lane, lanes ordered by predicted iteration count,
+// fd.redo[list] / fd.redo_count[list]: device work list for the tasks that leave their staged patch; those that find it full are counted in fd.redo_count[2]
+// fd.schedule: -1 = chosen by the problem (kernels_fd.hip: fd_schedule_of), 0 = pooled (workgroup task pool, one LM attempt per trip), 1 = one task per lane, lanes ordered by predicted iteration count,
 // 2 = one task per lane in (observation, task) order (the same kernel as 1, bit-identical); same expressions in the same order,
 // flags identical, Jacobian entries agree to ~1e-12 (0.004 % of them differ: the compiler contracts one multiply-add of the damped
 // 2 x 2 solve differently in the two kernels; include/cba.h: cba_set_fd_schedule, tests/test_gpu_stragglers.py)
-int launch_fd_tasks(const PassArgs& a, int model_mask, int tasks_per_obs, int localize_only, const double* pixels,
-                    const uint8_t* flags, double* fd_out, uint8_t* fd_ok, int64_t* redo, int* redo_count, int redo_cap, int* redo_overflow,
-                    hipStream_t s, int schedule = 0);
+int launch_fd_tasks(const PassArgs& a, int model_mask, int localize_only, PassOutputs& out, FdWork& fd, FdList list, hipStream_t s);
 // ---- kernels_obs.hip (stage B: Jacobian records and their accumulation; the records are a.jrec, a.rec_doubles apart) ----
-int launch_assemble(const PassArgs& a, const Layout& L, const DevState& st, int tasks_per_obs, const double* pixels, uint8_t* flags,
-                    const double* fd_out, const uint8_t* fd_ok, int* cells, uint8_t* fd_slow, hipStream_t s);
-// Grid-first order, one process (DESIGN.md section 3a): the grid rows x (point | pose) columns of F are accumulated where the
-// factorisation reads them -- S0[f_of_grid[grid column - n_rp]][border column], leading dimension ld, cleared before the pass --
-// not as the grid columns of B's pose rows and of H_dd's point rows.  S0 = null: those rows (every other order and path).
-struct GfStrips {
-  double* S0; int ld; const int* f_of_grid; int n_rp;
-};
-struct AccumTargets {
-  double* Dblk; double* bblk; double* B; double* Hdd; double* bd;
-  GfStrips gf;
-};
-static_assert(std::is_trivially_copyable_v<AccumTargets>);
-int launch_accumulate(const PassArgs& a, const Layout& L, const uint8_t* flags, const int* cells, const uint32_t* pair_tables,
-                      const int* pair_counts, AccumTargets t, const double* det_scale, int points_separate, hipStream_t s);
-// terms with a pattern-point column, bucketed by (camera, point) (poses eliminated); key lists: cba_set_observations
-int launch_accumulate_points(const PassArgs& a, const Layout& L, const std::vector<cba_camera>& cams, const uint8_t* flags, const int* cells,
-                             const int* key_start, const int* key_obs, AccumTargets t, const double* det_scale, hipStream_t s);
+int launch_assemble(const PassArgs& a, const Layout& L, const DevState& st, PassOutputs& out, StragglerSplit& slow, hipStream_t s);
+// The accumulation launchers add into `sys`; det_scale: the pass' fixed-point scales (DetMode::scale) in the deterministic mode, else null
+int launch_accumulate(const PassArgs& a, const Layout& L, const PassOutputs& out, const CellSort& cell, const SystemView& sys,
+                      const double* det_scale, int points_separate, hipStream_t s);
+// terms with a pattern-point column, bucketed by (camera, point) (poses eliminated); key lists: obs.pt_start / pt_obs (cba_set_observations)
+int launch_accumulate_points(const PassArgs& a, const Layout& L, const std::vector<cba_camera>& cams, const Observations& obs,
+                             const PassOutputs& out, const SystemView& sys, const double* det_scale, hipStream_t s);
 // deterministic mode (cba_config.deterministic): fixed-point scale of a pass, conversion of an accumulated array
-int launch_det_scale(const PassArgs& a, const uint8_t* flags, DevBuf<unsigned long long>& bits, double* scale, hipStream_t s);
+int launch_det_scale(const PassArgs& a, const PassOutputs& out, DetMode& det, hipStream_t s);
 int launch_det_convert(double* p, size_t n, const double* det_scale, hipStream_t s);
-int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, const uint8_t* flags, const int* cells,
-                             unsigned long long* band_mask, const int64_t* img_start, double* B, int ld, const GfStrips& gf,
-                             const double* det_scale, hipStream_t s);
-int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const std::vector<int>& cell_base_host, int ld,
-                            const uint8_t* flags, const int* cells, const int* cell_base, DevBuf<int>& count, int* start, DevBuf<int>& fill, int* order,
-                            double* Hdd, int rig_row_first, const double* det_scale, double* bd, hipStream_t s);
+int launch_accumulate_strips(const PassArgs& a, const Layout& L, const Observations& obs, const PassOutputs& out, CellSort& cell,
+                             const SystemView& sys, const double* det_scale, hipStream_t s);
+int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const PassOutputs& out, CellSort& cell,
+                            const SystemView& sys, int rig_row_first, const double* det_scale, hipStream_t s);
 // exclusive scan of n counts into n + 1 starts (one workgroup; the counting sorts of kernels_obs.hip and kernels_fit.hip)
 int launch_exclusive_scan(const int* count, int n, int* start, hipStream_t s);
 // ---- kernels_update.hip (cost reductions, state update) ----
@@ -407,11 +450,16 @@ int ldlt_workspace_alloc(LdltWorkspace& w, int n, int flag_rows_blocks = 0);
 int ldlt_collect_spans(LdltWorkspace& w, GemmStats* st);
 // k_begin: rows above it are factored already and their update is applied (the border of the grid-first order)
 int ldlt_factor(double* S, int n, int ld, LdltWorkspace& w, hipStream_t s, GemmStats* trailing_stats, int k_begin = 0);
-// Grid-first elimination (gridfirst_plan.h): device copies of the plan's arrays
+// Grid-first elimination (gridfirst_plan.h): the plan's dimensions and device copies of its arrays
 struct GfDevice {
   DevBuf<GfTask> tasks; DevBuf<GfIval> ivals; DevBuf<GfChain> chains;
   int n_tasks0 = 0, n_tasks1 = 0, n_chains = 0;
   int nbg = 0, nbf = 0;
+  // F = [grid | border]: n_pad x n_pad, rows [0, n_fact) factored; Gf grid rows (G unknowns and padding), then the border = n_rp rig /
+  // point columns (rig_dof rig columns first) and the pose columns, n_border in all
+  int n_pad = 0, n_fact = 0, Gf = 0, G = 0, n_rp = 0, n_border = 0, rig_dof = 0;
+  DevBuf<int> grid_of_f, f_of_grid;          // row of F -> engine grid index (-1 = padding) and back
+  DevBuf<int> tiles; int n_tiles = 0;        // 64 x 64 tiles of F the forming kernel writes
   DevBuf<unsigned long long> rowmask; int mask_words = 0;      // static structure of every factored block row (the plan's)
   double flops_grid = 0;
   // per Jacobian pass (launch_gf_activity): activity of the grid x border tiles and what is derived from it
@@ -424,14 +472,13 @@ struct GfDevice {
   // s0[row of F][column of F - 64 nbg], leading dimension s0_ld
   const double* s0 = nullptr; int s0_ld = 0, s0_c0 = 0, s0_c1 = 0;
 };
-// F = [grid | border] in the plan's order, ld = its n_pad; Xb: (rows of the grid part) x (ld - Gf) panel buffer (zero outside the
-// tiles the launch writes); kmask: optional block-sparsity of the border update (null = dense); tile_list: optional order of its
+// F = [grid | border] in the plan's order, g.n_pad x g.n_pad; Xb: g.Gf x (g.n_pad - g.Gf) panel buffer (zero outside the
+// tiles the launch writes); the border update is block-sparse by g.kmask; tile_list: optional order of its
 // upper tiles, tile_list_entries entries (tm, tn, s0, s1) relative to the border -- every upper tile once (s1 = 0) or as parts whose K-slab
 // ranges [s0, s1) cover all slabs (added atomically), tm = -1 = an empty slot.  last_part: 0 = the block-sparse launch of the grid rows
 // only, 1 = and the border update, 2 = and the border factorisation (the whole factorisation; the others: cba_debug_gridfirst)
-int ldlt_factor_gridfirst(double* F, int n_fact, int ld, const GfDevice& g, double* Xb, int ldxb, LdltWorkspace& w, hipStream_t s,
-                          GemmStats* st, const unsigned long long* kmask, int kmask_words, const int* tile_list, int tile_list_entries,
-                          int last_part = 2);
+int ldlt_factor_gridfirst(double* F, const GfDevice& g, double* Xb, LdltWorkspace& w, hipStream_t s, GemmStats* st, const int* tile_list,
+                          int tile_list_entries, int last_part = 2);
 // pivot chains the block-sparse launch has control words for
 int ldlt_gridfirst_max_chains();
 // Rows that the final dataflow launch factors (w.tail_rows clamped to the workspace's flag storage)
@@ -457,20 +504,16 @@ size_t ldlt_dist_buffer_doubles(int n_pad, int world);
 int ldlt_factor_distributed(double* S, int n, int ld, LdltWorkspace& w, hipStream_t s, const DistComm& c, GemmStats* trailing_stats);
 
 // ---- kernels_gridfirst.hip ----
-int launch_gf_form(double* F, int ldf, int Gf, int n_rp, int n_border, const int* grid_of_f, const double* Hdd, int ldh, const double* bd,
-                   const double* B, const double* S0, int lds0, int rig_dof, const double* Dblk, const double* bblk, double lambda,
-                   const int* tiles, int n_tiles, const unsigned long long* act, int act_words, hipStream_t s);
-int launch_gf_activity(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
-                       int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, DevBuf<unsigned long long>& act,
-                       unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
-                       int mask_words, hipStream_t s);
-int launch_gf_touch(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
-                    int n_rp, int rig_dof, int n_tiles, int words, int slot0, DevBuf<unsigned long long>& act, hipStream_t s);
-int launch_gf_close_masks(int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
-                          unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
-                          int mask_words, hipStream_t s);
-int launch_gf_scatter(const double* xF, int Gf, int n_rp, int block_dof, int G, const int* f_of_grid, int pose0, double* x, hipStream_t s);
-int launch_gf_shared(const GfShared& L, const int* col, double* Hdd, int ld, double* bd, double* buf, int unpack, hipStream_t s);
+// F (g.n_pad x g.n_pad) from the accumulated system `from` (image sharding: the pose rows of all ranks); the strips g.s0 stay where they are
+int launch_gf_form(double* F, const GfDevice& g, const SystemView& from, double lambda, hipStream_t s);
+// the activity g.act of this pass and the masks derived from it (g.kmask, g.rowmask_dyn), in one process
+int launch_gf_activity(const PassArgs& pa, const Observations& obs, const PassOutputs& out, GfDevice& g, hipStream_t s);
+// its two halves.  slot0: border slot of this process's first imageset; act_out (cba_debug_gridfirst): takes the touched rows in g.act's place
+int launch_gf_touch(const PassArgs& pa, const Observations& obs, const PassOutputs& out, GfDevice& g, int slot0, hipStream_t s,
+                    DevBuf<unsigned long long>* act_out = nullptr);
+int launch_gf_close_masks(GfDevice& g, hipStream_t s);
+int launch_gf_scatter(const double* xF, const GfDevice& g, int block_dof, int pose0, double* x, hipStream_t s);
+int launch_gf_shared(const GfShared& L, const int* col, const SystemView& sys, double* buf, int unpack, hipStream_t s);
 int launch_gf_words_to_doubles(const unsigned long long* w, int n, double* out, hipStream_t s);
 int launch_gf_or_words(const double* blocks, int world, long long block_stride, int n, unsigned long long* w, hipStream_t s);
 

@@ -260,45 +260,45 @@ int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n
   CBA_TRY(ldlt_workspace_alloc(w, n_pad));
   hipStream_t s = nullptr;
   CBA_TRY(make_main_stream(&s));
-  int cur = 0, rc = CBA_OK;
+  int cur = 0;
   double lambda = -1.0, last_cost = 0.0;
   const double init_lambda_factor = (double)0.001f;
-  for (int iteration = 0; iteration < max_iteration_count && rc == CBA_OK; ++iteration) {
+  for (int iteration = 0; iteration < max_iteration_count; ++iteration) {
     double t0 = now_s();
-    if ((rc = launch_tangents(g[cur], tang, G, s))) break;
-    if ((rc = launch_fit_pass(true, gw, gh, g[cur], tang, n, gp, dirs, cost_ref, rec, keys, status, s))) break;
+    CBA_TRY(launch_tangents(g[cur], tang, G, s));
+    CBA_TRY(launch_fit_pass(true, gw, gh, g[cur], tang, n, gp, dirs, cost_ref, rec, keys, status, s));
     CBA_TRY(H.zero_async(s));
     CBA_TRY(b.zero_async(s));
-    if ((rc = launch_fit_accumulate(gw, gh, n, rec, keys, count, start, fill, order, H, ld, b, s))) break;
-    if ((rc = launch_reduce_costs(cost_ref, nullptr, nullptr, 3 * n, partials, red8, s))) break;
-    if ((rc = launch_fit_diag_sum(H, ld, dof, scal, s))) break;
+    CBA_TRY(launch_fit_accumulate(gw, gh, n, rec, keys, count, start, fill, order, H, ld, b, s));
+    CBA_TRY(launch_reduce_costs(cost_ref, nullptr, nullptr, 3 * n, partials, red8, s));
+    CBA_TRY(launch_fit_diag_sum(H, ld, dof, scal, s));
     double h8[8], hsum = 0; int st = 0;
-    if ((rc = red8.download_sync(h8, 8, s)) || (rc = scal.download_sync(&hsum, 1, s))) break;
+    CBA_TRY(red8.download_sync(h8, 8, s)); CBA_TRY(scal.download_sync(&hsum, 1, s));
     CBA_TRY(status.download(&st, 1));
     rep.t_pass += now_s() - t0;
-    if (st == 3) { set_error("cba_fit_grid_to_directions: a grid point lies outside the grid's 4x4 patches"); rc = CBA_ERR_ARG; break; }
+    if (st == 3) { set_error("cba_fit_grid_to_directions: a grid point lies outside the grid's 4x4 patches"); return CBA_ERR_ARG; }
     last_cost = h8[0];
     if (iteration == 0) rep.initial_cost = last_cost;
     if (last_cost == 0) break;                              // lm_optimizer.h:755-760: before lambda is initialised (it stays -1)
     if (iteration == 0) lambda = init_lambda_factor * hsum / dof;
     bool applied = false;
-    for (int lm = 0; lm < 10 && rc == CBA_OK; ++lm) {
+    for (int lm = 0; lm < 10; ++lm) {
       rep.lm_attempts += 1;
       t0 = now_s();
       CBA_TRY(S.copy_from_async(H, H.size(), 0, 0, s));
-      if ((rc = launch_finish_diag(S, ld, dof, n_pad, lambda, s))) break;
-      if ((rc = launch_fit_set_rhs(S, ld, b, dof, s))) break;
+      CBA_TRY(launch_finish_diag(S, ld, dof, n_pad, lambda, s));
+      CBA_TRY(launch_fit_set_rhs(S, ld, b, dof, s));
       CBA_TRY(w.status.zero_async(s));
-      if ((rc = ldlt_factor(S, n_fact, ld, w, s, nullptr))) break;
-      if ((rc = ldlt_back_solve(S, n_fact, ld, ld - 1, w, x, s))) break;
+      CBA_TRY(ldlt_factor(S, n_fact, ld, w, s, nullptr));
+      CBA_TRY(ldlt_back_solve(S, n_fact, ld, ld - 1, w, x, s));
       CBA_TRY(w.status.download_sync(&st, 1, s));
       rep.t_solve += now_s() - t0;
       if (st != 0) { lambda = 2.f * lambda; continue; }     // zero pivot: treated like the reference's NaN update
       t0 = now_s();
-      if ((rc = launch_update_direction_grid(g[cur], x, G, g[cur ^ 1], s))) break;
-      if ((rc = launch_fit_pass(false, gw, gh, g[cur ^ 1], tang, n, gp, dirs, cost_test, nullptr, nullptr, status, s))) break;
-      if ((rc = launch_reduce_costs(cost_ref, cost_test, nullptr, 3 * n, partials, red8, s))) break;
-      if ((rc = red8.download_sync(h8, 8, s))) break;
+      CBA_TRY(launch_update_direction_grid(g[cur], x, G, g[cur ^ 1], s));
+      CBA_TRY(launch_fit_pass(false, gw, gh, g[cur ^ 1], tang, n, gp, dirs, cost_test, nullptr, nullptr, status, s));
+      CBA_TRY(launch_reduce_costs(cost_ref, cost_test, nullptr, 3 * n, partials, red8, s));
+      CBA_TRY(red8.download_sync(h8, 8, s));
       rep.t_pass += now_s() - t0;
       if (h8[4] > 0 && h8[3] < h8[2]) {                       // CostIsSmallerThan
         cur ^= 1;
@@ -312,12 +312,9 @@ int cba_fit_grid_to_directions(const cba_camera* camera, double* grid, int64_t n
     }
     if (!applied || last_cost == 0) break;
   }
-  if (rc == CBA_OK) {
-    rep.final_cost = last_cost; rep.lambda = lambda;
-    rc = g[cur].download(grid, 3 * (size_t)G);
-    if (report) *report = rep;
-  }
-  return rc;
+  rep.final_cost = last_cost; rep.lambda = lambda;
+  if (report) *report = rep;
+  return g[cur].download(grid, 3 * (size_t)G);
 }
 
 }  // extern "C"

@@ -39,27 +39,16 @@ int timers_collect(cba_problem* p) {
   return CBA_OK;
 }
 
-// -1 (default): pooled wherever the projections of one wavefront differ in length -- the non-central model (83 tasks per observation) and
-// rigs: 9 - 11 % faster in the bench trajectories of BASELINE configs[3] / [2] -- and one task per lane, the lanes ordered by the
-// predicted iteration count of their tasks (kernels_fd.hip: k_fd_tasks), for a single central-generic camera: the tasks of an
-// observation take one or two outer iterations depending on their control point's weight, which is known before the loop starts,
-// and the pool's bookkeeping inside the loop costs more than it balances (configs[1]: pooled 4 % slower than the unordered lanes,
-// which the ordered ones beat by 0.37 ms of 1.72).  profiles/r05_fd_schedules.txt, r05_fd_schedules_bench.txt, fd_lane_order.json
-// (the ordered lanes also beat the pool at the two-camera rig now: 29.5 against 30.7 ms per step; that default has not been switched)
-static int fd_schedule_of(const cba_problem* p) {
-  if (p->fd_schedule >= 0) return p->fd_schedule;
-  return (p->L.n_cameras == 1 && p->model_mask == 1) ? 1 : 0;
-}
 static PassArgs pass_args(cba_problem* p, int which) {
   PassArgs a;
-  a.n_obs = p->n_obs; a.n_cameras = p->L.n_cameras;
-  a.obs_xy = p->obs_xy; a.obs_point = p->obs_point; a.obs_image = p->obs_image; a.obs_camera = p->obs_camera;
-  a.last_projection = p->last_projection;
+  a.n_obs = p->obs.n; a.n_cameras = p->L.n_cameras;
+  a.obs_xy = p->obs.xy; a.obs_point = p->obs.point; a.obs_image = p->obs.image; a.obs_camera = p->obs.camera;
+  a.last_projection = p->obs.last_projection;
   a.points = p->st[which].points; a.itg = p->itg; a.cams = p->cams_dev[which];
   a.fd_delta = p->cfg.numerical_diff_delta;
   a.pose_slot = p->pose_slot;
   a.obs_list = nullptr; a.obs_count = nullptr; a.obs_list_cap = 0; a.skip = nullptr;
-  a.jrec = p->jrec; a.rec_doubles = p->rec_doubles;
+  a.jrec = p->out.jrec; a.rec_doubles = p->out.rec_doubles;
   a.guard = nullptr;
   return a;
 }
@@ -72,15 +61,15 @@ int allreduce(cba_problem* p, double* dev, int64_t count) {
   return CBA_OK;
 }
 
-// residual pass on state `which`; fills cost vector `cost_vec` and reduces to out8 (host)
-int residual_pass(cba_problem* p, int which, double* cost_vec, const int* guard) {
+// residual pass on state `which`; fills the cost vector out.cost_test
+int residual_pass(cba_problem* p, int which, const int* guard) {
   CBA_TRY(launch_compose_poses(p->st[which], p->L.n_images, p->L.n_cameras, p->itg, p->stream));
   PassArgs a = pass_args(p, which);
   a.guard = guard;
-  CBA_TRY(launch_base_project(a, p->model_mask, cost_vec, p->pixels, p->flags, p->slow_list, p->slow_count, p->slow_cap, p->slow_skip, p->straggler_threshold, nullptr, p->stream));
+  CBA_TRY(launch_base_project(a, p->model_mask, p->out, /* test_cost */ true, p->slow, /* use_fd_slow */ false, p->stream));
   PassArgs as = a;
-  as.obs_list = p->slow_list; as.obs_count = p->slow_count; as.obs_list_cap = p->slow_cap;
-  CBA_TRY(launch_base_project_slow(as, p->model_mask, cost_vec, p->pixels, p->flags, p->stream));
+  as.obs_list = p->slow.list; as.obs_count = p->slow.count; as.obs_list_cap = p->slow.cap;
+  CBA_TRY(launch_base_project_slow(as, p->model_mask, p->out, /* test_cost */ true, p->stream));
   return CBA_OK;
 }
 
@@ -92,41 +81,39 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   CBA_TRY(launch_compose_poses(p->st[w], L.n_images, L.n_cameras, p->itg, p->stream));
   PassArgs a = pass_args(p, w);
   PassArgs as = a;
-  as.obs_list = p->slow_list; as.obs_count = p->slow_count; as.obs_list_cap = p->slow_cap;
-  a.skip = p->slow_skip;
+  as.obs_list = p->slow.list; as.obs_count = p->slow.count; as.obs_list_cap = p->slow.cap;
+  a.skip = p->slow.skip;
   hipStream_t aux = p->ldlt.far_stream, clr = p->ldlt.mid_stream;
   if (p->pf.mask_pending) {      // (two passes without a solve in between: the previous pass's mask launch reads the B this one rewrites)
     CBA_HIP(hipStreamWaitEvent(p->stream, p->pf.ev_mask, 0));
     p->pf.mask_pending = false;
   }
   const size_t bs = L.block_size, nb = L.n_blocks;
-  CBA_TRY(p->fd_redo_count.zero_async(1, p->stream, 2));      // tasks that found a follow-up list full, this pass
-  CBA_TRY(launch_base_project(a, p->model_mask, p->cost_ref, p->pixels, p->flags, p->slow_list, p->slow_count, p->slow_cap, p->slow_skip, p->straggler_threshold, p->fd_slow, p->stream));
+  CBA_TRY(p->fd.redo_count.zero_async(1, p->stream, 2));      // tasks that found a follow-up list full, this pass
+  CBA_TRY(launch_base_project(a, p->model_mask, p->out, /* test_cost */ false, p->slow, /* use_fd_slow */ true, p->stream));
   // ... and the stragglers of the base projection (long projection chains, see k_base_project_slow) are finished there,
   // followed by their finite-difference tasks, underneath the main finite-difference launch
   CBA_HIP(hipEventRecord(p->ev_aux2, p->stream));
   CBA_HIP(hipStreamWaitEvent(aux, p->ev_aux2, 0));
-  CBA_TRY(launch_base_project_slow(as, p->model_mask, p->cost_ref, p->pixels, p->flags, aux));
-  CBA_TRY(launch_fd_tasks(as, p->model_mask, p->tasks_per_obs, L.localize_only, p->pixels, p->flags, p->fd_out, p->fd_ok, p->fd_redo[1], p->fd_redo_count + 1, p->fd_redo_cap,
-                          p->fd_redo_count + 2, aux, fd_schedule_of(p)));
+  CBA_TRY(launch_base_project_slow(as, p->model_mask, p->out, /* test_cost */ false, aux));
+  CBA_TRY(launch_fd_tasks(as, p->model_mask, L.localize_only, p->out, p->fd, kFdSideList, aux));
   CBA_HIP(hipEventRecord(p->ev_aux1, aux));
   CBA_TRY(timer_begin(p, kTimerFd));
-  CBA_TRY(launch_fd_tasks(a, p->model_mask, p->tasks_per_obs, L.localize_only, p->pixels, p->flags, p->fd_out, p->fd_ok, p->fd_redo[0], p->fd_redo_count, p->fd_redo_cap,
-                          p->fd_redo_count + 2, p->stream, fd_schedule_of(p)));
+  CBA_TRY(launch_fd_tasks(a, p->model_mask, L.localize_only, p->out, p->fd, kFdMainList, p->stream));
   CBA_TRY(timer_end(p, kTimerFd, 0, 0, 1));
   // Third stream: the accumulation targets are cleared (1.3 GB for H_dd at cfg 2) underneath the finite-difference launch.  Round 3
   // issued the memsets first, on the side stream: the 0.2 ms fill of H_dd then held the chip before the base projection of the pass
   // got a workgroup slot (profiles/r04_v2_step_timeline_cfg2.txt: base projection 0.25 ms after the tangents); queued behind the
   // VALU-bound FD kernel the fill's workgroups take slots as they come free.
   CBA_HIP(hipStreamWaitEvent(clr, p->ev_aux2, 0));            // behind the base projection of this pass
-  CBA_TRY(p->Dblk.zero_async(clr));
-  CBA_TRY(p->bblk.zero_async(clr));
+  CBA_TRY(p->sys.Dblk.zero_async(clr));
+  CBA_TRY(p->sys.bblk.zero_async(clr));
   if (L.eliminate_points)
-    CBA_TRY(p->B.zero_async(clr));
+    CBA_TRY(p->sys.B.zero_async(clr));
   else                                // padding rows of B (the strips below overwrite everything else, zeros included)
-    CBA_TRY(p->B.zero_async((size_t)(p->Kpad - L.block_dof) * p->n_pad, clr, (size_t)L.block_dof * p->n_pad));
-  CBA_TRY(p->Hdd.zero_async(clr));
-  CBA_TRY(p->bd.zero_async(clr));
+    CBA_TRY(p->sys.B.zero_async((size_t)(p->sys.Kpad - L.block_dof) * p->sys.n_pad, clr, (size_t)L.block_dof * p->sys.n_pad));
+  CBA_TRY(p->sys.Hdd.zero_async(clr));
+  CBA_TRY(p->sys.bd.zero_async(clr));
   if (p->gf.S0) CBA_TRY(p->gf.S0.zero_async(clr));      // grid-first order: the strips of F (the accumulation stores only what it reaches)
   CBA_HIP(hipEventRecord(p->ev_clear, clr));
   CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_aux1, 0));
@@ -135,19 +122,17 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   const bool side = !L.localize_only;      // the per-cell accumulation runs on the side stream
   // (Running the assembly / accumulation of one chunk of imagesets next to the finite-difference launches of the
   // next chunk was measured and gained nothing: the two share the same CUs and the sum stayed the same.)
-  CBA_TRY(launch_assemble(a, L, p->st[w], p->tasks_per_obs, p->pixels, p->flags, p->fd_out, p->fd_ok, p->cells, p->fd_slow, p->stream));
+  CBA_TRY(launch_assemble(a, L, p->st[w], p->out, p->slow, p->stream));
   double t0 = now_s();
   CBA_TRY(timer_begin(p, kTimerAccumulate));
-  AccumTargets T{p->Dblk, p->bblk, p->B, p->Hdd, p->bd};
-  Layout Lp = L;
-  Lp.dense_dof = p->n_pad;  // Hdd / B use the padded leading dimension as row stride
-  const double* det = p->cfg.deterministic ? (const double*)p->det_scale : nullptr;
-  if (det) CBA_TRY(launch_det_scale(a, p->flags, p->det_bits, p->det_scale, p->stream));
-  const int points_separate = (!L.eliminate_points && p->pt_start) ? 1 : 0;
+  SystemView T = p->sys.view();
+  const double* det = p->cfg.deterministic ? (const double*)p->det.scale : nullptr;
+  if (det) CBA_TRY(launch_det_scale(a, p->out, p->det, p->stream));
+  const int points_separate = (!L.eliminate_points && p->obs.pt_start) ? 1 : 0;
   // grid-first order, one process: grid rows x (point | pose) columns go straight to the strips of F (GfStrips)
   if (p->gf.S0) {
-    if (!points_separate && p->n_obs > 0) { set_error("grid-first order: no per-point observation lists"); return CBA_ERR_STATE; }
-    T.gf = GfStrips{p->gf.S0, p->gf.plan.n_pad - p->gf.plan.Gf, p->gf.f_of_grid, p->gf.plan.n_rp};
+    if (!points_separate && p->obs.n > 0) { set_error("grid-first order: no per-point observation lists"); return CBA_ERR_STATE; }
+    T.t.gf = GfStrips{p->gf.S0, p->gf.dev.s0_ld, p->gf.dev.f_of_grid, p->gf.dev.n_rp};
   }
   // The four accumulation kernels write disjoint parts of the system (or add atomically).  The per-cell kernel runs on the side
   // stream next to the others; the per-point kernel (120 KB of LDS per workgroup, one per CU) goes FIRST on the main stream, alone:
@@ -156,24 +141,23 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   if (side) {
     CBA_HIP(hipEventRecord(p->ev_aux0, p->stream));
     CBA_HIP(hipStreamWaitEvent(aux, p->ev_aux0, 0));
-    CBA_TRY(launch_accumulate_cells(a, p->cams, p->cell_base_host, p->n_pad, p->flags, p->cells, p->cell_base, p->cell_count,
-                                    p->cell_start, p->cell_fill, p->cell_order, p->Hdd,
-                                    (!L.eliminate_points && L.rig_in_state) ? L.first_camera_tr_rig - L.block_dof : -1, det, p->bd, aux));
+    CBA_TRY(launch_accumulate_cells(a, p->cams, p->out, p->cell, T, (!L.eliminate_points && L.rig_in_state) ? L.first_camera_tr_rig - L.block_dof : -1,
+                                    det, aux));
     if (p->gridfirst) CBA_TRY(gridfirst_pass_activity(p, a, aux));      // the activity masks of this pass, behind the per-cell accumulation
     CBA_HIP(hipEventRecord(p->ev_aux1, aux));
   }
   if (points_separate)
-    CBA_TRY(launch_accumulate_points(a, Lp, p->cams, p->flags, p->cells, p->pt_start, p->pt_obs, T, det, p->stream));
+    CBA_TRY(launch_accumulate_points(a, L, p->cams, p->obs, p->out, T, det, p->stream));
   if (!L.eliminate_points)   // B strips (plain stores), the remaining terms are added on top atomically
-    CBA_TRY(launch_accumulate_strips(a, Lp, L.n_images, p->flags, p->cells, p->band_mask, p->img_start, p->B, p->n_pad, T.gf, det, p->stream));
-  CBA_TRY(launch_accumulate(a, Lp, p->flags, p->cells, p->pair_tables, p->pair_counts, T, det, points_separate, p->stream));
+    CBA_TRY(launch_accumulate_strips(a, L, p->obs, p->out, p->cell, T, det, p->stream));
+  CBA_TRY(launch_accumulate(a, L, p->out, p->cell, T, det, points_separate, p->stream));
   if (side) CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_aux1, 0));
   if (det) {   // fixed point -> fp64, in place
-    CBA_TRY(launch_det_convert(p->Dblk, nb * bs * bs, det, p->stream));
-    CBA_TRY(launch_det_convert(p->bblk, nb * bs, det + 1, p->stream));      // J^T r: second scale
-    CBA_TRY(launch_det_convert(p->Hdd, (size_t)L.dense_dof * p->n_pad, det, p->stream));
-    CBA_TRY(launch_det_convert(p->bd, (size_t)p->n_pad, det + 1, p->stream));
-    CBA_TRY(launch_det_convert(p->B, (size_t)L.block_dof * p->n_pad, det, p->stream));   // strips store integers, the pose x rig atomics add to them
+    CBA_TRY(launch_det_convert(p->sys.Dblk, nb * bs * bs, det, p->stream));
+    CBA_TRY(launch_det_convert(p->sys.bblk, nb * bs, det + 1, p->stream));      // J^T r: second scale
+    CBA_TRY(launch_det_convert(p->sys.Hdd, (size_t)L.dense_dof * p->sys.n_pad, det, p->stream));
+    CBA_TRY(launch_det_convert(p->sys.bd, (size_t)p->sys.n_pad, det + 1, p->stream));
+    CBA_TRY(launch_det_convert(p->sys.B, (size_t)L.block_dof * p->sys.n_pad, det, p->stream));   // strips store integers, the pose x rig atomics add to them
     if (p->gf.S0) CBA_TRY(launch_det_convert(p->gf.S0, p->gf.S0.size(), det, p->stream));
   }
   CBA_TRY(timer_end(p, kTimerAccumulate, 0, 0, 1));

@@ -9,16 +9,16 @@ int alloc_posefirst_system(cba_problem* p) {
   const size_t bs = p->L.block_size, nb = p->L.n_blocks;
   CBA_TRY(p->pf.ev_mask.create(hipEventDisableTiming));
   CBA_TRY(p->pf.Dinv.alloc(nb * bs * bs));
-  CBA_TRY(p->pf.dinvb.alloc_zero((size_t)p->Kpad));
-  CBA_TRY(p->pf.W.alloc_zero((size_t)p->Kpad * p->n_pad));
-  CBA_TRY(p->pf.S.alloc_zero((size_t)p->n_pad * p->n_pad));
-  CBA_TRY(p->pf.kmask_host.alloc((size_t)(p->n_pad / 128) * schur_mask_words(p->Kpad)));
-  CBA_TRY(p->pf.kmask.alloc((size_t)(p->n_pad / 128) * schur_mask_words(p->Kpad)));
-  if (schur_chunk_count(p->n_pad) > 0) {
-    CBA_TRY(p->pf.chunk_order.alloc((size_t)schur_chunk_count(p->n_pad)));
-    CBA_TRY(p->pf.chunk_order_host.alloc((size_t)schur_chunk_count(p->n_pad)));
+  CBA_TRY(p->pf.dinvb.alloc_zero((size_t)p->sys.Kpad));
+  CBA_TRY(p->pf.W.alloc_zero((size_t)p->sys.Kpad * p->sys.n_pad));
+  CBA_TRY(p->pf.S.alloc_zero((size_t)p->sys.n_pad * p->sys.n_pad));
+  CBA_TRY(p->pf.kmask_host.alloc((size_t)(p->sys.n_pad / 128) * schur_mask_words(p->sys.Kpad)));
+  CBA_TRY(p->pf.kmask.alloc((size_t)(p->sys.n_pad / 128) * schur_mask_words(p->sys.Kpad)));
+  if (schur_chunk_count(p->sys.n_pad) > 0) {
+    CBA_TRY(p->pf.chunk_order.alloc((size_t)schur_chunk_count(p->sys.n_pad)));
+    CBA_TRY(p->pf.chunk_order_host.alloc((size_t)schur_chunk_count(p->sys.n_pad)));
   }
-  return p->pf.gemv_ws.alloc((size_t)gemv_t_workspace_doubles(p->n_pad));
+  return p->pf.gemv_ws.alloc((size_t)gemv_t_workspace_doubles(p->sys.n_pad));
 }
 
 // End of a Jacobian pass.  The block-sparsity mask of B is only read by the Schur product: it is built on the side stream, underneath
@@ -28,7 +28,7 @@ int posefirst_pass_end(cba_problem* p) {
   hipStream_t aux = p->ldlt.far_stream;
   CBA_HIP(hipEventRecord(p->ev_aux2, p->stream));
   CBA_HIP(hipStreamWaitEvent(aux, p->ev_aux2, 0));
-  CBA_TRY(launch_touch_mask(p->B, p->Kpad, p->n_pad, p->n_pad, p->pf.kmask, aux));
+  CBA_TRY(launch_touch_mask(p->sys.B, p->sys.Kpad, p->sys.n_pad, p->sys.n_pad, p->pf.kmask, aux));
   CBA_HIP(hipEventRecord(p->pf.ev_mask, aux));
   p->pf.mask_pending = true;
   return CBA_OK;
@@ -38,9 +38,9 @@ int posefirst_pass_end(cba_problem* p) {
 // kTimerFactor = the whole factorisation.
 int posefirst_enqueue(cba_problem* p, double lambda) {
   const Layout& L = p->L;
-  const int bs = L.block_size, nb = L.n_blocks, dd = L.dense_dof, ld = p->n_pad;
+  const int bs = L.block_size, nb = L.n_blocks, dd = L.dense_dof, ld = p->sys.n_pad;
   const bool multi = p->cfg.allreduce != nullptr;
-  CBA_TRY(launch_block_inverse(p->Dblk, p->bblk, lambda, bs, nb, p->pf.Dinv, p->pf.dinvb, p->status, p->stream));
+  CBA_TRY(launch_block_inverse(p->sys.Dblk, p->sys.bblk, lambda, bs, nb, p->pf.Dinv, p->pf.dinvb, p->status, p->stream));
   // Side stream, next to W = D^-1 B and the Schur product (MFMA-bound, bandwidth to spare): the partial sums of the right-hand
   // side B^T D^-1 b (one pass over B), the touch masks on their way to the host, and the control words of the factorisation's first
   // dataflow launch.  Round 3 had all three between the Schur product and the factorisation: 0.15 ms of small launches and gaps.
@@ -49,14 +49,14 @@ int posefirst_enqueue(cba_problem* p, double lambda) {
     CBA_HIP(hipEventRecord(p->ev_aux0, p->stream));
     CBA_HIP(hipStreamWaitEvent(side, p->ev_aux0, 0));
     // right-hand side: S[j][n_pad-1] = bd[j] - sum_k B[k][j] dinvb[k]; the Schur launch leaves that column alone (keep_col)
-    CBA_TRY(launch_gemv_t_partial(p->B, L.block_dof, dd, ld, p->pf.dinvb, p->pf.gemv_ws, side));
-    CBA_TRY(launch_gemv_t_final(dd, p->bd, p->pf.S + (ld - 1), ld, p->pf.gemv_ws, p->n_pad, side));      // padding rows of the column: zero
+    CBA_TRY(launch_gemv_t_partial(p->sys.B, L.block_dof, dd, ld, p->pf.dinvb, p->pf.gemv_ws, side));
+    CBA_TRY(launch_gemv_t_final(dd, p->sys.bd, p->pf.S + (ld - 1), ld, p->pf.gemv_ws, p->sys.n_pad, side));      // padding rows of the column: zero
     // (algorithmic flops of the Schur launch = K slabs actually multiplied: counted on the host after the solve)
     CBA_TRY(p->pf.kmask.download_async(p->pf.kmask_host, p->pf.kmask.size(), side));
     CBA_TRY(ldlt_clear_ctrl(p->ldlt, side));
     CBA_HIP(hipEventRecord(p->ev_aux1, side));
   }
-  CBA_TRY(launch_dinv_times_B_ld(p->pf.Dinv, p->B, bs, nb, dd, ld, p->pf.W, p->stream));
+  CBA_TRY(launch_dinv_times_B_ld(p->pf.Dinv, p->sys.B, bs, nb, dd, ld, p->pf.W, p->stream));
   CBA_HIP(hipStreamWaitEvent(p->stream, p->ev_aux1, 0));      // side stream: the touch masks (Jacobian pass), the right-hand side column, the control words
   p->pf.mask_pending = false;
   CBA_TRY(timer_begin(p, kTimerProduct));
@@ -68,14 +68,14 @@ int posefirst_enqueue(cba_problem* p, double lambda) {
     CBA_TRY(p->pf.chunk_order.upload_async(p->pf.chunk_order_host, p->pf.chunk_order.size(), p->stream));
     chunk_order = p->pf.chunk_order;
   }
-  CBA_TRY(schur_gemm(p->B, p->pf.W, p->Kpad, ld, p->Hdd, p->pf.S, p->n_pad, ld, dd, (!multi || (dist && p->cfg.rank == 0)) ? 1 : 0, lambda, p->pf.kmask, p->stream, chunk_order, ld - 1));
+  CBA_TRY(schur_gemm(p->sys.B, p->pf.W, p->sys.Kpad, ld, p->sys.Hdd, p->pf.S, p->sys.n_pad, ld, dd, (!multi || (dist && p->cfg.rank == 0)) ? 1 : 0, lambda, p->pf.kmask, p->stream, chunk_order, ld - 1));
   CBA_TRY(timer_end(p, kTimerProduct, 0, 0, 1));
 
   if (multi && !dist) {
-    CBA_TRY(launch_pack_upper(p->pf.S, p->n_pad, p->P, 0, p->stream));
-    CBA_TRY(allreduce(p, p->P, packed_upper_doubles(p->n_pad)));
-    CBA_TRY(launch_pack_upper(p->pf.S, p->n_pad, p->P, 1, p->stream));
-    CBA_TRY(launch_finish_diag(p->pf.S, ld, dd, p->n_pad, lambda, p->stream));
+    CBA_TRY(launch_pack_upper(p->pf.S, p->sys.n_pad, p->P, 0, p->stream));
+    CBA_TRY(allreduce(p, p->P, packed_upper_doubles(p->sys.n_pad)));
+    CBA_TRY(launch_pack_upper(p->pf.S, p->sys.n_pad, p->P, 1, p->stream));
+    CBA_TRY(launch_finish_diag(p->pf.S, ld, dd, p->sys.n_pad, lambda, p->stream));
   }
   GemmStats gs;
   CBA_TRY(timer_begin(p, kTimerFactor));
@@ -85,14 +85,14 @@ int posefirst_enqueue(cba_problem* p, double lambda) {
     c.collective = p->cfg.collective; c.collective_user = p->cfg.collective_user;
     c.allreduce = p->cfg.allreduce; c.allreduce_user = p->cfg.allreduce_user;
     c.send = p->P; c.recv = p->P2; c.buf_doubles = p->P2.size();
-    int rc = ldlt_factor_distributed(p->pf.S, p->n_fact, ld, p->ldlt, p->stream, c, &gs);
+    int rc = ldlt_factor_distributed(p->pf.S, p->sys.n_fact, ld, p->ldlt, p->stream, c, &gs);
     if (rc == CBA_ERR_STATE) set_error("distributed solve: a collective callback failed");
     CBA_TRY(rc);
   } else {
-    CBA_TRY(ldlt_factor(p->pf.S, p->n_fact, ld, p->ldlt, p->stream, &gs));
+    CBA_TRY(ldlt_factor(p->pf.S, p->sys.n_fact, ld, p->ldlt, p->stream, &gs));
   }
   CBA_TRY(timer_end(p, kTimerFactor, gs.flops, 0, gs.launches));
-  CBA_TRY(ldlt_back_solve(p->pf.S, p->n_fact, ld, ld - 1, p->ldlt, p->x + L.block_dof, p->stream));
+  CBA_TRY(ldlt_back_solve(p->pf.S, p->sys.n_fact, ld, ld - 1, p->ldlt, p->x + L.block_dof, p->stream));
   // block part: x_b = D^-1 b - W x_d      (lm_optimizer.h:1366-1367)
   CBA_TRY(launch_gemv_n(p->pf.W, L.block_dof, dd, ld, p->x + L.block_dof, p->pf.dinvb, p->x, p->stream));
   return CBA_OK;
@@ -100,7 +100,7 @@ int posefirst_enqueue(cba_problem* p, double lambda) {
 
 // Behind the host's wait for the solve: the executed flops / bytes of the Schur product from the touch masks, the next chunk order
 void posefirst_finish(cba_problem* p) {
-  const int mask_tiles = p->n_pad / 128, mask_words = schur_mask_words(p->Kpad);
+  const int mask_tiles = p->sys.n_pad / 128, mask_words = schur_mask_words(p->sys.Kpad);
   double slabs = 0;
   for (int tm = 0; tm < mask_tiles; ++tm)
     for (int tn = tm; tn < mask_tiles; ++tn)
@@ -108,7 +108,7 @@ void posefirst_finish(cba_problem* p) {
   const double tiles = mask_tiles * (mask_tiles + 1) / 2.0;
   // (host work while the device idles: only for the first solve and then every 16th -- the pattern hardly moves)
   if (p->pf.chunk_order_host && (!p->pf.chunk_order_valid || (++p->pf.chunk_order_age & 15) == 0)) {
-    schur_chunk_order(p->pf.kmask_host, p->n_pad, p->Kpad, p->pf.chunk_order_host);
+    schur_chunk_order(p->pf.kmask_host, p->sys.n_pad, p->sys.Kpad, p->pf.chunk_order_host);
     p->pf.chunk_order_valid = true;
   }
   p->timers[kTimerProduct].flops += slabs * 2.0 * 128 * 128 * schur_slab_rows();

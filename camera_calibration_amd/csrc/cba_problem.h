@@ -29,8 +29,6 @@ enum Timer {
   kNumTimers
 };
 
-constexpr int kSlowCapMin = 16384;   // capacity of the straggler list: max(this, n_obs / 8), set with the observations
-
 // (the state of the elimination orders and the functions below are internal to the cba_* units: kept out of the library's dynamic
 // symbol table)
 #pragma GCC visibility push(hidden)
@@ -60,8 +58,6 @@ struct GridFirstState {
   // ranks arrive as rows of B).
   DevBuf<double> S0;
   DevBuf<double> xF;              // plan.n_fact: solution in the order of F
-  DevBuf<int> tiles; int n_tiles = 0;        // tiles of F the forming kernel writes
-  DevBuf<int> grid_of_f, f_of_grid;
   PinnedBuf<unsigned long long> kmask_host;    // pinned copy of the border update's K-slab masks (executed flops of the launch)
   double update_flops = 0;                     // executed flops of the border update with the masks of the last pass
   // order of the border update's tiles, heaviest first, from the masks of the PREVIOUS solve (a scheduling hint: any permutation is
@@ -90,36 +86,24 @@ struct cba_problem {
   Layout L{};
   int device = 0;
   hipStream_t stream = nullptr;
-  int64_t n_obs = 0;
   bool have_obs = false, have_state = false, have_system = false;
   int model_mask = 0;
-  int tasks_per_obs = 0, rec_doubles = 0;
-  // observations
-  DevBuf<float> obs_xy; DevBuf<int> obs_point, obs_image, obs_camera;
-  DevBuf<double> last_projection;
+  // the state of the passes over the observations (cba_internal.h)
+  Observations obs;
+  PassOutputs out;
+  StragglerSplit slow;
+  FdWork fd;
+  CellSort cell;
+  DetMode det;
   // state (double buffered)
   DevState st[2];
   int cur = 0;
   DevBuf<double> itg;
   DevBuf<double> tangents[kMaxCameras];
   DevBuf<CamDev> cams_dev[2];
-  // pass outputs
-  DevBuf<double> cost_ref, cost_test, pixels; DevBuf<uint8_t> flags;
-  DevBuf<double> fd_out; DevBuf<uint8_t> fd_ok; DevBuf<double> jrec; DevBuf<int> cells;
-  DevBuf<uint32_t> pair_tables; DevBuf<int> pair_counts;
-  DevBuf<int> pt_start, pt_obs;   // observations bucketed by (camera, pattern point): k_accumulate_points
-  std::vector<int> cell_base_host; DevBuf<int> cell_base, cell_count, cell_start, cell_fill;
-  DevBuf<int> cell_order;
   // imageset -> position of its 6x6 block / rows of B.  Imagesets are sorted along a Z-order curve of the
   // centre of their observations so that the 16-row K slabs of the Schur product touch few grid tiles.
   std::vector<int> pose_slot_host; DevBuf<int> pose_slot;
-  // straggler split of the Jacobian pass (see PassArgs)
-  DevBuf<uint8_t> slow_skip, fd_slow; DevBuf<int> slow_list, slow_count;
-  int slow_cap = kSlowCapMin;
-  int straggler_threshold = 8;    // outer projection iterations before an observation goes to the straggler kernel
-  int fd_schedule = -1;           // finite-difference kernel: -1 = automatic (default), 0 = pooled tasks, 1 = one task per lane, lanes sorted by predicted length, 2 = one task per lane, consecutive (cba_set_fd_schedule)
-  DevBuf<int64_t> img_start;             // first observation of every imageset (+ end), for the strip accumulation
-  DevBuf<unsigned long long> band_mask;      // per observation: column bands of B it touches
   // the side stream is the factorisation's far stream (idle during the Jacobian pass): the process must stay
   // within four HIP streams -- a fifth shares a hardware queue with another one and serialises the LDL^T streams
   // (measured twice, also with GPU_MAX_HW_QUEUES=8)
@@ -128,9 +112,7 @@ struct cba_problem {
   DevBuf<int> gperm[kMaxCameras];
   std::vector<int> dense_perm_host;   // reference dense column -> engine dense column (identity outside the grids)
   DevBuf<double> red_partials, red8;
-  // system: the accumulated normal equations (both elimination orders read them)
-  int n_pad = 0, n_fact = 0, Kpad = 0;
-  DevBuf<double> Dblk, bblk, B, Hdd, bd;
+  NormalSystem sys;       // the accumulated normal equations (both elimination orders read them)
   double* P = nullptr; DevBuf<double> P_own;   // reduce buffer of the multi-rank paths: the caller's cba_config.reduce_buffer, or P_own
   DevBuf<double> P2;                           // receive buffer of the distributed solve
   int64_t P_cap = 0;                           // doubles of the reduce buffer P
@@ -138,11 +120,6 @@ struct cba_problem {
   DevBuf<int> status;
   LdltWorkspace ldlt;
   KernelTimer timers[kNumTimers];
-  // deterministic mode (cba_config.deterministic): fixed-point scale of the current pass
-  DevBuf<unsigned long long> det_bits; DevBuf<double> det_scale;
-  // finite-difference kernel: work lists of the tasks that leave their staged patch (main launch / side-stream launch)
-  DevBuf<int64_t> fd_redo[2]; DevBuf<int> fd_redo_count;   // counts: [0] main list, [1] side-stream list, [2] tasks that found a list full
-  int fd_redo_cap = 0;
   double last_lambda = 0;
   PinnedBuf<double> pin_status;   // pinned host memory: {status, ldlt status, x[0]} of the last solve
   PinnedBuf<double> pin_cost;     // pinned host memory: the 8 reduced scalars of the Jacobian pass when their read is deferred
@@ -196,7 +173,7 @@ int timer_begin(cba_problem* p, int which, hipStream_t s = nullptr);
 int timer_end(cba_problem* p, int which, double flops, double bytes, int launches, hipStream_t s = nullptr);
 int timers_collect(cba_problem* p);
 int allreduce(cba_problem* p, double* dev, int64_t count);
-int residual_pass(cba_problem* p, int which, double* cost_vec, const int* guard = nullptr);
+int residual_pass(cba_problem* p, int which, const int* guard = nullptr);
 int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc);
 
 // ---- cba_solve.hip ----

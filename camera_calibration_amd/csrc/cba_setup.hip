@@ -254,19 +254,19 @@ static int upload_pair_tables(cba_problem* p) {
       }
     counts[slot] = e;
   }
-  CBA_TRY(p->pair_tables.assign(tab));
-  return p->pair_counts.assign(counts, 2);
+  CBA_TRY(p->cell.pair_tables.assign(tab));
+  return p->cell.pair_counts.assign(counts, 2);
 }
 
 // what the passes over the observations need besides the observations: events, state, per-camera arrays, pair tables, cells
 int alloc_pass_buffers(cba_problem* p) {
   const Layout& L = p->L;
   for (Event* e : {&p->ev_aux0, &p->ev_aux1, &p->ev_aux2, &p->ev_clear}) CBA_TRY(e->create(hipEventDisableTiming));
-  CBA_TRY(p->slow_count.alloc_zero(1));
+  CBA_TRY(p->slow.count.alloc_zero(1));
   for (int c = 0; c < L.n_cameras; ++c) p->model_mask |= (p->cams[c].model_type == CBA_CENTRAL_GENERIC) ? 1 : 2;
   const int maxKg = L.localize_only ? 0 : ((p->model_mask & 2) ? 80 : 32);
-  p->tasks_per_obs = 3 + maxKg;
-  p->rec_doubles = kRecHeader + 2 * maxKg;
+  p->out.tasks_per_obs = 3 + maxKg;
+  p->out.rec_doubles = kRecHeader + 2 * maxKg;
   CBA_TRY(alloc_state(p, p->st[0]));
   CBA_TRY(alloc_state(p, p->st[1]));
   CBA_TRY(p->itg.alloc(16 * (size_t)L.n_images * L.n_cameras));
@@ -277,13 +277,13 @@ int alloc_pass_buffers(cba_problem* p) {
   CBA_TRY(upload_camdevs(p, 0));
   CBA_TRY(upload_camdevs(p, 1));
   CBA_TRY(upload_pair_tables(p));
-  p->cell_base_host.assign(L.n_cameras + 1, 0);
-  for (int c = 0; c < L.n_cameras; ++c) p->cell_base_host[c + 1] = p->cell_base_host[c] + p->cams[c].grid_w * p->cams[c].grid_h;
-  const size_t nk = (size_t)p->cell_base_host.back();
-  CBA_TRY(p->cell_base.assign(p->cell_base_host));
-  CBA_TRY(p->cell_count.alloc(nk + 1)); CBA_TRY(p->cell_start.alloc(nk + 1)); CBA_TRY(p->cell_fill.alloc(nk + 1));
-  CBA_TRY(p->det_bits.alloc(2)); CBA_TRY(p->det_scale.alloc(2));
-  CBA_TRY(p->fd_redo_count.alloc_zero(4));
+  p->cell.base_host.assign(L.n_cameras + 1, 0);
+  for (int c = 0; c < L.n_cameras; ++c) p->cell.base_host[c + 1] = p->cell.base_host[c] + p->cams[c].grid_w * p->cams[c].grid_h;
+  const size_t nk = (size_t)p->cell.base_host.back();
+  CBA_TRY(p->cell.base.assign(p->cell.base_host));
+  CBA_TRY(p->cell.count.alloc(nk + 1)); CBA_TRY(p->cell.start.alloc(nk + 1)); CBA_TRY(p->cell.fill.alloc(nk + 1));
+  CBA_TRY(p->det.bits.alloc(2)); CBA_TRY(p->det.scale.alloc(2));
+  CBA_TRY(p->fd.redo_count.alloc_zero(4));
   CBA_TRY(p->red_partials.alloc(256 * 8));
   CBA_TRY(p->red8.alloc(16));
   return CBA_OK;
@@ -292,16 +292,16 @@ int alloc_pass_buffers(cba_problem* p) {
 // normal equations: the accumulated parts, the system of the elimination order, the solve's buffers and pinned outputs
 int alloc_system(cba_problem* p) {
   const Layout& L = p->L;
-  padded_dims(L.dense_dof, &p->n_pad, &p->n_fact);
-  p->Kpad = round_up(L.block_dof > 0 ? L.block_dof : 1, 48);      // a multiple of the dense K slab (16) and of the block-sparse one (12)
+  padded_dims(L.dense_dof, &p->sys.n_pad, &p->sys.n_fact);
+  p->sys.Kpad = round_up(L.block_dof > 0 ? L.block_dof : 1, 48);      // a multiple of the dense K slab (16) and of the block-sparse one (12)
   const size_t bs = L.block_size, nb = L.n_blocks;
-  CBA_TRY(p->Dblk.alloc(nb * bs * bs));
-  CBA_TRY(p->bblk.alloc(nb * bs));
-  CBA_TRY(p->B.alloc((size_t)p->Kpad * p->n_pad));
-  CBA_TRY(p->Hdd.alloc((size_t)p->n_pad * p->n_pad));
-  CBA_TRY(p->bd.alloc((size_t)p->n_pad));
+  CBA_TRY(p->sys.Dblk.alloc(nb * bs * bs));
+  CBA_TRY(p->sys.bblk.alloc(nb * bs));
+  CBA_TRY(p->sys.B.alloc((size_t)p->sys.Kpad * p->sys.n_pad));
+  CBA_TRY(p->sys.Hdd.alloc((size_t)p->sys.n_pad * p->sys.n_pad));
+  CBA_TRY(p->sys.bd.alloc((size_t)p->sys.n_pad));
   CBA_TRY(p->gridfirst ? alloc_gridfirst_system(p) : alloc_posefirst_system(p));
-  CBA_TRY(p->x.alloc_zero((size_t)L.block_dof + p->n_pad));
+  CBA_TRY(p->x.alloc_zero((size_t)L.block_dof + p->sys.n_pad));
   CBA_TRY(p->scal.alloc(16));
   CBA_TRY(p->status.alloc(2));      // [0] block-inverse status, [1] guard word of the solve (k_solve_status)
   CBA_TRY(p->pin_status.alloc(4));
@@ -314,9 +314,9 @@ int alloc_system(cba_problem* p) {
 int alloc_reduce_buffer(cba_problem* p, const cba_config* config) {
   if (!config->allreduce) return CBA_OK;
   // the reduced system crosses ranks as its upper 128-row blocks only (half the all-reduce volume); grid-first: the shared blocks
-  int64_t need = p->gf_sharded ? p->sh.shared.doubles : packed_upper_doubles(p->n_pad);
+  int64_t need = p->gf_sharded ? p->sh.shared.doubles : packed_upper_doubles(p->sys.n_pad);
   if (config->distributed_solve) {       // staging of the reduce-scatter / all-gathers (send: P, receive: P2)
-    need = (int64_t)ldlt_dist_buffer_doubles(p->n_pad, config->world_size);
+    need = (int64_t)ldlt_dist_buffer_doubles(p->sys.n_pad, config->world_size);
     CBA_TRY(p->P2.alloc((size_t)need));
   }
   if (config->reduce_buffer) {
@@ -333,7 +333,7 @@ int alloc_reduce_buffer(cba_problem* p, const cba_config* config) {
 // LDL^T workspace (the grid-first one has flags for every grid block row), with the problem's solver options
 int alloc_ldlt_workspace(cba_problem* p) {
   if (p->gridfirst) CBA_TRY(ldlt_workspace_alloc(p->ldlt, p->gf.plan.n_pad, p->gf.plan.nbg));
-  else CBA_TRY(ldlt_workspace_alloc(p->ldlt, p->n_pad));
+  else CBA_TRY(ldlt_workspace_alloc(p->ldlt, p->sys.n_pad));
   apply_solver_options(p->ldlt, &p->cfg.solver);
   return CBA_OK;
 }

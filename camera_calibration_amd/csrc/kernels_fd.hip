@@ -489,10 +489,22 @@ __global__ void __launch_bounds__(256) k_fd_redo(PassArgs a, int tasks_per_obs, 
   if (c.model_type != MODEL) return;
   fd_task<MODEL, false>(a, c, cam, o, k, t, pixels, fd_out, fd_ok, nullptr, nullptr);
 }
-int launch_fd_tasks(const PassArgs& a, int model_mask, int tasks_per_obs, int localize_only, const double* pixels,
-                    const uint8_t* flags, double* fd_out, uint8_t* fd_ok, int64_t* redo, int* redo_count, int redo_cap, int* redo_overflow,
-                    hipStream_t s, int schedule) {
+// fd.schedule = -1 (default): pooled wherever the projections of one wavefront differ in length -- the non-central model (83 tasks per
+// observation) and rigs: 9 - 11 % faster in the bench trajectories of BASELINE configs[3] / [2] -- and one task per lane, the lanes
+// ordered by the predicted iteration count of their tasks (k_fd_tasks), for a single central-generic camera: the tasks of an
+// observation take one or two outer iterations depending on their control point's weight, which is known before the loop starts,
+// and the pool's bookkeeping inside the loop costs more than it balances (configs[1]: pooled 4 % slower than the unordered lanes,
+// which the ordered ones beat by 0.37 ms of 1.72).  profiles/r05_fd_schedules.txt, r05_fd_schedules_bench.txt, fd_lane_order.json
+// (the ordered lanes also beat the pool at the two-camera rig now: 29.5 against 30.7 ms per step; that default has not been switched)
+static int fd_schedule_of(const FdWork& fd, const PassArgs& a, int model_mask) {
+  if (fd.schedule >= 0) return fd.schedule;
+  return (a.n_cameras == 1 && model_mask == 1) ? 1 : 0;
+}
+int launch_fd_tasks(const PassArgs& a, int model_mask, int localize_only, PassOutputs& out, FdWork& fd, FdList list, hipStream_t s) {
   if (a.n_obs == 0) return CBA_OK;
+  const int tasks_per_obs = out.tasks_per_obs, schedule = fd_schedule_of(fd, a, model_mask), redo_cap = fd.redo_cap;
+  const double* pixels = out.pixels; const uint8_t* flags = out.flags; double* fd_out = out.fd_out; uint8_t* fd_ok = out.fd_ok;
+  int64_t* redo = fd.redo[list]; int* redo_count = fd.redo_count + list; int* redo_overflow = fd.redo_count + 2;
   int64_t total = (a.obs_list ? (int64_t)a.obs_list_cap : a.n_obs) * tasks_per_obs;
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
   if (tasks_per_obs < kFdMinStagedTasks) {      // localize_only: 3 tasks per observation

@@ -96,17 +96,15 @@ __global__ void __launch_bounds__(256) k_gf_form(GfFormArgs a) {
   }
 }
 
-int launch_gf_form(double* F, int ldf, int Gf, int n_rp, int n_border, const int* grid_of_f, const double* Hdd, int ldh, const double* bd,
-                   const double* B, const double* S0, int lds0, int rig_dof, const double* Dblk, const double* bblk, double lambda,
-                   const int* tiles, int n_tiles, const unsigned long long* act, int act_words, hipStream_t s) {
-  if (n_tiles <= 0) return CBA_OK;
+int launch_gf_form(double* F, const GfDevice& g, const SystemView& from, double lambda, hipStream_t s) {
+  if (g.n_tiles <= 0) return CBA_OK;
   GfFormArgs a{};
-  a.S0 = S0; a.lds0 = lds0; a.rig_dof = rig_dof;
-  a.act = act; a.act_words = act_words; a.nbg = Gf / 64;
-  a.F = F; a.ldf = ldf; a.Gf = Gf; a.n_rp = n_rp; a.n_border = n_border; a.grid_of_f = grid_of_f;
-  a.Hdd = Hdd; a.ldh = ldh; a.bd = bd; a.B = B; a.Dblk = Dblk; a.bblk = bblk; a.lambda = lambda;
-  a.tiles = reinterpret_cast<const int2*>(tiles);
-  hipLaunchKernelGGL(k_gf_form, dim3((unsigned)n_tiles), dim3(256), 0, s, a);
+  a.S0 = g.s0; a.lds0 = g.s0_ld; a.rig_dof = g.rig_dof;
+  a.act = g.act; a.act_words = g.act_words; a.nbg = g.Gf / 64;
+  a.F = F; a.ldf = g.n_pad; a.Gf = g.Gf; a.n_rp = g.n_rp; a.n_border = g.n_border; a.grid_of_f = g.grid_of_f;
+  a.Hdd = from.t.Hdd; a.ldh = from.ld; a.bd = from.t.bd; a.B = from.t.B; a.Dblk = from.t.Dblk; a.bblk = from.t.bblk; a.lambda = lambda;
+  a.tiles = reinterpret_cast<const int2*>((const int*)g.tiles);
+  hipLaunchKernelGGL(k_gf_form, dim3((unsigned)g.n_tiles), dim3(256), 0, s, a);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
@@ -233,36 +231,35 @@ __global__ void k_gf_masks(const unsigned long long* __restrict__ act, int n_til
 }
 // the two halves of launch_gf_activity: the touched rows of this process's observations (image sharding: OR-ed over the ranks in
 // between, cba_gridfirst.hip gf_exchange), then their closure and the masks derived from it
-int launch_gf_touch(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
-                    int n_rp, int rig_dof, int n_tiles, int words, int slot0, DevBuf<unsigned long long>& act, hipStream_t s) {
+int launch_gf_touch(const PassArgs& pa, const Observations& obs, const PassOutputs& out, GfDevice& g, int slot0, hipStream_t s,
+                    DevBuf<unsigned long long>* act_out) {
+  DevBuf<unsigned long long>& act = act_out ? *act_out : g.act;
+  const int n_images = (int)obs.img_start.size() - 1, n_tiles = g.n_act_tiles, words = g.act_words;
   if (words > 16) { set_error("grid-first: more than 1024 grid block rows"); return CBA_ERR_UNSUPPORTED; }
   CBA_TRY(act.zero_async((size_t)n_tiles * words, s));
   if (pa.n_obs > 0 && n_images > 0) {
     GfTouchArgs a{};
-    a.obs_point = pa.obs_point; a.obs_image = pa.obs_image; a.obs_camera = pa.obs_camera; a.flags = flags; a.cells = cells; a.img_start = img_start;
-    a.pose_slot = pa.pose_slot; a.cams = pa.cams; a.f_of_grid = f_of_grid;
-    a.n_rp = n_rp; a.rig_dof = rig_dof; a.n_tiles = n_tiles; a.words = words; a.slot0 = slot0; a.act = act;
+    a.obs_point = pa.obs_point; a.obs_image = pa.obs_image; a.obs_camera = pa.obs_camera; a.flags = out.flags; a.cells = out.cells; a.img_start = obs.img_start;
+    a.pose_slot = pa.pose_slot; a.cams = pa.cams; a.f_of_grid = g.f_of_grid;
+    a.n_rp = g.n_rp; a.rig_dof = g.rig_dof; a.n_tiles = n_tiles; a.words = words; a.slot0 = slot0; a.act = act;
     hipLaunchKernelGGL(k_gf_touch, dim3((unsigned)n_images), dim3(256), sizeof(unsigned long long) * (size_t)n_tiles * words, s, a);
   }
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
-int launch_gf_close_masks(int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, unsigned long long* act,
-                          unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
-                          int mask_words, hipStream_t s) {
-  hipLaunchKernelGGL(k_gf_close, dim3((n_tiles + 63) / 64), dim3(64), 0, s, act, n_tiles, words, nbg, gridrow);
-  const int total = n_tiles * kwords + nbf * mask_words;
-  hipLaunchKernelGGL(k_gf_masks, dim3((total + 255) / 256), dim3(256), 0, s, act, n_tiles, words, nbg, nbf, tile0, kmask, kwords, rowmask_static, rowmask, mask_words);
+int launch_gf_close_masks(GfDevice& g, hipStream_t s) {
+  const int n_tiles = g.n_act_tiles, words = g.act_words;
+  unsigned long long* act = g.act;
+  hipLaunchKernelGGL(k_gf_close, dim3((n_tiles + 63) / 64), dim3(64), 0, s, act, n_tiles, words, g.nbg, (const unsigned long long*)g.gridrow);
+  const int total = n_tiles * g.kmask_words + g.nbf * g.mask_words;
+  hipLaunchKernelGGL(k_gf_masks, dim3((total + 255) / 256), dim3(256), 0, s, (const unsigned long long*)act, n_tiles, words, g.nbg, g.nbf, g.Gf / 128,
+                     (unsigned long long*)g.kmask, g.kmask_words, (const unsigned long long*)g.rowmask, (unsigned long long*)g.rowmask_dyn, g.mask_words);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
-int launch_gf_activity(const PassArgs& pa, const uint8_t* flags, const int* cells, const int64_t* img_start, int n_images, const int* f_of_grid,
-                       int n_rp, int rig_dof, int n_tiles, int words, int nbg, int nbf, const unsigned long long* gridrow, DevBuf<unsigned long long>& act,
-                       unsigned long long* kmask, int kwords, int tile0, const unsigned long long* rowmask_static, unsigned long long* rowmask,
-                       int mask_words, hipStream_t s) {
-  int rc = launch_gf_touch(pa, flags, cells, img_start, n_images, f_of_grid, n_rp, rig_dof, n_tiles, words, 0, act, s);
-  if (rc != CBA_OK) return rc;
-  return launch_gf_close_masks(n_tiles, words, nbg, nbf, gridrow, act, kmask, kwords, tile0, rowmask_static, rowmask, mask_words, s);
+int launch_gf_activity(const PassArgs& pa, const Observations& obs, const PassOutputs& out, GfDevice& g, hipStream_t s) {
+  CBA_TRY(launch_gf_touch(pa, obs, out, g, 0, s));
+  return launch_gf_close_masks(g, s);
 }
 
 // x (engine layout: 6 N pose entries in slot order, then the dense columns [rig | points | grid]) from xF (rows of F); pose0: first
@@ -278,9 +275,9 @@ __global__ void __launch_bounds__(256) k_gf_scatter(const double* __restrict__ x
   else f = f_of_grid[i - block_dof - n_rp];
   x[i] = xF[f];
 }
-int launch_gf_scatter(const double* xF, int Gf, int n_rp, int block_dof, int G, const int* f_of_grid, int pose0, double* x, hipStream_t s) {
-  const int total = block_dof + n_rp + G;
-  hipLaunchKernelGGL(k_gf_scatter, dim3((total + 255) / 256), dim3(256), 0, s, xF, Gf, n_rp, block_dof, G, f_of_grid, pose0, x);
+int launch_gf_scatter(const double* xF, const GfDevice& g, int block_dof, int pose0, double* x, hipStream_t s) {
+  const int total = block_dof + g.n_rp + g.G;
+  hipLaunchKernelGGL(k_gf_scatter, dim3((total + 255) / 256), dim3(256), 0, s, xF, g.Gf, g.n_rp, block_dof, g.G, (const int*)g.f_of_grid, pose0, x);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
@@ -339,9 +336,9 @@ __global__ void __launch_bounds__(256) k_gf_shared(GfSharedArgs a) {
     else a.buf[e] = h >= 0 ? a.Hdd[h] : 0.0;
   }
 }
-int launch_gf_shared(const GfShared& L, const int* col, double* Hdd, int ld, double* bd, double* buf, int unpack, hipStream_t s) {
+int launch_gf_shared(const GfShared& L, const int* col, const SystemView& sys, double* buf, int unpack, hipStream_t s) {
   GfSharedArgs a{};
-  a.Hdd = Hdd; a.ld = ld; a.bd = bd; a.buf = buf; a.col = col;
+  a.Hdd = sys.t.Hdd; a.ld = sys.ld; a.bd = sys.t.bd; a.buf = buf; a.col = col;
   a.n_cams = L.n_cameras; a.rig = L.rig; a.n_rp = L.n_rp; a.G = L.G;
   for (int c = 0; c <= L.n_cameras; ++c) { a.cam_pos[c] = L.cam_pos[c]; a.band_off[c] = L.band_off[c]; }
   for (int c = 0; c < L.n_cameras; ++c) a.width[c] = L.width[c];

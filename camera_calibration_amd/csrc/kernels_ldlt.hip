@@ -301,29 +301,28 @@ static int ldlt_sparse(double* F, int ld, const GfDevice& g, LdltWorkspace& w, h
   return CBA_OK;
 }
 
-// Factors rows [0, n_fact) of F = [grid | border] (ld = n_pad of the plan): block-sparse launch of the grid rows, ONE update of
-// the border by the K = Gf product C -= L^T X on the 128 x 128 MFMA GEMM (optionally block-sparse in K: `kmask`, one bit per
+// Factors rows [0, g.n_fact) of F = [grid | border] (ld = g.n_pad): block-sparse launch of the grid rows, ONE update of
+// the border by the K = Gf product C -= L^T X on the 128 x 128 MFMA GEMM (block-sparse in K: g.kmask, one bit per
 // 128-column border tile and 16-row slab; `tile_list`: the (tm, tn) tiles of the update in the order they should be handed out,
 // heaviest first -- a scheduling hint, any permutation of the upper tiles is correct), then the dense border by the two-level
 // schedule of ldlt_factor.  last_part (cba_debug_gridfirst): stop behind the block-sparse launch (0) or behind the border update (1).
-int ldlt_factor_gridfirst(double* F, int n_fact, int ld, const GfDevice& g, double* Xb, int ldxb, LdltWorkspace& w, hipStream_t s,
-                          GemmStats* st, const unsigned long long* kmask, int kmask_words, const int* tile_list, int tile_list_entries,
-                          int last_part) {
+int ldlt_factor_gridfirst(double* F, const GfDevice& g, double* Xb, LdltWorkspace& w, hipStream_t s, GemmStats* st, const int* tile_list,
+                          int tile_list_entries, int last_part) {
   int rc;
+  const int Gf = g.nbg * kInner, ld = g.n_pad, ldxb = ld - Gf;
   if ((rc = ldlt_sparse(F, ld, g, w, s, st, Xb, ldxb))) return rc;
   if (last_part < 1) return CBA_OK;
-  const int Gf = g.nbg * kInner;
   GemmArgs u{};
   u.A = F; u.lda = ld; u.B = Xb - Gf; u.ldb = ldxb; u.K = Gf;
   u.C = F; u.ldc = ld; u.Cin = F; u.ldcin = ld; u.diag = 0; u.upper = 1;
   const int tl = (ld - Gf) / 128;
   u.m_off = Gf; u.m_tiles = tl; u.n_off = Gf; u.n_tiles = tl;
-  u.kmask = kmask; u.kmask_words = kmask_words; u.slab16 = 1; u.tile_list = reinterpret_cast<const int4*>(tile_list); u.tile_list_entries = tile_list_entries;
+  u.kmask = g.kmask; u.kmask_words = g.kmask_words; u.slab16 = 1; u.tile_list = reinterpret_cast<const int4*>(tile_list); u.tile_list_entries = tile_list_entries;
   if ((rc = timed_gemm128(u, s, w, st != nullptr, (double)tl * (tl + 1) / 2))) return rc;
-  if (st && kmask && w.spans_used > 0) w.spans[w.spans_used - 1].masked_update = true;      // (the caller replaces the dense flop count by the executed one)
+  if (st && w.spans_used > 0) w.spans[w.spans_used - 1].masked_update = true;      // (the caller replaces the dense flop count by the executed one)
   if (st) { const double rows = (double)(ld - Gf); st->flops += rows * rows * Gf; st->launches += 1; }
   if (last_part < 2) return CBA_OK;
-  return ldlt_factor(F, n_fact, ld, w, s, st, Gf);
+  return ldlt_factor(F, g.n_fact, ld, w, s, st, Gf);
 }
 
 }  // namespace cba

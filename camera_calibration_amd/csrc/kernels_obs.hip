@@ -155,12 +155,11 @@ __global__ void __launch_bounds__(256) k_assemble(PassArgs a, int rig_in_state, 
   if (o < a.n_obs) fd_slow[o] = flags[o] == 1;
   (void)with_jacobian;     // the 2 x K_g grid part of the record was written by the finite-difference tasks themselves (fd_task)
 }
-int launch_assemble(const PassArgs& a, const Layout& L, const DevState& st, int tasks_per_obs, const double* pixels, uint8_t* flags,
-                    const double* fd_out, const uint8_t* fd_ok, int* cells, uint8_t* fd_slow, hipStream_t s) {
+int launch_assemble(const PassArgs& a, const Layout& L, const DevState& st, PassOutputs& out, StragglerSplit& slow, hipStream_t s) {
   if (a.n_obs == 0) return CBA_OK;
   hipLaunchKernelGGL(k_assemble, dim3((unsigned)((a.n_obs + 255) / 256)), dim3(256), 0, s, a, L.rig_in_state,
-                     L.localize_only, st.rig_tr_global, st.camera_tr_rig, tasks_per_obs, a.rec_doubles, pixels, flags,
-                     fd_out, fd_ok, a.jrec, cells, fd_slow);
+                     L.localize_only, st.rig_tr_global, st.camera_tr_rig, out.tasks_per_obs, a.rec_doubles, out.pixels, out.flags,
+                     out.fd_out, out.fd_ok, a.jrec, out.cells, slow.fd_slow);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
@@ -175,14 +174,14 @@ int launch_assemble(const PassArgs& a, const Layout& L, const DevState& st, int 
 struct AccumLayout {
   int rig_in_state, eliminate_points, localize_only;
   int first_rig_tr_global, first_camera_tr_rig, first_points;
-  int block_dof, block_size, dense_dof;
+  int block_dof, block_size, ld;      // ld: row stride of B and H_dd
 };
 static_assert(std::is_trivially_copyable_v<AccumLayout>);
-static AccumLayout accum_layout(const Layout& L) {
+static AccumLayout accum_layout(const Layout& L, int ld) {
   AccumLayout al;
   al.rig_in_state = L.rig_in_state; al.eliminate_points = L.eliminate_points; al.localize_only = L.localize_only;
   al.first_rig_tr_global = L.first_rig_tr_global; al.first_camera_tr_rig = L.first_camera_tr_rig;
-  al.first_points = L.first_points; al.block_dof = L.block_dof; al.block_size = L.block_size; al.dense_dof = L.dense_dof;
+  al.first_points = L.first_points; al.block_dof = L.block_dof; al.block_size = L.block_size; al.ld = ld;
   return al;
 }
 // A run-time flag as a compile-time one: calls f(std::true_type{}) or f(std::false_type{}).  The launchers below pick the DET
@@ -239,10 +238,10 @@ __device__ __forceinline__ void acc_add_H(const AccumLayout& L, const AccumTarge
       int base = blk * L.block_size;
       Acc<DET>::add(T.Dblk + (size_t)blk * L.block_size * L.block_size + (row - base) * L.block_size + (col - base), v);
     } else {
-      Acc<DET>::add(T.B + (size_t)row * L.dense_dof + (col - L.block_dof), v);
+      Acc<DET>::add(T.B + (size_t)row * L.ld + (col - L.block_dof), v);
     }
   } else {
-    Acc<DET>::add(T.Hdd + (size_t)(row - L.block_dof) * L.dense_dof + (col - L.block_dof), v);
+    Acc<DET>::add(T.Hdd + (size_t)(row - L.block_dof) * L.ld + (col - L.block_dof), v);
   }
 }
 template <bool DET>
@@ -576,7 +575,7 @@ __global__ void __launch_bounds__(kPointThreads) k_accumulate_points(PassArgs a,
     } else {
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        double* out = T.Hdd + (size_t)(point_idx - L.block_dof + r) * L.dense_dof + cd.intr_offset + c0;
+        double* out = T.Hdd + (size_t)(point_idx - L.block_dof + r) * L.ld + cd.intr_offset + c0;
         for (int c = tid; c < c1 - c0; c += NT) out[c] = s_rows[r * chunk_cols + c];
       }
     }
@@ -643,10 +642,10 @@ int point_chunks(const std::vector<cba_camera>& cams, int localize_only, int* ch
   *chunk_cols = std::max(8, ((maxcols + nchunks - 1) / nchunks + 7) / 8 * 8);
   return nchunks;
 }
-int launch_accumulate_points(const PassArgs& a, const Layout& L, const std::vector<cba_camera>& cams, const uint8_t* flags, const int* cells,
-                             const int* key_start, const int* key_obs, AccumTargets t, const double* det_scale, hipStream_t s) {
+int launch_accumulate_points(const PassArgs& a, const Layout& L, const std::vector<cba_camera>& cams, const Observations& obs,
+                             const PassOutputs& out, const SystemView& sys, const double* det_scale, hipStream_t s) {
   if (a.n_obs == 0 || L.n_points == 0) return CBA_OK;
-  const AccumLayout al = accum_layout(L);
+  const AccumLayout al = accum_layout(L, sys.ld);
   int chunk_cols = 0;
   const int nchunks = point_chunks(cams, L.localize_only, &chunk_cols);
   const size_t lds = sizeof(double) * 3 * (size_t)chunk_cols;
@@ -660,8 +659,8 @@ int launch_accumulate_points(const PassArgs& a, const Layout& L, const std::vect
   });
   CBA_HIP(attr_rc);
   by_flag(det_scale != nullptr, [&](auto det) {
-    hipLaunchKernelGGL(k_accumulate_points<decltype(det)::value>, grid, dim3(kPointThreads), lds, s, a, al, a.rec_doubles, flags, a.jrec, cells, key_start,
-                       key_obs, L.n_points, nchunks, chunk_cols, t, det_scale);
+    hipLaunchKernelGGL(k_accumulate_points<decltype(det)::value>, grid, dim3(kPointThreads), lds, s, a, al, a.rec_doubles, out.flags, a.jrec, out.cells,
+                       obs.pt_start, obs.pt_obs, L.n_points, nchunks, chunk_cols, sys.t, det_scale);
   });
   CBA_HIP(hipGetLastError());
   return CBA_OK;
@@ -840,18 +839,16 @@ __global__ void __launch_bounds__(256) k_accumulate_cells(PassArgs a, int cam, i
     Acc<DET>::add(Hdd + (size_t)(rig_row0 + q) * ld + col, racc[t]);      // rig rows precede the grid columns
   }
 }
-int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const std::vector<int>& cell_base_host, int ld,
-                            const uint8_t* flags, const int* cells, const int* cell_base, DevBuf<int>& count, int* start, DevBuf<int>& fill, int* order,
-                            double* Hdd, int rig_row_first /* dense row of camera 0's rig block, or -1 */, const double* det_scale, double* bd,
-                            hipStream_t s) {
+int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& cams, const PassOutputs& out, CellSort& cell,
+                            const SystemView& sys, int rig_row_first /* dense row of camera 0's rig block, or -1 */, const double* det_scale, hipStream_t s) {
   if (a.n_obs == 0) return CBA_OK;
-  const int n_keys = cell_base_host.back();
-  CBA_TRY(count.zero_async((size_t)n_keys, s));
-  CBA_TRY(fill.zero_async((size_t)n_keys, s));
+  const int n_keys = cell.base_host.back();
+  CBA_TRY(cell.count.zero_async((size_t)n_keys, s));
+  CBA_TRY(cell.fill.zero_async((size_t)n_keys, s));
   dim3 grid((unsigned)((a.n_obs + 255) / 256)), block(256);
-  hipLaunchKernelGGL(k_cell_count, grid, block, 0, s, a, flags, cells, cell_base, count);
-  CBA_TRY(launch_exclusive_scan(count, n_keys, start, s));
-  hipLaunchKernelGGL(k_cell_fill, grid, block, 0, s, a, flags, cells, cell_base, start, fill, order);
+  hipLaunchKernelGGL(k_cell_count, grid, block, 0, s, a, out.flags, out.cells, cell.base, cell.count);
+  CBA_TRY(launch_exclusive_scan(cell.count, n_keys, cell.start, s));
+  hipLaunchKernelGGL(k_cell_fill, grid, block, 0, s, a, out.flags, out.cells, cell.base, cell.start, cell.fill, cell.order);
   for (size_t c = 0; c < cams.size(); ++c) {
     const int n_cells = cams[c].grid_w * cams[c].grid_h;
     dim3 g2((unsigned)n_cells);
@@ -859,8 +856,8 @@ int launch_accumulate_cells(const PassArgs& a, const std::vector<cba_camera>& ca
     const bool central = cams[c].model_type == CBA_CENTRAL_GENERIC;
     by_flag(det_scale != nullptr, [&](auto det) { by_flag(rr >= 0, [&](auto rig) { by_flag(central, [&](auto cen) {
       constexpr int PER = decltype(cen)::value ? 2 : 5;
-      hipLaunchKernelGGL((k_accumulate_cells<PER, decltype(det)::value, decltype(rig)::value>), g2, block, 0, s, a, (int)c, cell_base_host[c], n_cells,
-                         a.rec_doubles, ld, a.jrec, start, order, Hdd, rr, det_scale, bd);
+      hipLaunchKernelGGL((k_accumulate_cells<PER, decltype(det)::value, decltype(rig)::value>), g2, block, 0, s, a, (int)c, cell.base_host[c], n_cells,
+                         a.rec_doubles, sys.ld, a.jrec, cell.start, cell.order, sys.t.Hdd, rr, det_scale, sys.t.bd);
     }); }); });
   }
   CBA_HIP(hipGetLastError());
@@ -1091,36 +1088,35 @@ __global__ void __launch_bounds__(64 * kStripWaves) k_accumulate_strips(PassArgs
     out[(size_t)fog[c] * gf.ld + k] = accb[k * kStripBand + c];
   }
 }
-int launch_accumulate_strips(const PassArgs& a, const Layout& L, int n_images, const uint8_t* flags, const int* cells,
-                             unsigned long long* band_mask, const int64_t* img_start, double* B, int ld, const GfStrips& gf,
-                             const double* det_scale, hipStream_t s) {
-  if (n_images == 0) return CBA_OK;
-  const AccumLayout al = accum_layout(L);
-  const int bands = (ld + kStripBand - 1) / kStripBand;
+int launch_accumulate_strips(const PassArgs& a, const Layout& L, const Observations& obs, const PassOutputs& out, CellSort& cell,
+                             const SystemView& sys, const double* det_scale, hipStream_t s) {
+  if (L.n_images == 0) return CBA_OK;
+  const AccumLayout al = accum_layout(L, sys.ld);
+  const int bands = (sys.ld + kStripBand - 1) / kStripBand;
   if (a.n_obs > 0 && !L.localize_only)      // (localize_only: no grid columns, the mask is not read)
-    hipLaunchKernelGGL(k_strip_band_mask, dim3((unsigned)((a.n_obs + 255) / 256)), dim3(256), 0, s, a, flags, cells, band_mask, bands);
+    hipLaunchKernelGGL(k_strip_band_mask, dim3((unsigned)((a.n_obs + 255) / 256)), dim3(256), 0, s, a, out.flags, out.cells, cell.band_mask, bands);
   by_flag(det_scale != nullptr, [&](auto det) {
-    hipLaunchKernelGGL(k_accumulate_strips<decltype(det)::value>, dim3((unsigned)n_images, (unsigned)bands), dim3(64 * kStripWaves), 0, s, a, al, L.n_points,
-                       a.rec_doubles, flags, a.jrec, cells, band_mask, img_start, B, ld, gf, det_scale);
+    hipLaunchKernelGGL(k_accumulate_strips<decltype(det)::value>, dim3((unsigned)L.n_images, (unsigned)bands), dim3(64 * kStripWaves), 0, s, a, al, L.n_points,
+                       a.rec_doubles, out.flags, a.jrec, out.cells, cell.band_mask, obs.img_start, sys.t.B, sys.ld, sys.t.gf, det_scale);
   });
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
 
-int launch_accumulate(const PassArgs& a, const Layout& L, const uint8_t* flags, const int* cells, const uint32_t* pair_tables,
-                      const int* pair_counts, AccumTargets t, const double* det_scale, int points_separate, hipStream_t s) {
+int launch_accumulate(const PassArgs& a, const Layout& L, const PassOutputs& out, const CellSort& cell, const SystemView& sys,
+                      const double* det_scale, int points_separate, hipStream_t s) {
   if (a.n_obs == 0) return CBA_OK;
-  const AccumLayout al = accum_layout(L);
+  const AccumLayout al = accum_layout(L, sys.ld);
   const int chunk = points_separate ? kAccChunkHot : kAccChunk;
   const dim3 grid((unsigned)((a.n_obs + 4 * chunk - 1) / (4 * chunk)));
   by_flag(det_scale != nullptr, [&](auto det) {
     constexpr bool DET = decltype(det)::value;
     if (points_separate)      // only the pose / rig-pose entries are left
       by_flag(L.rig_in_state != 0, [&](auto rig) {
-        hipLaunchKernelGGL((k_accumulate_poses<DET, decltype(rig)::value>), grid, dim3(256), 0, s, a, al, a.rec_doubles, flags, a.jrec, t, det_scale);
+        hipLaunchKernelGGL((k_accumulate_poses<DET, decltype(rig)::value>), grid, dim3(256), 0, s, a, al, a.rec_doubles, out.flags, a.jrec, sys.t, det_scale);
       });
     else
-      hipLaunchKernelGGL(k_accumulate<DET>, grid, dim3(256), 0, s, a, al, a.rec_doubles, flags, a.jrec, cells, pair_tables, pair_counts, t, det_scale);
+      hipLaunchKernelGGL(k_accumulate<DET>, grid, dim3(256), 0, s, a, al, a.rec_doubles, out.flags, a.jrec, out.cells, cell.pair_tables, cell.pair_counts, sys.t, det_scale);
   });
   CBA_HIP(hipGetLastError());
   return CBA_OK;
@@ -1155,11 +1151,11 @@ __global__ void k_det_scale(const unsigned long long* __restrict__ bits, int64_t
     scale[i] = ldexp(1.0, 62 - e);                              // bound * scale < 2^62
   }
 }
-int launch_det_scale(const PassArgs& a, const uint8_t* flags, DevBuf<unsigned long long>& bits, double* scale, hipStream_t s) {
-  CBA_TRY(bits.zero_async(2, s));
+int launch_det_scale(const PassArgs& a, const PassOutputs& out, DetMode& det, hipStream_t s) {
+  CBA_TRY(det.bits.zero_async(2, s));
   if (a.n_obs > 0)      // (every double of a record counts: the unused tails of mixed-model problems are zero)
-    hipLaunchKernelGGL(k_det_bound, dim3(1024), dim3(256), 0, s, a.n_obs, a.rec_doubles, a.rec_doubles, flags, a.jrec, bits);
-  hipLaunchKernelGGL(k_det_scale, dim3(1), dim3(1), 0, s, bits, a.n_obs, scale);
+    hipLaunchKernelGGL(k_det_bound, dim3(1024), dim3(256), 0, s, a.n_obs, a.rec_doubles, a.rec_doubles, out.flags, a.jrec, det.bits);
+  hipLaunchKernelGGL(k_det_scale, dim3(1), dim3(1), 0, s, det.bits, a.n_obs, det.scale);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

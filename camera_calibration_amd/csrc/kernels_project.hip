@@ -282,22 +282,25 @@ __global__ void __launch_bounds__(256) k_base_project_slow(PassArgs a, double* _
 
 // Main launch (one lane per observation, stragglers deferred) followed by the straggler launch on `s_slow` (the same stream
 // in a cost pass; the Jacobian pass passes its side stream and orders it with `ev_main_done`).
-int launch_base_project(const PassArgs& a, int model_mask, double* cost_vec, double* pixels, uint8_t* flags, int* defer_list,
-                        DevBuf<int>& defer_count, int defer_cap, uint8_t* defer_skip, int outer_cap, const uint8_t* fd_slow, hipStream_t s) {
+int launch_base_project(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, StragglerSplit& slow, bool use_fd_slow,
+                        hipStream_t s) {
   if (a.n_obs == 0) return CBA_OK;
-  CBA_TRY(defer_count.zero_async(1, s));
+  CBA_TRY(slow.count.zero_async(1, s));
   dim3 grid((unsigned)((a.n_obs + 255) / 256)), block(256);
-  if (model_mask & 1) hipLaunchKernelGGL(k_base_project<kCentral>, grid, block, 0, s, a, cost_vec, pixels, flags, defer_list, defer_count, defer_cap, defer_skip, outer_cap, fd_slow);
-  if (model_mask & 2) hipLaunchKernelGGL(k_base_project<kNoncentral>, grid, block, 0, s, a, cost_vec, pixels, flags, defer_list, defer_count, defer_cap, defer_skip, outer_cap, fd_slow);
+  double* cost_vec = test_cost ? out.cost_test : out.cost_ref;
+  const uint8_t* fd_slow = use_fd_slow ? (const uint8_t*)slow.fd_slow : nullptr;
+  if (model_mask & 1) hipLaunchKernelGGL(k_base_project<kCentral>, grid, block, 0, s, a, cost_vec, out.pixels, out.flags, slow.list, slow.count, slow.cap, slow.skip, slow.threshold, fd_slow);
+  if (model_mask & 2) hipLaunchKernelGGL(k_base_project<kNoncentral>, grid, block, 0, s, a, cost_vec, out.pixels, out.flags, slow.list, slow.count, slow.cap, slow.skip, slow.threshold, fd_slow);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
 // `a.obs_list / obs_count / obs_list_cap` = the straggler list filled by launch_base_project
-int launch_base_project_slow(const PassArgs& a, int model_mask, double* cost_vec, double* pixels, uint8_t* flags, hipStream_t s) {
+int launch_base_project_slow(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, hipStream_t s) {
   if (a.n_obs == 0) return CBA_OK;
+  double* cost_vec = test_cost ? out.cost_test : out.cost_ref;
   dim3 grid((unsigned)(((int64_t)a.obs_list_cap * 16 + 255) / 256)), block(256);
-  if (model_mask & 1) hipLaunchKernelGGL(k_base_project_slow<kCentral>, grid, block, 0, s, a, cost_vec, pixels, flags);
-  if (model_mask & 2) hipLaunchKernelGGL(k_base_project_slow<kNoncentral>, grid, block, 0, s, a, cost_vec, pixels, flags);
+  if (model_mask & 1) hipLaunchKernelGGL(k_base_project_slow<kCentral>, grid, block, 0, s, a, cost_vec, out.pixels, out.flags);
+  if (model_mask & 2) hipLaunchKernelGGL(k_base_project_slow<kNoncentral>, grid, block, 0, s, a, cost_vec, out.pixels, out.flags);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

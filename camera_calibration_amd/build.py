@@ -9,9 +9,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcalib_ba_hip.so")
-SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip", "cba_report.hip", "cba_compare.hip",
-           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip"]
+SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip", "cba_report.hip", "cba_compare.hip", "cba_undistort.hip",
+           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "kernels_undistort.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip"]
 HEADERS = ["cba_internal.h", "hip_buf.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "block_device.hip.h", "localize_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
+# public headers besides cba.h that a unit includes (cba_undistort.h: cba_undistort.hip)
+PUBLIC_HEADERS = [os.path.join("..", "..", "include", "cba_undistort.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]  # keep MFMA accumulators in VGPRs: no AGPR<->VGPR copies in the K loop
 
@@ -37,7 +39,7 @@ def needs_build() -> bool:
     if built_with != _extra_flags():            # a library tuned by a leftover CBA_BUILD_EXTRA_FLAGS is never reused silently
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS + PUBLIC_HEADERS]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -70,6 +72,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     check_no_scratch(os.path.join(CSRC, "kernels_localize.o"), NO_SCRATCH_LOCALIZE)
     check_no_scratch(os.path.join(CSRC, "kernels_parametric.o"), NO_SCRATCH_PARAMETRIC)
     check_no_scratch(os.path.join(CSRC, "kernels_localize_images.o"), NO_SCRATCH_LOCALIZE_IMAGES)
+    check_no_scratch(os.path.join(CSRC, "kernels_undistort.o"), NO_SCRATCH_UNDISTORT)
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
     with open(FLAGS_STAMP, "w") as f:
         f.write(_extra_flags())
@@ -130,6 +133,10 @@ NO_SCRATCH_LOCALIZE_IMAGES = ("k_localize_images", "k_localize_bearings")
 # the passes of the thin-prism fisheye fit call one un-projection that is not inlined: its twelve parameters and a lane's row of H
 # stay in registers
 NO_SCRATCH_PARAMETRIC = ("k_parametric_jacobian", "k_parametric_cost", "k_parametric_unproject")
+# the remap is a gather of a few bytes per lane; the map pass inlines its one projection call site (both of its launches are that one
+# kernel) instead of paying the 80 bytes of scratch per lane a call costs k_compare_pass: neither may spill
+# 
+NO_SCRATCH_UNDISTORT = ("k_remap_u8ILi1E", "k_remap_u8ILi3E", "k_undistort_pass")
 
 
 def check_no_scratch(obj: str, kernels) -> int:

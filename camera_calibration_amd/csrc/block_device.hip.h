@@ -1,6 +1,7 @@
 // Workgroup- and wavefront-level device idioms that more than one kernel unit uses: the fixed-order block reduction and the fold of
 // its block partials (kernels_update.hip, kernels_compare.hip, kernels_report.hip, kernels_fit.hip, kernels_linalg.hip), the
-// wave-aggregated list append and the reference's double -> integer conversion (kernels_report.hip, kernels_compare.hip).
+// wave-aggregated list append (kernels_report.hip, kernels_compare.hip, kernels_undistort.hip) and the reference's double -> integer
+// conversion (kernels_report.hip, kernels_compare.hip).
 // What belongs here: an idiom with two or more users whose ORDER of operations is a promise (run-to-run identical sums, list slots
 // per wavefront) and must therefore have one definition.  Per-observation helpers are obs_device.hip.h's, camera-model expressions
 // model.hip.h's; a helper with one user stays in that user's unit.

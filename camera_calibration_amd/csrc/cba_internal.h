@@ -314,6 +314,35 @@ struct CompareColorArgs {
 static_assert(std::is_trivially_copyable_v<CompareColorArgs>);
 int launch_compare_colors(const CompareColorArgs& c, hipStream_t s);
 
+// ---- kernels_undistort.hip (undistortion map of a central-generic model and the bilinear remap that applies it) ----
+// Per pixel (u, v) of the W x H pinhole image: Project(R * normalize(((u + 0.5) - cx) / fx, ((v + 0.5) - cy) / fy, 1)).  source_pixels
+// (2 W H doubles, NaN where the projection fails), ok (W H bytes) and map_xy (2 W H floats = (float)(source pixel - 0.5), NaN where
+// not ok) may each be null; list: W * H ints, *list_count zeroed by the caller.
+struct UndistortArgs {
+  const CamDev* cam;
+  double R[9];                 // row-major source_r_target
+  double fx, fy, cx, cy;
+  double scale_x, scale_y;     // source width / W, source height / H (start 1)
+  int W, H;
+  int init_mode;               // 0 = centre of the calibrated area, 1 = the scaled target pixel centre clamped into it
+  int max_outer;               // outer iterations of the first launch (100 = complete, 0 = every pixel is listed)
+  double* source_pixels; uint8_t* ok; float* map_xy;
+  int* list; int* list_count;
+};
+static_assert(std::is_trivially_copyable_v<UndistortArgs>);
+int launch_undistort_pass(const UndistortArgs& a, hipStream_t s);
+// the same kernel over the first n_list entries of a.list, 100 outer iterations
+int launch_undistort_second(const UndistortArgs& a, int n_list, hipStream_t s);
+// n images of src_w x src_h x channels bytes -> n images of W x H x channels bytes through map (2 W H floats, pixel-centre
+// convention); the arithmetic is include/cba.h's (cba_remap_apply)
+struct RemapArgs {
+  const float* map; const uint8_t* src; uint8_t* dst;
+  int W, H, src_w, src_h, n;
+  uint8_t fill;
+};
+static_assert(std::is_trivially_copyable_v<RemapArgs>);
+int launch_remap_u8(const RemapArgs& a, int channels, hipStream_t s);
+
 // ---- kernels_parametric.hip (thin-prism fisheye model and its fit to a dense direction image, APP/models/parametric.cc) ----
 struct ParVec { double v[12]; };                       // fx fy cx cy k1 k2 k3 k4 p1 p2 sx1 sy1
 struct ParDirection { double x, y, z; int ok; };

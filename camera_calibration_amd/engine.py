@@ -101,6 +101,11 @@ class CbaCompareStats(C.Structure):
 INITIAL_ESTIMATE_CENTER, INITIAL_ESTIMATE_PIXEL = 0, 1
 
 
+class CbaUndistortOptions(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("rotation", C.c_double * 9), ("initial_estimate", C.c_int32), ("straggler_threshold", C.c_int32)]
+
+
 class CbaLocalizationOptions(C.Structure):
     _fields_ = [("n_trials", C.c_int64), ("first_trial", C.c_int64), ("seed", C.c_uint64), ("min_distance", C.c_double),
                 ("max_distance", C.c_double), ("point_count", C.c_int32), ("max_candidates", C.c_int32), ("max_iterations", C.c_int32),
@@ -225,6 +230,16 @@ PROTOTYPES = {
     "cba_kernel_stats": (_I, [_VP, _I32, _D, _D, _D, _I32P]),
 }
 EXPORTED_SYMBOLS = list(PROTOTYPES)
+# The same table for include/cba_undistort.h (tests/test_undistort_header.py checks it against that header)
+UNDISTORT_PROTOTYPES = {
+    "cba_model_undistortion_map": (_I, [_VP, C.POINTER(CbaUndistortOptions), _D, _U8, _F32P, _I64P]),
+    "cba_remap_create": (_I, [_VP, C.POINTER(CbaUndistortOptions), C.POINTER(_VP)]),
+    "cba_remap_create_from_map": (_I, [_I32, _I32, _F32P, _I32, C.POINTER(_VP)]),
+    "cba_remap_destroy": (None, [_VP]),
+    "cba_remap_get_map": (_I, [_VP, _F32P]),
+    "cba_remap_apply": (_I, [_VP, _I32, _I32, _I32, _I32, _VP, _VP, C.c_uint8]),
+    "cba_remap_apply_device": (_I, [_VP, _I32, _I32, _I32, _I32, _VP, _VP, C.c_uint8, _VP]),
+}
 
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
 DUMP_BLOCK_DIAG_H, DUMP_BLOCK_DIAG_B, DUMP_OFF_DIAG_H, DUMP_DENSE_H, DUMP_DENSE_B, DUMP_X = 5, 6, 7, 8, 9, 10
@@ -257,7 +272,7 @@ def load() -> C.CDLL:
         raise EngineError(f"{LIB_PATH} is missing -- run `python -c 'import __graft_entry__ as g; g.build()'`; "
                           "the engine has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **UNDISTORT_PROTOTYPES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -673,8 +688,30 @@ class DeviceModel:
                "cba_model_direction_moments")
         return M, int(n.value)
 
+    # -- undistortion ------------------------------------------------------------------------------
+    def undistortion_map(self, pinhole: "Pinhole", rotation: Optional[np.ndarray] = None, initial_estimate: int = INITIAL_ESTIMATE_CENTER,
+                         straggler_threshold: int = 0, want_source_pixels: bool = True, want_ok: bool = True, want_map: bool = True) -> dict:
+        """cba_model_undistortion_map: source_pixels (H, W, 2) fp64 (pixel-corner convention, NaN where the projection fails), ok (H, W)
+        bool, map_xy (H, W, 2) float32 (pixel-centre convention), n_second_launch; H, W = the pinhole image."""
+        o = undistort_options(pinhole, rotation, initial_estimate, straggler_threshold)
+        H, W = int(pinhole.height), int(pinhole.width)
+        shape = (max(H, 0), max(W, 0))
+        px = np.zeros(shape + (2,)) if want_source_pixels else None
+        ok = np.zeros(shape, dtype=np.uint8) if want_ok else None
+        mp = np.zeros(shape + (2,), dtype=np.float32) if want_map else None
+        n2 = C.c_int64(0)
+        _check(self.L.cba_model_undistortion_map(self._h, C.byref(o), _dp(px) if px is not None else None,
+                                                 ok.ctypes.data_as(_U8) if ok is not None else None,
+                                                 mp.ctypes.data_as(_F32P) if mp is not None else None, C.byref(n2)), "cba_model_undistortion_map")
+        res = dict(n_second_launch=int(n2.value))
+        if px is not None:
+            res["source_pixels"] = px
+        if ok is not None:
+            res["ok"] = ok.astype(bool)
+        if mp is not None:
+            res["map_xy"] = mp
+        return res
 
-    # -- localization accuracy test ----------------------------------------------------------------
     def localization_accuracy(self, compared: "DeviceModel", n_trials: int = 0, first_trial: int = 0, point_count: int = 0,
                               min_distance: float = 0.0, max_distance: float = 0.0, seed: int = 0, max_candidates: int = 0,
                               max_iterations: int = 0, want_trials: bool = True, want_samples: bool = False) -> dict:
@@ -742,6 +779,105 @@ class DeviceModel:
                     setattr(out, name, res[name].ctypes.data)
         _check(L.cba_model_localize_images(C.byref(inp), C.byref(o), C.byref(out)), "cba_model_localize_images")
         return res
+
+
+class Pinhole:
+    """The target of an undistortion: image size and fx, fy, cx, cy in the "pixel corner" convention."""
+
+    def __init__(self, width: int, height: int, fx: float, fy: float, cx: float, cy: float):
+        self.width, self.height = int(width), int(height)
+        self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
+
+    def __repr__(self):
+        return f"Pinhole({self.width}, {self.height}, {self.fx!r}, {self.fy!r}, {self.cx!r}, {self.cy!r})"
+
+
+def undistort_options(pinhole: Pinhole, rotation: Optional[np.ndarray] = None, initial_estimate: int = INITIAL_ESTIMATE_CENTER,
+                      straggler_threshold: int = 0) -> CbaUndistortOptions:
+    o = CbaUndistortOptions()
+    o.width, o.height = int(pinhole.width), int(pinhole.height)
+    o.fx, o.fy, o.cx, o.cy = float(pinhole.fx), float(pinhole.fy), float(pinhole.cx), float(pinhole.cy)
+    o.rotation[:] = list(np.asarray(np.eye(3) if rotation is None else rotation, dtype=np.float64).reshape(9))
+    o.initial_estimate, o.straggler_threshold = int(initial_estimate), int(straggler_threshold)
+    return o
+
+
+class Remap:
+    """cba_remap: a device-resident float map (H, W, 2; pixel-centre convention, NaN = no source) and the bilinear remap of uint8
+    images through it.  Build it from a model (``Remap.from_model``: the map never leaves the device) or from an explicit map."""
+
+    def __init__(self, map_xy: np.ndarray, device: int = 0):
+        self.L = load()
+        m = np.ascontiguousarray(map_xy, dtype=np.float32)
+        if m.ndim != 3 or m.shape[2] != 2:
+            raise ValueError("Remap: the map is (H, W, 2)")
+        self.height, self.width = int(m.shape[0]), int(m.shape[1])
+        self._h = C.c_void_p()
+        _check(self.L.cba_remap_create_from_map(self.width, self.height, m.ctypes.data_as(_F32P), int(device), C.byref(self._h)),
+               "cba_remap_create_from_map")
+
+    @classmethod
+    def from_model(cls, model: "DeviceModel", pinhole: Pinhole, rotation: Optional[np.ndarray] = None,
+                   initial_estimate: int = INITIAL_ESTIMATE_CENTER, straggler_threshold: int = 0) -> "Remap":
+        self = cls.__new__(cls)
+        self.L = load()
+        self.height, self.width = int(pinhole.height), int(pinhole.width)
+        self._h = C.c_void_p()
+        o = undistort_options(pinhole, rotation, initial_estimate, straggler_threshold)
+        _check(self.L.cba_remap_create(model._h, C.byref(o), C.byref(self._h)), "cba_remap_create")
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.cba_remap_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def get_map(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width, 2), dtype=np.float32)
+        _check(self.L.cba_remap_get_map(self._h, out.ctypes.data_as(_F32P)), "cba_remap_get_map")
+        return out
+
+    @staticmethod
+    def _layout(shape):
+        """(n, src_h, src_w, channels, batched) of an (H, W), (H, W, 3), (N, H, W, 1) or (N, H, W, 3) image array"""
+        if len(shape) == 2:
+            return 1, shape[0], shape[1], 1, False
+        if len(shape) == 3 and shape[2] == 3:
+            return 1, shape[0], shape[1], 3, False
+        if len(shape) == 4:
+            return shape[0], shape[1], shape[2], shape[3], True
+        raise ValueError("images: (H, W), (H, W, 3) or a batch (N, H, W, C)")
+
+    def _out_shape(self, n, ch, batched, squeeze):
+        shape = (self.height, self.width) if squeeze else (self.height, self.width, ch)
+        return (n,) + shape if batched else shape
+
+    def apply(self, images, fill: int = 0):
+        """A numpy uint8 array goes through cba_remap_apply and comes back as one; a torch uint8 tensor on the handle's device goes
+        through cba_remap_apply_device on torch's current stream and comes back as a tensor (no host copy, no synchronisation)."""
+        if isinstance(images, np.ndarray):
+            src = np.ascontiguousarray(images)
+            if src.dtype != np.uint8:
+                raise ValueError("images: uint8")
+            n, sh, sw, ch, batched = self._layout(src.shape)
+            dst = np.zeros(self._out_shape(n, ch, batched, src.ndim == 2), dtype=np.uint8)
+            _check(self.L.cba_remap_apply(self._h, n, sw, sh, ch, src.ctypes.data, dst.ctypes.data, int(fill)), "cba_remap_apply")
+            return dst
+        import torch
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or not images.is_cuda:
+            raise ValueError("images: a numpy uint8 array or a torch uint8 tensor on the GPU")
+        src = images.contiguous()
+        n, sh, sw, ch, batched = self._layout(tuple(src.shape))
+        dst = torch.empty(self._out_shape(n, ch, batched, src.dim() == 2), dtype=torch.uint8, device=src.device)
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+        _check(self.L.cba_remap_apply_device(self._h, n, sw, sh, ch, src.data_ptr(), dst.data_ptr(), int(fill), stream), "cba_remap_apply_device")
+        return dst
 
 
 def render_nearest_feature_image(width: int, height: int, site_xy_quarter_px: np.ndarray, site_rgb: np.ndarray, device: int = 0,

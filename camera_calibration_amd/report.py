@@ -174,6 +174,70 @@ def write_png(path: str, image: np.ndarray) -> None:
                 + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
+def read_png(path: str) -> np.ndarray:
+    """8-bit grey or RGB, non-interlaced PNG -> (H, W) or (H, W, 3) uint8; the five filter types (PNG specification, section 9).
+    Anything else (16 bits, a palette, an alpha channel, Adam7) is refused with a ValueError that says what was found."""
+    raw = open(path, "rb").read()
+    if raw[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG file")
+    pos, idat, head = 8, [], None
+    while pos + 12 <= len(raw):
+        n, tag = struct.unpack(">I", raw[pos:pos + 4])[0], raw[pos + 4:pos + 8]
+        data = raw[pos + 8:pos + 8 + n]
+        if len(data) != n:
+            raise ValueError(f"{path}: truncated {tag!r} chunk")
+        if tag == b"IHDR":
+            head = struct.unpack(">IIBBBBB", data)
+        elif tag == b"IDAT":
+            idat.append(data)
+        elif tag == b"IEND":
+            break
+        pos += 12 + n
+    if head is None:
+        raise ValueError(f"{path}: no IHDR chunk")
+    w, h, depth, colour, compression, filter_method, interlace = head
+    if depth != 8 or colour not in (0, 2):
+        raise ValueError(f"{path}: only 8-bit grey and RGB PNGs are read (bit depth {depth}, colour type {colour})")
+    if interlace != 0 or compression != 0 or filter_method != 0:
+        raise ValueError(f"{path}: only non-interlaced PNGs are read (interlace method {interlace})")
+    if w < 1 or h < 1:
+        raise ValueError(f"{path}: empty image")
+    bpp = 3 if colour == 2 else 1
+    stride = w * bpp
+    data = zlib.decompress(b"".join(idat))
+    if len(data) != h * (1 + stride):
+        raise ValueError(f"{path}: {len(data)} bytes of image data, expected {h * (1 + stride)}")
+    rows = np.frombuffer(data, dtype=np.uint8).reshape(h, 1 + stride)
+    out = np.zeros((h, stride), dtype=np.uint8)
+    zero = np.zeros(stride, dtype=np.uint8)
+    for y in range(h):
+        ft, line = int(rows[y, 0]), rows[y, 1:]
+        up = out[y - 1] if y else zero
+        if ft == 0:
+            out[y] = line
+        elif ft == 2:                                    # Up
+            out[y] = line + up
+        elif ft == 1:                                    # Sub: a running sum per channel
+            out[y] = np.cumsum(line.reshape(w, bpp), axis=0, dtype=np.uint8).reshape(stride)
+        elif ft in (3, 4):                               # Average, Paeth: each byte needs its reconstructed left neighbour
+            cur, upi = [0] * stride, [int(v) for v in up]
+            for i, v in enumerate(line.tolist()):
+                a = cur[i - bpp] if i >= bpp else 0
+                b = upi[i]
+                if ft == 3:
+                    pred = (a + b) >> 1
+                else:
+                    c = upi[i - bpp] if i >= bpp else 0
+                    p = a + b - c
+                    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+                    pred = a if pa <= pb and pa <= pc else (b if pb <= pc else c)
+                cur[i] = (v + pred) & 0xFF
+            out[y] = cur
+        else:
+            raise ValueError(f"{path}: unknown filter type {ft} in row {y}")
+    return out.reshape((h, w, 3) if bpp == 3 else (h, w))
+
+
 def compute_biasedness(cam: Camera, errors: np.ndarray, features: np.ndarray, return_all: bool = False):
     """ComputeBiasedness (:219-350): median over the 50 x 50 cells of the calibrated area (those with at least 5 features) of the
     KL divergence between the cell's 8 x 8 histogram of mean-normalised errors and a unit Gaussian.  NaN without such a cell (the

@@ -9,11 +9,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcalib_ba_hip.so")
-SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip", "cba_report.hip", "cba_compare.hip", "cba_undistort.hip",
-           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "kernels_undistort.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip"]
+SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip", "cba_report.hip", "cba_compare.hip", "cba_undistort.hip", "cba_features.hip",
+           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "kernels_undistort.hip", "kernels_features.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip"]
 HEADERS = ["cba_internal.h", "hip_buf.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "block_device.hip.h", "localize_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
-# public headers besides cba.h that a unit includes (cba_undistort.h: cba_undistort.hip)
-PUBLIC_HEADERS = [os.path.join("..", "..", "include", "cba_undistort.h")]
+# public headers besides cba.h that a unit includes (cba_undistort.h: cba_undistort.hip; cba_features.h: cba_internal.h)
+PUBLIC_HEADERS = [os.path.join("..", "..", "include", "cba_undistort.h"), os.path.join("..", "..", "include", "cba_features.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]  # keep MFMA accumulators in VGPRs: no AGPR<->VGPR copies in the K loop
 
@@ -73,6 +73,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     check_no_scratch(os.path.join(CSRC, "kernels_parametric.o"), NO_SCRATCH_PARAMETRIC)
     check_no_scratch(os.path.join(CSRC, "kernels_localize_images.o"), NO_SCRATCH_LOCALIZE_IMAGES)
     check_no_scratch(os.path.join(CSRC, "kernels_undistort.o"), NO_SCRATCH_UNDISTORT)
+    check_no_scratch(os.path.join(CSRC, "kernels_features.o"), NO_SCRATCH_FEATURES)
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
     with open(FLAGS_STAMP, "w") as f:
         f.write(_extra_flags())
@@ -137,6 +138,9 @@ NO_SCRATCH_PARAMETRIC = ("k_parametric_jacobian", "k_parametric_cost", "k_parame
 # kernel) instead of paying the 80 bytes of scratch per lane a call costs k_compare_pass: neither may spill
 # 
 NO_SCRATCH_UNDISTORT = ("k_remap_u8ILi1E", "k_remap_u8ILi3E", "k_undistort_pass")
+# the feature refinement keeps the sums of a pass (1 + 8 + 36 fp64 accumulators per lane) and the 8 x 8 LDL^T in registers
+# (DESIGN.md section 3e); k_refine_symmetry matches both refinement types
+NO_SCRATCH_FEATURES = ("k_gradient_image", "k_refine_matching", "k_refine_symmetry")
 
 
 def check_no_scratch(obj: str, kernels) -> int:
@@ -208,12 +212,12 @@ def _check_kernel_m0(asm: str, kernel: str, obj: str) -> int:
 
 HOST_DIR = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HERE, "libcalib_ba_host.so")
-HOST_SOURCES = ["joint_optimization_hip.cc", "calibration_report_hip.cc", "calibration_io.cc", "central_generic_fit_hip.cc", "calibration_hip.cc", "fitting_report_hip.cc", "localization_accuracy_hip.cc", "image_localization_hip.cc"]
+HOST_SOURCES = ["joint_optimization_hip.cc", "calibration_report_hip.cc", "calibration_io.cc", "central_generic_fit_hip.cc", "calibration_hip.cc", "fitting_report_hip.cc", "localization_accuracy_hip.cc", "image_localization_hip.cc", "feature_refinement_hip.cc"]
 # test scaffolding (extern "C" entry points that build Dataset / BAState objects from packed arrays for the Python tests):
 # its own library, NOT part of the product library
 HOST_TEST_LIB = os.path.join(HERE, "libcalib_ba_host_test.so")
-HOST_TEST_SOURCES = ["host_test_shim.cc"]
-HOST_HEADERS = ["vis_types.h", "camera_model.h", "dataset.h", "joint_optimization.h", "fitting_report.h", "localization_accuracy.h", "image_localization.h"]
+HOST_TEST_SOURCES = ["host_test_shim.cc", "feature_refinement_test_shim.cc"]
+HOST_HEADERS = ["vis_types.h", "camera_model.h", "dataset.h", "joint_optimization.h", "fitting_report.h", "localization_accuracy.h", "image_localization.h", "feature_refinement.h"]
 
 
 def build_host(force: bool = False) -> str:

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/cba.h"
+#include "../../include/cba_features.h"
 #include "gridfirst_plan.h"
 #include "hip_buf.h"
 #include "model.hip.h"
@@ -342,6 +343,31 @@ struct RemapArgs {
 };
 static_assert(std::is_trivially_copyable_v<RemapArgs>);
 int launch_remap_u8(const RemapArgs& a, int channels, hipStream_t s);
+
+// ---- kernels_features.hip (refinement of star-pattern feature positions, include/cba_features.h) ----
+// n features, one workgroup each.  pattern_tr_pixel: the inverses of pixel_tr_pattern (9 n floats each, row-major); rendered:
+// n * (n_samples / 8) floats of working memory; matched / out_positions 2 n, final_cost / status n.
+struct FeatureArgs {
+  const uint8_t* image; const float2* gradient; int W, H;
+  int window, refinement_type, n_samples, num_star_segments, n;
+  const float2* samples;
+  const float* positions; const float* pattern_tr_pixel; const float* pixel_tr_pattern;
+  float* rendered;
+  float* matched; float* out_positions; float* final_cost; int* status;
+};
+static_assert(std::is_trivially_copyable_v<FeatureArgs>);
+int launch_gradient_image(const uint8_t* img, float2* grad, int W, int H, hipStream_t s);
+// k_refine_matching, then k_refine_symmetry of the refinement type, on s
+int launch_refine_features(const FeatureArgs& a, hipStream_t s);
+// one pass of feature 0 of the arguments (cba_feature_refiner_debug_pass); records of invalid samples are not written
+struct FeatureDebugArgs {
+  int stage, with_jacobian, has_state;
+  float state[8];
+  uint8_t* valid; float* residual; float* jacobian;      // each may be null
+  double* sums; float* state_out; int* pass_ok;           // 45, 8, 1
+};
+static_assert(std::is_trivially_copyable_v<FeatureDebugArgs>);
+int launch_feature_debug_pass(const FeatureArgs& a, const FeatureDebugArgs& d, hipStream_t s);
 
 // ---- kernels_parametric.hip (thin-prism fisheye model and its fit to a dense direction image, APP/models/parametric.cc) ----
 struct ParVec { double v[12]; };                       // fx fy cx cy k1 k2 k3 k4 p1 p2 sx1 sy1

@@ -68,12 +68,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if failed:
         raise RuntimeError("hipcc compilation failed")
     check_tail_m0(os.path.join(CSRC, "kernels_ldlt.o"))
-    check_no_scratch(os.path.join(CSRC, "kernels_report.o"), NO_SCRATCH_KERNELS)
-    check_no_scratch(os.path.join(CSRC, "kernels_localize.o"), NO_SCRATCH_LOCALIZE)
-    check_no_scratch(os.path.join(CSRC, "kernels_parametric.o"), NO_SCRATCH_PARAMETRIC)
-    check_no_scratch(os.path.join(CSRC, "kernels_localize_images.o"), NO_SCRATCH_LOCALIZE_IMAGES)
-    check_no_scratch(os.path.join(CSRC, "kernels_undistort.o"), NO_SCRATCH_UNDISTORT)
-    check_no_scratch(os.path.join(CSRC, "kernels_features.o"), NO_SCRATCH_FEATURES)
+    for obj, kernels in NO_SCRATCH.items():
+        check_no_scratch(os.path.join(CSRC, obj), kernels)
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs])
     with open(FLAGS_STAMP, "w") as f:
         f.write(_extra_flags())
@@ -125,22 +121,26 @@ def kernel_resources(obj: str) -> dict:
     return out
 
 
-# kernels of the report that must keep their polygon / patch data out of scratch memory
-NO_SCRATCH_KERNELS = ("k_direction_image", "k_nearest_site", "k_clip_cells")
-# the localization accuracy test keeps its 28 fp64 sums, the 3 x 6 Jacobian and the 6 x 6 factor in registers
-NO_SCRATCH_LOCALIZE = ("k_localize",)
-# the localization of images keeps the same sums, and a hypothesis' quartic, depths and pose, in registers
-NO_SCRATCH_LOCALIZE_IMAGES = ("k_localize_images", "k_localize_bearings")
-# the passes of the thin-prism fisheye fit call one un-projection that is not inlined: its twelve parameters and a lane's row of H
-# stay in registers
-NO_SCRATCH_PARAMETRIC = ("k_parametric_jacobian", "k_parametric_cost", "k_parametric_unproject")
-# the remap is a gather of a few bytes per lane; the map pass inlines its one projection call site (both of its launches are that one
-# kernel) instead of paying the 80 bytes of scratch per lane a call costs k_compare_pass: neither may spill
-# 
-NO_SCRATCH_UNDISTORT = ("k_remap_u8ILi1E", "k_remap_u8ILi3E", "k_undistort_pass")
-# the feature refinement keeps the sums of a pass (1 + 8 + 36 fp64 accumulators per lane) and the 8 x 8 LDL^T in registers
-# (DESIGN.md section 3e); k_refine_symmetry matches both refinement types
-NO_SCRATCH_FEATURES = ("k_gradient_image", "k_refine_matching", "k_refine_symmetry")
+# object -> kernels (substrings of the mangled names) that must not use scratch memory
+NO_SCRATCH = {
+    # the report keeps its polygon / patch data out of scratch memory
+    "kernels_report.o": ("k_direction_image", "k_nearest_site", "k_clip_cells"),
+    # the localization accuracy test keeps its 28 fp64 sums, the 3 x 6 Jacobian and the 6 x 6 factor in registers
+    "kernels_localize.o": ("k_localize",),
+    # the localization of images keeps the same sums, and a hypothesis' quartic, depths and pose, in registers
+    "kernels_localize_images.o": ("k_localize_images", "k_localize_bearings"),
+    # the passes of the thin-prism fisheye fit call one un-projection that is not inlined: its twelve parameters and a lane's row of H
+    # stay in registers
+    "kernels_parametric.o": ("k_parametric_jacobian", "k_parametric_cost", "k_parametric_unproject"),
+    # both launches of the comparison's per-pixel pass are one kernel that inlines its one projection call site: it pays no call
+    # frame and must not spill
+    "kernels_compare.o": ("k_compare_pass",),
+    # the remap is a gather of a few bytes per lane; the map pass has the shape of k_compare_pass
+    "kernels_undistort.o": ("k_remap_u8ILi1E", "k_remap_u8ILi3E", "k_undistort_pass"),
+    # the feature refinement keeps the sums of a pass (1 + 8 + 36 fp64 accumulators per lane) and the 8 x 8 LDL^T in registers
+    # (DESIGN.md section 3e); k_refine_symmetry matches both refinement types
+    "kernels_features.o": ("k_gradient_image", "k_refine_matching", "k_refine_symmetry"),
+}
 
 
 def check_no_scratch(obj: str, kernels) -> int:

@@ -1,10 +1,11 @@
 // Workgroup- and wavefront-level device idioms that more than one kernel unit uses: the fixed-order block reduction and the fold of
 // its block partials (kernels_update.hip, kernels_compare.hip, kernels_report.hip, kernels_fit.hip, kernels_linalg.hip), the
-// wave-aggregated list append (kernels_report.hip, kernels_compare.hip, kernels_undistort.hip) and the reference's double -> integer
-// conversion (kernels_report.hip, kernels_compare.hip).
+// wave-aggregated list append (kernels_report.hip, kernels_compare.hip, kernels_undistort.hip), the lane -> pixel mapping of the
+// lane-per-pixel kernels and the start pixel of their projections (kernels_compare.hip, kernels_undistort.hip, kernels_parametric.hip,
+// kernels_features.hip) and the reference's double -> integer conversion (kernels_report.hip, kernels_compare.hip).
 // What belongs here: an idiom with two or more users whose ORDER of operations is a promise (run-to-run identical sums, list slots
-// per wavefront) and must therefore have one definition.  Per-observation helpers are obs_device.hip.h's, camera-model expressions
-// model.hip.h's; a helper with one user stays in that user's unit.
+// per wavefront, the pixels of a wavefront) and must therefore have one definition.  Per-observation helpers are obs_device.hip.h's,
+// camera-model expressions model.hip.h's; a helper with one user stays in that user's unit.
 #pragma once
 #include "cba_internal.h"
 
@@ -57,6 +58,36 @@ __device__ __forceinline__ int wave_append(bool want, int* __restrict__ counter)
   if (lane == leader) base = atomicAdd(counter, __popcll(m));
   base = __shfl(base, leader);
   return want ? base + __popcll(m & ((1ull << lane) - 1)) : -1;
+}
+
+// The lane-per-pixel kernels: a workgroup of 256 lanes covers 32 x 8 pixels as four 8 x 8 wavefront tiles side by side.  lane_pixel
+// gives a lane its pixel and returns whether it has one: n_list < 0 is that tile mapping on pixel_tile_grid, n_list >= 0 the list
+// mapping y * W + x = list[blockIdx.x * 256 + threadIdx.x] on ceil(n_list / 256) workgroups (a pass's second launch).
+constexpr int kPixelTileW = 32, kPixelTileH = 8;
+__device__ __forceinline__ bool lane_pixel(int W, int H, const int* list, int n_list, int& x, int& y) {
+  if (n_list < 0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    x = blockIdx.x * kPixelTileW + wave * 8 + (lane & 7); y = blockIdx.y * kPixelTileH + (lane >> 3);
+    return x < W && y < H;
+  }
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int p = i < n_list ? list[i] : 0;
+  x = p % W; y = p / W;
+  return i < n_list;
+}
+__device__ __forceinline__ bool tile_pixel(int W, int H, int& x, int& y) { return lane_pixel(W, H, nullptr, -1, x, y); }
+inline dim3 pixel_tile_grid(int W, int H, int images = 1) {
+  return dim3((unsigned)((W + kPixelTileW - 1) / kPixelTileW), (unsigned)((H + kPixelTileH - 1) / kPixelTileH), (unsigned)images);
+}
+
+// Start pixel of an iterative projection: mode 0 = centre of the calibrated area (CameraModel::Project), 1 = the pixel centre
+// (cx, cy) scaled to this camera's image and clamped into the area as projection_candidate clamps its iterates (no contraction
+// is possible here: the products feed fmin)
+__device__ __forceinline__ void projection_start(const CamDev& c, int mode, double cx, double cy, double scale_x, double scale_y,
+                                                 double& px, double& py) {
+  if (mode != 1) return center_pixel(c, px, py);
+  px = fmax((double)c.min_x, fmin(cx * scale_x, c.max_x + 0.999));
+  py = fmax((double)c.min_y, fmin(cy * scale_y, c.max_y + 0.999));
 }
 
 // double -> int of the reference's x86-64 builds: truncated; what no 32-bit integer holds (NaN included) is INT_MIN.  Its

@@ -11,8 +11,6 @@ using namespace cba;
 
 namespace {
 
-constexpr int kDefaultStragglerThreshold = 8;
-
 // the device arrays of one comparison
 struct CompareBuffers {
   DevBuf<double> base_dir, fit_dir, err, reproj, partials, sums;
@@ -123,15 +121,10 @@ int cba_model_compare(cba_model* base, cba_model* fitted, const cba_compare_opti
   CBA_TRY(b.alloc(n));
   CompareArgs a = make_args(base, fitted, options->rotation, options->border_x, options->border_y, b);
   a.init_mode = options->initial_estimate;
-  const int thr = options->straggler_threshold;
-  a.max_outer = thr == 0 ? kDefaultStragglerThreshold : (thr < 0 ? 0 : std::min(thr, 100));
+  a.max_outer = straggler_max_outer(options->straggler_threshold);
   a.do_project = 1;
-  CBA_TRY(b.count.zero_async(nullptr));
-  CBA_TRY(launch_compare_pass(a, nullptr));
   int n_list = 0;
-  CBA_TRY(b.count.download(&n_list, 1));
-  if (n_list < 0 || (size_t)n_list > n) { set_error("cba_model_compare: pixel list corrupt"); return CBA_ERR_HIP; }
-  CBA_TRY(launch_compare_second(a, n_list, nullptr));
+  CBA_TRY(run_pixel_pass(a, b.count, n, "cba_model_compare", launch_compare_pass, launch_compare_second, &n_list));
   return compare_finish(options, o, stats, b, n, n_list);
 }
 
@@ -173,8 +166,7 @@ int cba_model_direction_moments(cba_model* base, cba_model* fitted, int32_t bord
   const double identity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};      // 1 * a + 0 * b + 0 * c is a: base_dir holds the unrotated directions
   CompareArgs a = make_args(base, fitted, identity, border_x, border_y, b);
   a.max_outer = 100; a.do_project = 0;
-  CBA_TRY(b.count.zero_async(nullptr));
-  CBA_TRY(launch_compare_pass(a, nullptr));
+  CBA_TRY(run_pixel_pass(a, b.count, n, "cba_model_direction_moments", launch_compare_pass));
   CBA_TRY(launch_compare_reduce((int64_t)n, b.flags, b.err, b.reproj, b.fit_dir, b.base_dir, true, b.partials, b.sums, nullptr));
   double h[kCompareSums];
   CBA_TRY(b.sums.download(h, kCompareSums));

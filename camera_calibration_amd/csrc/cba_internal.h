@@ -297,6 +297,7 @@ struct CompareArgs {
 };
 static_assert(std::is_trivially_copyable_v<CompareArgs>);
 int launch_compare_pass(const CompareArgs& a, hipStream_t s);
+// the same kernel over the first n_list entries of a.list, 100 outer iterations
 int launch_compare_second(const CompareArgs& a, int n_list, hipStream_t s);
 // slots of the reduction
 constexpr int kCmpBaseOk = 0, kCmpBothOk = 1, kCmpProjected = 2, kCmpMaxComponent = 3, kCmpMaxNorm = 4, kCmpReprojSum = 5, kCmpReprojMax = 6,

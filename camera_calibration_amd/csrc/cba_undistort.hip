@@ -1,6 +1,5 @@
 // Entry points of the C ABI (include/cba_undistort.h) behind the undistortion of a central-generic camera's images: cba_model_undistortion_map
 // and the cba_remap_* handle.  Kernels: kernels_undistort.hip.
-#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -24,7 +23,6 @@ struct cba_remap {
 
 namespace {
 
-constexpr int kDefaultStragglerThreshold = 8;      // as cba_model_compare
 constexpr int64_t kMaxPixels = (int64_t)1 << 28;
 constexpr int kMaxImages = 65535;                  // the image index is the third grid dimension
 
@@ -53,16 +51,11 @@ int build_map(const cba_model* m, const cba_undistort_options* o, double* d_sour
   a.scale_x = (double)m->cam.width / (double)o->width; a.scale_y = (double)m->cam.height / (double)o->height;
   a.W = o->width; a.H = o->height;
   a.init_mode = o->initial_estimate;
-  const int thr = o->straggler_threshold;
-  a.max_outer = thr == 0 ? kDefaultStragglerThreshold : (thr < 0 ? 0 : std::min(thr, 100));
+  a.max_outer = straggler_max_outer(o->straggler_threshold);
   a.source_pixels = d_source_pixels; a.ok = d_ok; a.map_xy = d_map;
   a.list = list; a.list_count = count;
-  CBA_TRY(count.zero_async(nullptr));
-  CBA_TRY(launch_undistort_pass(a, nullptr));
   int n_list = 0;
-  CBA_TRY(count.download(&n_list, 1));
-  if (n_list < 0 || (size_t)n_list > n) { set_error("undistortion map: pixel list corrupt"); return CBA_ERR_HIP; }
-  CBA_TRY(launch_undistort_second(a, n_list, nullptr));
+  CBA_TRY(run_pixel_pass(a, count, n, "undistortion map", launch_undistort_pass, launch_undistort_second, &n_list));
   CBA_HIP(hipStreamSynchronize(nullptr));      // list and count are released on return
   if (n_second_launch) *n_second_launch = n_list;
   return CBA_OK;

@@ -2,20 +2,22 @@
 // CentralGenericModel>, called by APP/tools/compare_calibrations.cc:39-74): the per-pixel loop (:83-125), its reductions and the
 // five images (:135-178).
 //
-//  k_compare_pass     one lane per pixel (x, y) of the fitted model's image, 8 x 8 pixels per wavefront (neighbouring pixels share
-//                     control patches and take similar iteration counts): a = Unproject_A(border + (x, y) + 0.5f), g = R a,
-//                     f = Unproject_B((x, y) + 0.5f), error = f - g, Project_B(g) from the start pixel, reprojection error =
-//                     (x + 0.5f, y + 0.5f) - pixel.  A projection that reaches the iteration cap writes nothing; its pixel index goes
-//                     to a device list (ballot, one atomic per wavefront; one slot per pixel: the list cannot overflow).
-//  k_compare_second   the complete projection (100 outer iterations) of the listed pixels, packed into full wavefronts, from the same
-//                     start and from the g the first launch stored.
+//  k_compare_pass     first launch (n_list < 0): one lane per pixel (x, y) of the fitted model's image, 8 x 8 pixels per wavefront
+//                     (neighbouring pixels share control patches and take similar iteration counts):
+//                     a = Unproject_A(border + (x, y) + 0.5f), g = R a, f = Unproject_B((x, y) + 0.5f), error = f - g, Project_B(g)
+//                     from the start pixel, reprojection error = (x + 0.5f, y + 0.5f) - pixel.  A projection that reaches the
+//                     iteration cap writes nothing more; its pixel index goes to a device list (wave_append; one slot per pixel:
+//                     the list cannot overflow).
+//                     second launch (n_list >= 0) OF THE SAME KERNEL: the complete projection (100 outer iterations) of the listed
+//                     pixels, packed into full wavefronts, from the same start, the g and the flags the first launch stored.
 //  k_compare_reduce   counts, maxima, the sum of the reprojection magnitudes and (want_moments) M = sum f a^T: a fixed assignment of
 //  (+ fold)           pixels to lanes and fixed trees (as k_center_point_sums): run-to-run identical.
 //  k_compare_colors   the five images from the per-pixel arrays and the maxima.
 //
-// Both launches project through ONE non-inlined device function (compare_project): they execute the same machine code, so a pixel's
-// result does not depend on which launch finished it (cba_internal.h records what two inlined copies of the LM loop can do to one
-// contraction).  The spline and LM arithmetic is model.hip.h's, unchanged; the control points are gathered (no LDS stage).
+// The two launches are ONE kernel with ONE inlined call site of project_point, as in k_undistort_pass: they differ in how a lane finds
+// its pixel and g and in the value of max_outer, not in a single instruction of the projection, so a pixel's result does not depend
+// on which launch finished it (cba_internal.h records what two inlined copies of the LM loop can do to one contraction).  The
+// spline and LM arithmetic is model.hip.h's, unchanged; the control points are gathered (no LDS stage).
 //
 // Per-pixel arrays: flags bit 0 = base un-projection ok, bit 1 = fitted un-projection ok, bit 2 = projected.  base_dir = g (NaN
 // without bit 0), fit_dir = f (NaN without bit 1), error = f - g with both bits, +inf with bit 0 only (:100), NaN without bit 0 (:90);
@@ -32,102 +34,66 @@
 
 namespace cba {
 
-constexpr int kCmpTileW = 32, kCmpTileH = 8;      // a workgroup: four 8 x 8 wavefront tiles side by side
-
-// start pixel of the projection into B: 0 = centre of B's calibrated area (the reference), 1 = the pixel itself, clamped into the
-// area as projection_candidate clamps its iterates
-__device__ __forceinline__ void compare_start(const CamDev& cb, int mode, int x, int y, double& px, double& py) {
-  if (mode == 1) {
-    px = fmax((double)cb.min_x, fmin(pixel_center(x), cb.max_x + 0.999));
-    py = fmax((double)cb.min_y, fmin(pixel_center(y), cb.max_y + 0.999));
-  } else {
-    center_pixel(cb, px, py);
-  }
-}
-
-struct CompareProjection { double px, py; int ok, capped; };
-// CameraModel::ProjectWithInitialEstimate on the fitted model; NOT inlined: see the header comment
-__device__ __noinline__ CompareProjection compare_project(const CamDev* __restrict__ fitted, double gx, double gy, double gz, double px,
-                                                          double py, int max_outer) {
-  const CamDev cb = *fitted;
-  const Subst none = no_subst();
-  const double g[3] = {gx, gy, gz};
-  bool capped = false;
-  CompareProjection r;
-  r.px = px; r.py = py;
-  r.ok = project_point<kCentral>(cb, none, g, r.px, r.py, nullptr, nullptr, max_outer, &capped) ? 1 : 0;
-  r.capped = capped ? 1 : 0;
-  return r;
-}
-
-__global__ void __launch_bounds__(256) k_compare_pass(CompareArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x = blockIdx.x * kCmpTileW + wave * 8 + (lane & 7), y = blockIdx.y * kCmpTileH + (lane >> 3);
-  const bool inside = x < a.W && y < a.H;
-  const double nan = quiet_nan(), inf = __longlong_as_double(0x7ff0000000000000ll);
-  const Subst none = no_subst();
+__global__ void __launch_bounds__(256) k_compare_pass(CompareArgs a, int n_list) {
+  int x, y;
+  const bool inside = lane_pixel(a.W, a.H, a.list, n_list, x, y);
   bool capped = false;
   if (inside) {
     const size_t p = (size_t)y * a.W + x;
-    double av[3], f[3], o[3], g[3] = {nan, nan, nan}, e[3] = {nan, nan, nan};
-    const CamDev ca = *a.base;
-    const bool base_ok = unproject<kCentral>(ca, none, pixel_center(a.border_x + x), pixel_center(a.border_y + y), av, o);
+    const Subst none = no_subst();
     const CamDev cb = *a.fitted;
-    const bool fit_ok = unproject<kCentral>(cb, none, pixel_center(x), pixel_center(y), f, o);
-    if (!fit_ok) f[0] = f[1] = f[2] = nan;
-    if (base_ok) {
+    const double nan = quiet_nan(), inf = __longlong_as_double(0x7ff0000000000000ll);
+    double g[3] = {nan, nan, nan};
+    int fl;
+    bool project;      // false: nothing to project from (no g, or direction moments only)
+    if (n_list < 0) {
+      double av[3], f[3], o[3], e[3] = {nan, nan, nan};
+      const CamDev ca = *a.base;
+      const bool base_ok = unproject<kCentral>(ca, none, pixel_center(a.border_x + x), pixel_center(a.border_y + y), av, o);
+      const bool fit_ok = unproject<kCentral>(cb, none, pixel_center(x), pixel_center(y), f, o);
+      if (!fit_ok) f[0] = f[1] = f[2] = nan;
+      if (base_ok) {
 #pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        g[r] = a.R[3 * r] * av[0] + a.R[3 * r + 1] * av[1] + a.R[3 * r + 2] * av[2];
-        e[r] = fit_ok ? f[r] - g[r] : inf;
+        for (int r = 0; r < 3; ++r) {
+          g[r] = a.R[3 * r] * av[0] + a.R[3 * r + 1] * av[1] + a.R[3 * r + 2] * av[2];
+          e[r] = fit_ok ? f[r] - g[r] : inf;
+        }
       }
+      fl = (base_ok ? 1 : 0) | (fit_ok ? 2 : 0);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { a.base_dir[3 * p + k] = g[k]; a.fit_dir[3 * p + k] = f[k]; a.err[3 * p + k] = e[k]; }
+      a.reproj[2 * p] = 0; a.reproj[2 * p + 1] = 0;
+      a.flags[p] = (uint8_t)fl;
+      project = base_ok && a.do_project;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g[k] = a.base_dir[3 * p + k];
+      fl = a.flags[p];
+      project = true;
     }
-    int fl = (base_ok ? 1 : 0) | (fit_ok ? 2 : 0);
-    double rx = 0, ry = 0;
-    if (base_ok && a.do_project) {
+    if (project) {
       double px, py;
-      compare_start(cb, a.init_mode, x, y, px, py);
-      const CompareProjection pr = compare_project(a.fitted, g[0], g[1], g[2], px, py, a.max_outer);
-      capped = pr.capped != 0;
-      if (pr.ok) {
-        fl |= 4;
-        rx = pixel_center(x) - pr.px; ry = pixel_center(y) - pr.py;
+      projection_start(cb, a.init_mode, pixel_center(x), pixel_center(y), 1.0, 1.0, px, py);      // the pixel itself
+      // CameraModel::ProjectWithInitialEstimate on the fitted model: the ONE call site
+      if (project_point<kCentral>(cb, none, g, px, py, nullptr, nullptr, n_list < 0 ? a.max_outer : 100, &capped)) {
+        a.reproj[2 * p] = pixel_center(x) - px; a.reproj[2 * p + 1] = pixel_center(y) - py;
+        a.flags[p] = (uint8_t)(fl | 4);
       }
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { a.base_dir[3 * p + k] = g[k]; a.fit_dir[3 * p + k] = f[k]; a.err[3 * p + k] = e[k]; }
-    a.reproj[2 * p] = rx; a.reproj[2 * p + 1] = ry;
-    a.flags[p] = (uint8_t)fl;
   }
+  // (max_outer = 100 never caps: the second launch appends nothing)
   const int slot = wave_append(capped, a.list_count);
   if (slot >= 0) a.list[slot] = y * a.W + x;
 }
 
-__global__ void __launch_bounds__(64) k_compare_second(CompareArgs a, int n_list) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= n_list) return;
-  const int p = a.list[i];
-  const int x = p % a.W, y = p / a.W;
-  const CamDev cb = *a.fitted;
-  double px, py;
-  compare_start(cb, a.init_mode, x, y, px, py);
-  const CompareProjection pr = compare_project(a.fitted, a.base_dir[3 * (size_t)p], a.base_dir[3 * (size_t)p + 1], a.base_dir[3 * (size_t)p + 2],
-                                               px, py, 100);
-  if (pr.ok) {
-    a.reproj[2 * (size_t)p] = pixel_center(x) - pr.px; a.reproj[2 * (size_t)p + 1] = pixel_center(y) - pr.py;
-    a.flags[p] = a.flags[p] | 4;
-  }
-}
-
 int launch_compare_pass(const CompareArgs& a, hipStream_t s) {
-  dim3 grid((unsigned)((a.W + kCmpTileW - 1) / kCmpTileW), (unsigned)((a.H + kCmpTileH - 1) / kCmpTileH)), block(256);
-  hipLaunchKernelGGL(k_compare_pass, grid, block, 0, s, a);
+  hipLaunchKernelGGL(k_compare_pass, pixel_tile_grid(a.W, a.H), dim3(256), 0, s, a, -1);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
 int launch_compare_second(const CompareArgs& a, int n_list, hipStream_t s) {
-  if (n_list == 0) return CBA_OK;
-  hipLaunchKernelGGL(k_compare_second, dim3((unsigned)((n_list + 63) / 64)), dim3(64), 0, s, a, n_list);
+  if (n_list <= 0) return CBA_OK;
+  hipLaunchKernelGGL(k_compare_pass, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, s, a, n_list);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

@@ -92,9 +92,8 @@ __device__ __forceinline__ void load_f2(const float2* __restrict__ img, int W, c
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_gradient_image(const uint8_t* __restrict__ img, float2* __restrict__ grad, int W, int H) {
 #pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x = blockIdx.x * 32 + wave * 8 + (lane & 7), y = blockIdx.y * 8 + (lane >> 3);
-  if (x >= W || y >= H) return;
+  int x, y;
+  if (!tile_pixel(W, H, x, y)) return;
   const int mx = max(0, x - 1), px = min(W - 1, x + 1), my = max(0, y - 1), py = min(H - 1, y + 1);
   const uint8_t* row = img + (size_t)y * W;
   float2 g;
@@ -104,8 +103,7 @@ __global__ void __launch_bounds__(256) k_gradient_image(const uint8_t* __restric
 }
 
 int launch_gradient_image(const uint8_t* img, float2* grad, int W, int H, hipStream_t s) {
-  dim3 grid((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8)), block(256);
-  hipLaunchKernelGGL(k_gradient_image, grid, block, 0, s, img, grad, W, H);
+  hipLaunchKernelGGL(k_gradient_image, pixel_tile_grid(W, H), dim3(256), 0, s, img, grad, W, H);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

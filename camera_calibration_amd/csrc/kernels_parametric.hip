@@ -6,9 +6,9 @@
 //  k_parametric_jacobian  ParametricDirectionCostFunction::Compute<true>              (APP/models/parametric.cc:81-181)
 //  k_parametric_cost      ... ::Compute<false>
 //  k_parametric_linear    the sums of FitSimpleParametricToDenseModelLinearly         (:197-319)
-// The un-projection is ONE function that is not inlined: the direction of a sample must not depend on the kernel that computed it
-// (the compare_project idiom of kernels_compare.hip).  Deviation from the reference, stated in include/cba.h: the equidistant branch
-// of Unproject (theta, sine, cosine) is evaluated in fp64, not in float.
+// The un-projection is ONE function that is not inlined (parametric_unproject_scalars): every kernel that calls it executes the same machine
+// code, so the direction of a sample does not depend on the kernel that computed it.  Deviation from the reference, stated in
+// include/cba.h: the equidistant branch of Unproject (theta, sine, cosine) is evaluated in fp64, not in float.
 #include "block_device.hip.h"
 #include "cba_internal.h"
 
@@ -336,9 +336,8 @@ __global__ void __launch_bounds__(256) k_parametric_linear(const double* __restr
 // arrays and flags of k_compare_pass (kernels_compare.hip), with the fitted model's un-projection and closed-form projection.  No
 // projection is iterative here, so nothing is listed for a second launch.
 __global__ void __launch_bounds__(256) k_compare_parametric(CompareParametricArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x = blockIdx.x * 32 + wave * 8 + (lane & 7), y = blockIdx.y * 8 + (lane >> 3);
-  if (x >= a.W || y >= a.H) return;
+  int x, y;
+  if (!tile_pixel(a.W, a.H, x, y)) return;
   const double nan = quiet_nan(), inf = __longlong_as_double(0x7ff0000000000000ll);
   const Subst none = no_subst();
   const size_t p = (size_t)y * a.W + x;
@@ -373,8 +372,7 @@ __global__ void __launch_bounds__(256) k_compare_parametric(CompareParametricArg
 }  // namespace
 
 int launch_compare_parametric(const CompareParametricArgs& a, hipStream_t s) {
-  dim3 grid((unsigned)((a.W + 31) / 32), (unsigned)((a.H + 7) / 8)), block(256);
-  hipLaunchKernelGGL(k_compare_parametric, grid, block, 0, s, a);
+  hipLaunchKernelGGL(k_compare_parametric, pixel_tile_grid(a.W, a.H), dim3(256), 0, s, a);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

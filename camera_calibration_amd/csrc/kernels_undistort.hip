@@ -13,14 +13,11 @@
 //                       neighbouring lanes gather neighbouring bytes), four tiles per workgroup, the image index in grid z.  A lane
 //                       reads its map entry as one 8-byte load and writes the C bytes of its pixel itself (no LDS transpose).
 //
-// HOW BOTH LAUNCHES EXECUTE THE SAME MACHINE CODE.  kernels_compare.hip gets there with two kernels that call one non-inlined
-// function, compare_project.  That function was neither moved to a shared header nor copied: a call costs what this unit must not
-// have.  The callee keeps 19 callee-saved VGPRs in scratch memory (80 bytes per lane: the private segment of k_compare_pass and
-// k_compare_second) and the callers are compiled for 280 VGPRs; the map pass is on build.py's no-scratch list.  Here the two
-// launches are ONE kernel with ONE inlined call site of project_point (0 bytes of scratch, 180 VGPRs): the launches differ in
-// how a lane finds its pixel and in the value of max_outer, not in a single instruction of the projection, so a pixel's result
-// does not depend on which launch finished it (cba_internal.h records what two inlined copies of the LM loop can do to one
-// contraction).  The spline and LM arithmetic is model.hip.h's, unchanged; the control points are gathered (no LDS stage).
+// HOW BOTH LAUNCHES EXECUTE THE SAME MACHINE CODE.  The two launches are ONE kernel with ONE inlined call site of project_point
+// (0 bytes of scratch: the pass is on build.py's no-scratch list), as in k_compare_pass: the launches differ in how a lane finds
+// its pixel (block_device.hip.h: lane_pixel) and in the value of max_outer, not in a single instruction of the projection, so a
+// pixel's result does not depend on which launch finished it (cba_internal.h records what two inlined copies of the LM loop can
+// do to one contraction).  The spline and LM arithmetic is model.hip.h's, unchanged; the control points are gathered (no LDS stage).
 // The ray, the start pixel and the float map entry are compiled WITHOUT contraction: every operation is one IEEE operation.
 //
 // The remap's arithmetic is a promise (include/cba_undistort.h): fp32, no contraction, so that a float32 numpy restatement reproduces
@@ -28,8 +25,6 @@
 #include "block_device.hip.h"
 
 namespace cba {
-
-constexpr int kUndTileW = 32, kUndTileH = 8;      // a workgroup: four 8 x 8 wavefront tiles side by side
 
 __device__ __forceinline__ void undistort_ray(const UndistortArgs& a, int u, int v, double (&g)[3]) {
 #pragma clang fp contract(off)
@@ -40,16 +35,10 @@ __device__ __forceinline__ void undistort_ray(const UndistortArgs& a, int u, int
   for (int r = 0; r < 3; ++r) g[r] = (a.R[3 * r] * t[0] + a.R[3 * r + 1] * t[1]) + a.R[3 * r + 2] * t[2];
 }
 
-// start pixel of the projection: 0 = centre of the calibrated area (CameraModel::Project), 1 = the target pixel centre scaled to
-// the source image, clamped into the area as compare_start clamps
+// start pixel of the projection (projection_start): with init_mode 1 the target pixel centre scaled to the source image
 __device__ __forceinline__ void undistort_start(const UndistortArgs& a, const CamDev& c, int u, int v, double& px, double& py) {
 #pragma clang fp contract(off)
-  if (a.init_mode == 1) {
-    px = fmax((double)c.min_x, fmin(((double)u + 0.5) * a.scale_x, c.max_x + 0.999));
-    py = fmax((double)c.min_y, fmin(((double)v + 0.5) * a.scale_y, c.max_y + 0.999));
-  } else {
-    center_pixel(c, px, py);
-  }
+  projection_start(c, a.init_mode, (double)u + 0.5, (double)v + 0.5, a.scale_x, a.scale_y, px, py);
 }
 
 __device__ __forceinline__ void undistort_store(const UndistortArgs& a, size_t p, bool ok, double px, double py) {
@@ -66,20 +55,9 @@ __device__ __forceinline__ void undistort_store(const UndistortArgs& a, size_t p
 }
 
 __global__ void __launch_bounds__(256) k_undistort_pass(UndistortArgs a, int n_list) {
-  int u, v, max_outer;
-  bool inside;
-  if (n_list < 0) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u = blockIdx.x * kUndTileW + wave * 8 + (lane & 7); v = blockIdx.y * kUndTileH + (lane >> 3);
-    inside = u < a.W && v < a.H;
-    max_outer = a.max_outer;
-  } else {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    inside = i < n_list;
-    const int p = inside ? a.list[i] : 0;
-    u = p % a.W; v = p / a.W;
-    max_outer = 100;
-  }
+  int u, v;
+  const bool inside = lane_pixel(a.W, a.H, a.list, n_list, u, v);
+  const int max_outer = n_list < 0 ? a.max_outer : 100;
   bool capped = false;
   if (inside) {
     double g[3], px, py;
@@ -96,8 +74,7 @@ __global__ void __launch_bounds__(256) k_undistort_pass(UndistortArgs a, int n_l
 }
 
 int launch_undistort_pass(const UndistortArgs& a, hipStream_t s) {
-  dim3 grid((unsigned)((a.W + kUndTileW - 1) / kUndTileW), (unsigned)((a.H + kUndTileH - 1) / kUndTileH)), block(256);
-  hipLaunchKernelGGL(k_undistort_pass, grid, block, 0, s, a, -1);
+  hipLaunchKernelGGL(k_undistort_pass, pixel_tile_grid(a.W, a.H), dim3(256), 0, s, a, -1);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }
@@ -122,9 +99,8 @@ __device__ __forceinline__ float remap_lerp(float a, float b, float w) {
 template <int CHANNELS>
 __global__ void __launch_bounds__(256) k_remap_u8(RemapArgs a) {
 #pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int x = blockIdx.x * kUndTileW + wave * 8 + (lane & 7), y = blockIdx.y * kUndTileH + (lane >> 3);
-  if (x >= a.W || y >= a.H) return;
+  int x, y;
+  if (!tile_pixel(a.W, a.H, x, y)) return;
   const size_t p = (size_t)y * a.W + x;
   const float2 sxy = reinterpret_cast<const float2*>(a.map)[p];
   uint8_t out[CHANNELS];
@@ -155,7 +131,7 @@ __global__ void __launch_bounds__(256) k_remap_u8(RemapArgs a) {
 }
 
 int launch_remap_u8(const RemapArgs& a, int channels, hipStream_t s) {
-  dim3 grid((unsigned)((a.W + kUndTileW - 1) / kUndTileW), (unsigned)((a.H + kUndTileH - 1) / kUndTileH), (unsigned)a.n), block(256);
+  const dim3 grid = pixel_tile_grid(a.W, a.H, a.n), block(256);
   if (channels == 1) hipLaunchKernelGGL(k_remap_u8<1>, grid, block, 0, s, a);
   else hipLaunchKernelGGL(k_remap_u8<3>, grid, block, 0, s, a);
   CBA_HIP(hipGetLastError());

@@ -10,10 +10,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcalib_ba_hip.so")
 SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip", "cba_report.hip", "cba_compare.hip", "cba_undistort.hip", "cba_features.hip",
-           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "kernels_undistort.hip", "kernels_features.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip"]
+           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "kernels_undistort.hip", "kernels_features.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip", "cba_stereo.hip", "kernels_stereo.hip"]
 HEADERS = ["cba_internal.h", "hip_buf.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "block_device.hip.h", "localize_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
-# public headers besides cba.h that a unit includes (cba_undistort.h: cba_undistort.hip; cba_features.h: cba_internal.h)
-PUBLIC_HEADERS = [os.path.join("..", "..", "include", "cba_undistort.h"), os.path.join("..", "..", "include", "cba_features.h")]
+# public headers besides cba.h that a unit includes (cba_undistort.h: cba_undistort.hip; cba_features.h: cba_internal.h;
+# cba_stereo.h: cba_stereo.hip, kernels_stereo.hip)
+PUBLIC_HEADERS = [os.path.join("..", "..", "include", "cba_undistort.h"), os.path.join("..", "..", "include", "cba_features.h"),
+                  os.path.join("..", "..", "include", "cba_stereo.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]  # keep MFMA accumulators in VGPRs: no AGPR<->VGPR copies in the K loop
 
@@ -140,6 +142,9 @@ NO_SCRATCH = {
     # the feature refinement keeps the sums of a pass (1 + 8 + 36 fp64 accumulators per lane) and the 8 x 8 LDL^T in registers
     # (DESIGN.md section 3e); k_refine_symmetry matches both refinement types
     "kernels_features.o": ("k_gradient_image", "k_refine_matching", "k_refine_symmetry"),
+    # the stereo stages keep the three sums, the normal and the plane of every hypothesis of a pixel (up to 20) in registers
+    # 
+    "kernels_stereo.o": ("k_stereo_init", "k_stereo_mutation", "k_stereo_propagation", "k_stereo_refinement", "k_stereo_cost", "k_stereo_filter"),
 }
 
 

@@ -345,6 +345,29 @@ struct RemapArgs {
 static_assert(std::is_trivially_copyable_v<RemapArgs>);
 int launch_remap_u8(const RemapArgs& a, int channels, hipStream_t s);
 
+// ---- kernels_stereo.hip (PatchMatch stereo of a calibrated two-camera rig, include/cba_stereo.h) ----
+// The lookups, images and pose of one direction and the state a launch reads (inv_depth, normal, cost) and writes (out_*: the same
+// arrays for the in-place stages, the second buffers for the propagation, the cost array alone for launch_stereo_cost).
+struct StereoArgs {
+  const float2* unprojection; const uint8_t* reference_image; const uint8_t* stereo_image; const float2* projection;
+  float M[12];                   // stereo_tr_reference, row-major 3 x 4
+  float fx, fy, cx, cy;
+  int W, H, Ws, Hs, PW, PH, r;
+  const float* inv_depth; const int8_t* normal; const float* cost;
+  float* out_inv_depth; int8_t* out_normal; float* out_cost;
+  unsigned long long seed; int pass;
+  float max_normal_2d_length, inv_min, inv_max, step_range;
+  // the filter's
+  float cost_threshold, min_cos, lr_factor_threshold;
+  const float* other_inv_depth; float* filtered;
+};
+static_assert(std::is_trivially_copyable_v<StereoArgs>);
+// stage: CBA_STEREO_INIT .. CBA_STEREO_REFINEMENT (include/cba_stereo.h), one launch over the inner region (the propagation: over
+// the image, pixels outside the inner region are copied)
+int launch_stereo_stage(const StereoArgs& a, int stage, hipStream_t s);
+int launch_stereo_cost(const StereoArgs& a, hipStream_t s);
+int launch_stereo_filter(const StereoArgs& a, hipStream_t s);
+
 // ---- kernels_features.hip (refinement of star-pattern feature positions, include/cba_features.h) ----
 // n features, one workgroup each.  pattern_tr_pixel: the inverses of pixel_tr_pattern (9 n floats each, row-major); rendered:
 // n * (n_samples / 8) floats of working memory; matched / out_positions 2 n, final_cost / status n.

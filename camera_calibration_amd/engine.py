@@ -241,6 +241,30 @@ UNDISTORT_PROTOTYPES = {
     "cba_remap_apply_device": (_I, [_VP, _I32, _I32, _I32, _I32, _VP, _VP, C.c_uint8, _VP]),
 }
 
+
+class CbaStereoOptions(C.Structure):
+    _fields_ = [("context_radius", C.c_int32), ("iterations", C.c_int32), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("max_normal_2d_length", C.c_float), ("cost_threshold", C.c_float), ("angle_threshold", C.c_float),
+                ("lr_consistency_factor_threshold", C.c_float), ("seed", C.c_uint64)]
+
+
+# The same table for include/cba_stereo.h (tests/test_stereo_cases.py checks it against that header)
+_I8P, _SOPT = C.POINTER(C.c_int8), C.POINTER(CbaStereoOptions)
+STEREO_PROTOTYPES = {
+    "cba_stereo_create": (_I, [_I32, _I32, _I32, _I32, _F32P, C.c_float, C.c_float, C.c_float, C.c_float, _I32, _I32, _F32P, _F32P, _I32,
+                               C.POINTER(_VP)]),
+    "cba_stereo_destroy": (None, [_VP]),
+    "cba_stereo_set_images": (_I, [_VP, _U8, _U8]),
+    "cba_stereo_set_pose": (_I, [_VP, _F32P]),
+    "cba_stereo_match": (_I, [_VP, _SOPT]),
+    "cba_stereo_get_state": (_I, [_VP, _F32P, _I8P, _F32P]),
+    "cba_stereo_set_state": (_I, [_VP, _F32P, _I8P, _F32P]),
+    "cba_stereo_run_stage": (_I, [_VP, _SOPT, _I32, _I32]),
+    "cba_stereo_cost": (_I, [_VP, _SOPT, _F32P, _I8P, _F32P]),
+    "cba_stereo_filter": (_I, [_VP, _SOPT, _F32P, _F32P]),
+}
+STEREO_INIT, STEREO_MUTATION, STEREO_PROPAGATION, STEREO_REFINEMENT = 0, 1, 2, 3
+
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
 DUMP_BLOCK_DIAG_H, DUMP_BLOCK_DIAG_B, DUMP_OFF_DIAG_H, DUMP_DENSE_H, DUMP_DENSE_B, DUMP_X = 5, 6, 7, 8, 9, 10
 DUMP_TEST_COST_VECTOR = 11
@@ -272,7 +296,7 @@ def load() -> C.CDLL:
         raise EngineError(f"{LIB_PATH} is missing -- run `python -c 'import __graft_entry__ as g; g.build()'`; "
                           "the engine has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **UNDISTORT_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **UNDISTORT_PROTOTYPES, **STEREO_PROTOTYPES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -878,6 +902,98 @@ class Remap:
         stream = torch.cuda.current_stream(src.device).cuda_stream
         _check(self.L.cba_remap_apply_device(self._h, n, sw, sh, ch, src.data_ptr(), dst.data_ptr(), int(fill), stream), "cba_remap_apply_device")
         return dst
+
+
+def stereo_options(context_radius: int = 10, iterations: int = 50, min_depth: float = 0.3, max_depth: float = 20.0,
+                   max_normal_2d_length: float = 1.0, cost_threshold: float = 1.0, angle_threshold: float = 1.3,
+                   lr_consistency_factor_threshold: float = 1.025, seed: int = 0) -> CbaStereoOptions:
+    """cba_stereo_options; the defaults are the reference tool's settings and its matcher's defaults."""
+    return CbaStereoOptions(int(context_radius), int(iterations), float(min_depth), float(max_depth), float(max_normal_2d_length),
+                            float(cost_threshold), float(angle_threshold), float(lr_consistency_factor_threshold), int(seed) & (2 ** 64 - 1))
+
+
+class StereoHandle:
+    """cba_stereo (include/cba_stereo.h): one matching direction on the device.  unprojection (H, W, 2) and projection (PH, PW, 2)
+    float32, grid = (fx, fy, cx, cy) of the projection lookup's pinhole, stereo_tr_reference 12 floats (row-major 3 x 4)."""
+
+    def __init__(self, unprojection: np.ndarray, stereo_size, projection: np.ndarray, grid, stereo_tr_reference: np.ndarray, device: int = 0):
+        self.L = load()
+        u = np.ascontiguousarray(unprojection, dtype=np.float32)
+        p = np.ascontiguousarray(projection, dtype=np.float32)
+        if u.ndim != 3 or u.shape[2] != 2 or p.ndim != 3 or p.shape[2] != 2:
+            raise ValueError("StereoHandle: the lookups are (H, W, 2)")
+        self.height, self.width = int(u.shape[0]), int(u.shape[1])
+        self.stereo_width, self.stereo_height = int(stereo_size[0]), int(stereo_size[1])
+        m = np.ascontiguousarray(stereo_tr_reference, dtype=np.float32).reshape(12)
+        self._h = C.c_void_p()
+        _check(self.L.cba_stereo_create(self.width, self.height, self.stereo_width, self.stereo_height, u.ctypes.data_as(_F32P),
+                                        float(grid[0]), float(grid[1]), float(grid[2]), float(grid[3]), int(p.shape[1]), int(p.shape[0]),
+                                        p.ctypes.data_as(_F32P), m.ctypes.data_as(_F32P), int(device), C.byref(self._h)), "cba_stereo_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.cba_stereo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_images(self, reference_image: np.ndarray, stereo_image: np.ndarray) -> None:
+        a, b = np.ascontiguousarray(reference_image, dtype=np.uint8), np.ascontiguousarray(stereo_image, dtype=np.uint8)
+        if a.shape != (self.height, self.width) or b.shape != (self.stereo_height, self.stereo_width):
+            raise ValueError("StereoHandle.set_images: 8-bit one-channel images of the two cameras' sizes")
+        _check(self.L.cba_stereo_set_images(self._h, a.ctypes.data_as(_U8), b.ctypes.data_as(_U8)), "cba_stereo_set_images")
+
+    def set_pose(self, stereo_tr_reference: np.ndarray) -> None:
+        m = np.ascontiguousarray(stereo_tr_reference, dtype=np.float32).reshape(12)
+        _check(self.L.cba_stereo_set_pose(self._h, m.ctypes.data_as(_F32P)), "cba_stereo_set_pose")
+
+    def match(self, options: CbaStereoOptions) -> None:
+        _check(self.L.cba_stereo_match(self._h, C.byref(options)), "cba_stereo_match")
+
+    def run_stage(self, options: CbaStereoOptions, stage: int, pass_index: int) -> None:
+        _check(self.L.cba_stereo_run_stage(self._h, C.byref(options), int(stage), int(pass_index)), "cba_stereo_run_stage")
+
+    def get_state(self):
+        """(inv_depth (H, W) float32, normal (H, W, 2) int8, cost (H, W) float32)"""
+        d = np.zeros((self.height, self.width), dtype=np.float32)
+        n = np.zeros((self.height, self.width, 2), dtype=np.int8)
+        c = np.zeros((self.height, self.width), dtype=np.float32)
+        _check(self.L.cba_stereo_get_state(self._h, d.ctypes.data_as(_F32P), n.ctypes.data_as(_I8P), c.ctypes.data_as(_F32P)), "cba_stereo_get_state")
+        return d, n, c
+
+    def _state_arrays(self, inv_depth, normal, cost=None):
+        d = np.ascontiguousarray(inv_depth, dtype=np.float32)
+        n = np.ascontiguousarray(normal, dtype=np.int8)
+        c = None if cost is None else np.ascontiguousarray(cost, dtype=np.float32)
+        if d.shape != (self.height, self.width) or n.shape != (self.height, self.width, 2) or (c is not None and c.shape != d.shape):
+            raise ValueError("StereoHandle: a state is inv_depth (H, W), normal (H, W, 2), cost (H, W)")
+        return d, n, c
+
+    def set_state(self, inv_depth, normal, cost) -> None:
+        d, n, c = self._state_arrays(inv_depth, normal, cost)
+        _check(self.L.cba_stereo_set_state(self._h, d.ctypes.data_as(_F32P), n.ctypes.data_as(_I8P), c.ctypes.data_as(_F32P)), "cba_stereo_set_state")
+
+    def cost(self, options: CbaStereoOptions, inv_depth, normal) -> np.ndarray:
+        d, n, _ = self._state_arrays(inv_depth, normal)
+        out = np.zeros((self.height, self.width), dtype=np.float32)
+        _check(self.L.cba_stereo_cost(self._h, C.byref(options), d.ctypes.data_as(_F32P), n.ctypes.data_as(_I8P), out.ctypes.data_as(_F32P)),
+               "cba_stereo_cost")
+        return out
+
+    def filter(self, options: CbaStereoOptions, other_inv_depth: Optional[np.ndarray] = None) -> np.ndarray:
+        other = None
+        if other_inv_depth is not None:
+            other = np.ascontiguousarray(other_inv_depth, dtype=np.float32)
+            if other.shape != (self.stereo_height, self.stereo_width):
+                raise ValueError("StereoHandle.filter: the other direction's map has the stereo image's size")
+        out = np.zeros((self.height, self.width), dtype=np.float32)
+        _check(self.L.cba_stereo_filter(self._h, C.byref(options), other.ctypes.data_as(_F32P) if other is not None else None,
+                                        out.ctypes.data_as(_F32P)), "cba_stereo_filter")
+        return out
 
 
 def render_nearest_feature_image(width: int, height: int, site_xy_quarter_px: np.ndarray, site_rgb: np.ndarray, device: int = 0,

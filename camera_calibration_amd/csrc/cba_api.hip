@@ -10,6 +10,7 @@
 #include <memory>
 
 #include "cba_problem.h"
+#include "../../include/cba_diagnostics.h"
 
 namespace cba {
 
@@ -556,6 +557,18 @@ int cba_debug_fd_redo_counts(cba_problem* p, int64_t out[3]) {
   CBA_HIP(hipStreamSynchronize(p->stream));
   CBA_TRY(p->fd.redo_count.download(v, 3));
   for (int i = 0; i < 3; ++i) out[i] = v[i];
+  return CBA_OK;
+}
+int cba_debug_straggler_stats(cba_problem* p, int64_t out[5]) {
+  if (!p || !out || !p->slow.count) { set_error("cba_debug_straggler_stats: bad argument"); return CBA_ERR_ARG; }
+  int v[kSlowCounters];
+  CBA_HIP(hipSetDevice(p->device));
+  CBA_HIP(hipStreamSynchronize(p->stream));
+  // (the Jacobian pass runs its straggler launch on the side stream and joins it before the assembly: complete here as well)
+  CBA_TRY(p->slow.count.download(v, kSlowCounters));
+  out[0] = 0;                                                  // no pass keeps a prediction
+  out[1] = v[kSlowListCount] < p->slow.cap ? v[kSlowListCount] : p->slow.cap;
+  out[2] = v[kSlowStatPeriod1]; out[3] = v[kSlowStatPeriodN]; out[4] = v[kSlowStatFullBudget];
   return CBA_OK;
 }
 

@@ -91,7 +91,7 @@ struct PassArgs {
   double fd_delta;
   const int* pose_slot;     // block position of each imageset (rows of B sorted by image footprint) or null
   // straggler split: observations whose base projection exceeds the iteration cap of the one-lane kernel are listed by
-  // it and finished by the 16-lanes-per-observation kernel (kernels_project.hip: k_base_project_slow); in the Jacobian pass
+  // it and finished by the straggler kernel, 2 x 20 lanes per observation (kernels_project.hip: k_base_project_slow); in the Jacobian pass
   // that launch and the finite-difference tasks of the listed observations run on a side stream while the main launch skips them
   const int* obs_list;      // null = all observations in order
   const int* obs_count;     // device: entries in obs_list (clamped to obs_list_cap)
@@ -125,6 +125,10 @@ struct PassOutputs {
 };
 // Straggler split (see PassArgs)
 constexpr int kSlowCapMin = 16384;
+// StragglerSplit::count, cleared at the start of every pass: [0] fill count of the list (may exceed its capacity), then the straggler
+// kernel's counters of the pass (cba_debug_straggler_stats): attempts ended by an exact repeat of period 1 / of period >= 2 / that
+// ran all 100 outer iterations
+enum SlowCounter { kSlowListCount = 0, kSlowStatPeriod1, kSlowStatPeriodN, kSlowStatFullBudget, kSlowCounters };
 struct StragglerSplit {
   DevBuf<uint8_t> skip, fd_slow; DevBuf<int> list, count;
   int cap = kSlowCapMin;          // capacity of the list: max(this, n_obs / 8), set with the observations
@@ -202,7 +206,7 @@ int launch_tangents(const double* dir_grid, double* tang, int G, hipStream_t s);
 // slow.fd_slow go to the list as well
 int launch_base_project(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, StragglerSplit& slow, bool use_fd_slow,
                         hipStream_t s);
-int launch_base_project_slow(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, hipStream_t s);
+int launch_base_project_slow(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, StragglerSplit& slow, hipStream_t s);
 int launch_project_points(const CamDev* cam_dev, int model, int64_t n, const double* local, const double* init,
                           double* pixels, uint8_t* ok, hipStream_t s);
 int launch_unproject(const CamDev* cam_dev, int model, int64_t n, const double* pixels, double* lines, double* jac,

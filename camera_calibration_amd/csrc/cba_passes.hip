@@ -69,7 +69,7 @@ int residual_pass(cba_problem* p, int which, const int* guard) {
   CBA_TRY(launch_base_project(a, p->model_mask, p->out, /* test_cost */ true, p->slow, /* use_fd_slow */ false, p->stream));
   PassArgs as = a;
   as.obs_list = p->slow.list; as.obs_count = p->slow.count; as.obs_list_cap = p->slow.cap;
-  CBA_TRY(launch_base_project_slow(as, p->model_mask, p->out, /* test_cost */ true, p->stream));
+  CBA_TRY(launch_base_project_slow(as, p->model_mask, p->out, /* test_cost */ true, p->slow, p->stream));
   return CBA_OK;
 }
 
@@ -95,7 +95,7 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   // followed by their finite-difference tasks, underneath the main finite-difference launch
   CBA_HIP(hipEventRecord(p->ev_aux2, p->stream));
   CBA_HIP(hipStreamWaitEvent(aux, p->ev_aux2, 0));
-  CBA_TRY(launch_base_project_slow(as, p->model_mask, p->out, /* test_cost */ false, aux));
+  CBA_TRY(launch_base_project_slow(as, p->model_mask, p->out, /* test_cost */ false, p->slow, aux));
   CBA_TRY(launch_fd_tasks(as, p->model_mask, L.localize_only, p->out, p->fd, kFdSideList, aux));
   CBA_HIP(hipEventRecord(p->ev_aux1, aux));
   CBA_TRY(timer_begin(p, kTimerFd));

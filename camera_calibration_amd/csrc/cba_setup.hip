@@ -262,7 +262,7 @@ static int upload_pair_tables(cba_problem* p) {
 int alloc_pass_buffers(cba_problem* p) {
   const Layout& L = p->L;
   for (Event* e : {&p->ev_aux0, &p->ev_aux1, &p->ev_aux2, &p->ev_clear}) CBA_TRY(e->create(hipEventDisableTiming));
-  CBA_TRY(p->slow.count.alloc_zero(1));
+  CBA_TRY(p->slow.count.alloc_zero(kSlowCounters));
   for (int c = 0; c < L.n_cameras; ++c) p->model_mask |= (p->cams[c].model_type == CBA_CENTRAL_GENERIC) ? 1 : 2;
   const int maxKg = L.localize_only ? 0 : ((p->model_mask & 2) ? 80 : 32);
   p->out.tasks_per_obs = 3 + maxKg;

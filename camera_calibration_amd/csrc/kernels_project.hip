@@ -4,7 +4,7 @@
 //  k_tangents        ComputeTangentsImage                                      (joint_optimization.cc:229-238)
 //  k_base_project    AddReprojectionResidual, residual part                    (joint_optimization.cc:321-347)
 //  k_base_project_slow  the same for the observations whose projection runs long (failing projections: the reference's
-//                    whole 100 x 10-iteration budget, twice), 16 lanes per observation
+//                    whole 100 x 10-iteration budget, twice), 2 x 20 lanes per observation
 //  k_project_points / k_unproject   stateless model-level kernels (cba_project / cba_unproject, the grid-fit path)
 //
 // The packed observation array is streamed coalesced, one lane per observation; the finite-difference re-projections of the
@@ -86,7 +86,7 @@ int launch_tangents(const double* dir_grid, double* tang, int G, hipStream_t s) 
 // single lane, and a pass cannot end before its slowest lane (0.4 % of the observations of the BASELINE configs fail from
 // the perturbed initial state: points whose projection is pinned at the border of the calibrated area, or that settle in a
 // local minimum next to it).  So a lane gives up after `outer_cap` (default 8) outer iterations of either attempt and puts its
-// observation on the straggler list; k_base_project_slow then runs the COMPLETE procedure for the list with 16 lanes per
+// observation on the straggler list; k_base_project_slow then runs the COMPLETE procedure for the list with 2 x 20 lanes per
 // observation.  Nothing of the 100 x 10 semantics is cut short, the long chains are only evaluated faster.
 
 template <int MODEL>
@@ -150,133 +150,173 @@ __global__ void __launch_bounds__(256) k_base_project(PassArgs a, double* __rest
   store_base_projection(a, o, ok, px, py, cost_vec, pixels, flags);
 }
 
-// The straggler kernel: 16 lanes per listed observation evaluate the SAME procedure speculatively.
-//   lanes 0-7: the warm-start attempt, lanes 8-15: the attempt from the centre of the calibrated area -- the second attempt
-//     does not depend on the first (same target, fixed start), the reference merely skips it when the first succeeds;
-//   within an attempt, lane k (k = 0..7) takes damping attempt lm = base + k of the current round (lambda * 2^k) and
-//     evaluates BOTH Unproject at the candidate (the test cost) and UnprojectWithJacobian at the same candidate (what the
-//     NEXT outer iteration needs if this candidate is the first accepted one) -- two independent instruction streams in
-//     one lane, which the scheduler interleaves.  The first accepted candidate in reference order (lowest lm) wins and
-//     broadcasts pixel and evaluation to the group.
-// An outer iteration thus costs one evaluation latency instead of 1 + (attempts until acceptance), and both attempts run
-// side by side: ~100 evaluation latencies instead of ~600.  All arithmetic goes through the same device functions as the
-// one-lane loop (project_target), evaluated on identical inputs.
-// Exact shortcut: the loop state is (pixel, lambda); an iteration that maps it to itself (bitwise) will do so 100 times and
-// end in `return false` -- the pinned-at-the-border lanes -- so the attempt stops there with that result.
+// The straggler kernel: one workgroup of two wavefronts per kSlowObs listed observations evaluates the SAME procedure
+// speculatively, one evaluation stream per lane.
+//   A lane of either wavefront stands for (observation slot, attempt, damping candidate): 3 x 2 x 10 = 60 lanes.  Attempt 0 is
+//     the warm start, attempt 1 the start from the centre of the calibrated area -- the second attempt does not depend on the
+//     first (same target, fixed start), the reference merely skips it when the first succeeds.  Candidate lm (0..9) is damping
+//     attempt lm of the current outer iteration (lambda * 2^lm).
+//   Wavefront 0 holds the loop state of every attempt (replicated over its 10 lanes), forms the normal equations and the
+//     candidate pixels, evaluates Unproject at its candidate (the test cost) and picks the first accepted candidate in
+//     reference order (lowest lm).  Wavefront 1 evaluates UnprojectWithJacobian at the same candidates (what the NEXT outer
+//     iteration needs if that candidate wins) and hands its results over in LDS.  The two streams sit on two SIMDs: an outer
+//     iteration costs one evaluation latency of the longer stream, where one lane running both paid for the sum of their
+//     instructions (a wavefront alone on its SIMD is bound by instruction issue; so are two streams in diverging lanes of one).
+//   Wavefront 1 keeps no state and takes no decision: whether another iteration follows is one LDS word written by wavefront 0,
+//     so both execute the same number of barriers, at most 2 x 100.
+// All arithmetic goes through the same device functions as the one-lane loop (project_target), evaluated on identical inputs.
+// Exact shortcut: the loop state is (pixel, lambda) and the map is deterministic, so an attempt that revisits a state bit for bit
+// without having terminated runs to 100 iterations and ends in `return false` -- nothing is stored for it.  Brent's cycle
+// detection (one saved state, renewed at powers of two, three 64-bit compares per iteration) ends it at the first exact repeat
+// of any period: the pinned-at-the-border lanes (period 1) and the orbits between a few pixels.
+// stats (per pass, cba_debug_straggler_stats): attempts ended by a repeat of period 1 / of period >= 2 / that ran all 100.
+constexpr int kSlowObs = 3;            // observation slots of a workgroup
+constexpr int kSlowCand = 10;          // damping candidates of an attempt (lanes)
+constexpr int kSlowLanes = 2 * kSlowCand;   // lanes of an observation slot in either wavefront
 template <int MODEL>
-__global__ void __launch_bounds__(256) k_base_project_slow(PassArgs a, double* __restrict__ cost_vec, double* __restrict__ pixels,
-                                                           uint8_t* __restrict__ flags) {
+__global__ void __launch_bounds__(128) k_base_project_slow(PassArgs a, double* __restrict__ cost_vec, double* __restrict__ pixels,
+                                                           uint8_t* __restrict__ flags, int* __restrict__ stats) {
   constexpr double kEpsilon = 1e-12;
-  const int tid = blockIdx.x * 256 + threadIdx.x;
+  constexpr int NJ = (MODEL == kCentral) ? 9 : 18;            // dir, jd (, org, jo)
+  __shared__ double s_tx[64], s_ty[64], s_j[NJ][64];
+  __shared__ int s_mine[64], s_in[64], s_go;
   const int lane = threadIdx.x & 63;
-  if (a.guard && *a.guard != 0) return;                     // (wave-uniform) the solve in front of this cost pass broke down
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (a.guard && *a.guard != 0) return;                     // (workgroup-uniform) the solve in front of this cost pass broke down
   const int cnt = min(*a.obs_count, a.obs_list_cap);
-  if (((tid & ~63) >> 4) >= cnt) return;                    // wave-uniform
-  const int g = tid >> 4;
-  const int64_t o = a.obs_list[g < cnt ? g : cnt - 1];      // idle groups shadow the last entry; they never evaluate or store
+  const int g0 = blockIdx.x * kSlowObs;
+  if (g0 >= cnt) return;                                    // workgroup-uniform, in front of every barrier
+  const int slot = lane / kSlowLanes, cand = lane % kSlowCand, gbase = lane - cand;
+  const int attempt = (lane / kSlowCand) & 1;
+  const int g = g0 + slot;
+  const bool used = slot < kSlowObs && g < cnt;
+  const int64_t o = a.obs_list[used ? g : cnt - 1];         // idle lanes shadow the last entry; they never evaluate or store
   const int cam = a.obs_camera[o];
   const CamDev c = a.cams[cam];
-  const bool live = g < cnt && c.model_type == MODEL;
-  const int attempt = (lane >> 3) & 1, cand = lane & 7, gbase = lane & ~7;
+  const bool live = used && c.model_type == MODEL;
+  const Subst none = no_subst();
+
+  if (wave == 1) {      // UnprojectWithJacobian at the candidates of wavefront 0
+    for (int it = 0; it < 100; ++it) {
+      __syncthreads();                                      // (A) candidates and s_go of this iteration are in LDS
+      if (!s_go) break;
+      double ndir[3] = {0, 0, 0}, norg[3] = {0, 0, 0}, njd[6] = {0, 0, 0, 0, 0, 0}, njo[6] = {0, 0, 0, 0, 0, 0};
+      int nin = 0;
+      if (s_mine[lane]) {
+        const double tx = s_tx[lane], ty = s_ty[lane];
+        // the clamped candidate lies inside the calibrated area, so UnprojectWithJacobian reduces to its evaluation part
+        // (model.hip.h: unproject_jac) -- straight-line code
+        if (in_calibrated_area(c, tx, ty)) {
+          double gx, gy;
+          pixel_to_grid(c, tx, ty, gx, gy);
+          gx += 2; gy += 2;
+          unproject_jac_eval<MODEL, false>(c, none, (lds_cdouble_ptr)0, (lds_cdouble_ptr)0, (int)floor(gx), (int)floor(gy), gx, gy, ndir, norg, njd, njo);
+          nin = 1;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s_j[k][lane] = ndir[k];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s_j[3 + k][lane] = njd[k];
+      if (MODEL != kCentral) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s_j[9 + k][lane] = norg[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s_j[12 + k][lane] = njo[k];
+      }
+      s_in[lane] = nin;
+      __syncthreads();                                      // (B) the evaluations are in LDS
+    }
+    return;
+  }
+
   double target[3];
   local_point_of(a, o, cam, target);
   if (MODEL == kCentral) normalize3(target[0], target[1], target[2]);
   double px = a.last_projection[2 * o], py = a.last_projection[2 * o + 1];
   if (attempt == 1 || !in_calibrated_area(c, px, py) || px != px || py != py) center_pixel(c, px, py);
-  const Subst none = no_subst();
   double dir[3] = {0, 0, 0}, org[3] = {0, 0, 0}, jd[6] = {0, 0, 0, 0, 0, 0}, jo[6] = {0, 0, 0, 0, 0, 0};
   bool cur_in = false, active = live, result = false;
   if (active) cur_in = unproject_jac<MODEL>(c, none, px, py, dir, org, jd, jo);
   double lambda = -1.0;
-  long long prev_px = -1, prev_py = -1, prev_lambda = -1;   // bit patterns of the previous iteration's state (-1 = NaN pattern: none)
+  long long saved_px = 0, saved_py = 0, saved_lambda = 0;   // Brent: bit patterns of the saved state,
+  int steps = 0, power = 1, period = 0;                     // iterations since it was saved, when to renew it; period of the repeat found
   for (int it = 0; it < 100; ++it) {
-    if (!__any(active)) break;
+    const bool go = __any(active);
+    if (lane == 0) s_go = go;
     if (active && !cur_in) { result = false; active = false; }          // CHECK() in the reference
     double cost = 0, H00 = 0, H01 = 0, H11 = 0, b0 = 0, b1 = 0;
     if (active) {
       projection_normal_equations<MODEL>(dir, org, jd, jo, target, cost, H00, H01, H11, b0, b1);
       if (lambda < 0) lambda = 0.01 * 0.5 * (H00 + H11);
       const long long bx = __double_as_longlong(px), by = __double_as_longlong(py), bl = __double_as_longlong(lambda);
-      if (bx == prev_px && by == prev_py && bl == prev_lambda) { result = false; active = false; }   // fixed point
-      prev_px = bx; prev_py = by; prev_lambda = bl;
-    }
-    bool accepted = false;
-#pragma unroll 1
-    for (int base = 0; base < 10; base += 8) {
-      const int lm = base + cand;
-      const bool mine = active && !accepted && lm < 10;
-      double lam_c = lambda;
-      for (int k = 0; k < cand; ++k) lam_c *= 2.0;             // the rejected attempts before this one
-      double tx = px, ty = py, tc = INFINITY;
-      double ndir[3] = {0, 0, 0}, norg[3] = {0, 0, 0}, njd[6] = {0, 0, 0, 0, 0, 0}, njo[6] = {0, 0, 0, 0, 0, 0};
-      bool nin = false;
-      if (mine) {
-        projection_candidate(c, H00, H01, H11, b0, b1, lam_c, px, py, tx, ty);
-        // the clamped candidate lies inside the calibrated area, so Unproject / UnprojectWithJacobian reduce to their
-        // evaluation parts (model.hip.h: unproject, unproject_jac) -- straight-line code for both
-        if (in_calibrated_area(c, tx, ty)) {
-          double gx, gy;
-          pixel_to_grid(c, tx, ty, gx, gy);
-          gx += 2; gy += 2;
-          double td[3], to[3];
-          unproject_eval<MODEL, false>(c, none, (lds_cdouble_ptr)0, (lds_cdouble_ptr)0, (int)gx, (int)gy, gx, gy, td, to);
-          unproject_jac_eval<MODEL, false>(c, none, (lds_cdouble_ptr)0, (lds_cdouble_ptr)0, (int)floor(gx), (int)floor(gy), gx, gy, ndir, norg, njd, njo);
-          tc = projection_test_cost<MODEL>(td, to, target);
-          nin = true;
-        }
+      if (it > 0) {
+        steps += 1;
+        if (bx == saved_px && by == saved_py && bl == saved_lambda) { period = steps; result = false; active = false; }   // exact repeat
       }
-      const bool acc_c = mine && (tc < cost);
-      const unsigned m = (unsigned)((__ballot(acc_c) >> gbase) & 0xffull);
-      const int w = m ? (__ffs(m) - 1) : -1;
-      const int src = gbase + (w < 0 ? 0 : w);
-      const double wtx = __shfl(tx, src, 64), wty = __shfl(ty, src, 64);
-      const int w_in = __shfl((int)nin, src, 64);
-      double wdir[3], worg[3], wjd[6], wjo[6];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) wdir[k] = __shfl(ndir[k], src, 64);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) wjd[k] = __shfl(njd[k], src, 64);
-      if (MODEL != kCentral) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) worg[k] = __shfl(norg[k], src, 64);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) wjo[k] = __shfl(njo[k], src, 64);
-      }
-      if (active && !accepted) {
-        if (w >= 0) {
-          double l = lambda;
-          for (int k = 0; k < w; ++k) l *= 2.0;              // the rejected attempts before the accepted one
-          lambda = l * 0.5;
-          px = wtx; py = wty;
-#pragma unroll
-          for (int k = 0; k < 3; ++k) dir[k] = wdir[k];
-#pragma unroll
-          for (int k = 0; k < 6; ++k) jd[k] = wjd[k];
-          if (MODEL != kCentral) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) org[k] = worg[k];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) jo[k] = wjo[k];
-          }
-          cur_in = w_in != 0;
-          accepted = true;
-        } else {
-          const int tried = 10 - base < 8 ? 10 - base : 8;
-          for (int k = 0; k < tried; ++k) lambda *= 2.0;
-        }
+      if (it == 0 || steps == power) {
+        if (it > 0) power *= 2;
+        saved_px = bx; saved_py = by; saved_lambda = bl; steps = 0;
       }
     }
+    const bool mine = active;
+    double lam_c = lambda;
+    for (int k = 0; k < cand; ++k) lam_c *= 2.0;               // the rejected attempts before this one
+    double tx = px, ty = py, tc = INFINITY;
+    if (mine) projection_candidate(c, H00, H01, H11, b0, b1, lam_c, px, py, tx, ty);
+    s_tx[lane] = tx; s_ty[lane] = ty; s_mine[lane] = mine ? 1 : 0;
+    __syncthreads();                                        // (A)
+    if (!go) break;
+    // the clamped candidate lies inside the calibrated area, so Unproject reduces to its evaluation part (model.hip.h: unproject)
+    if (mine && in_calibrated_area(c, tx, ty)) {
+      double gx, gy;
+      pixel_to_grid(c, tx, ty, gx, gy);
+      gx += 2; gy += 2;
+      double td[3], to[3];
+      unproject_eval<MODEL, false>(c, none, (lds_cdouble_ptr)0, (lds_cdouble_ptr)0, (int)gx, (int)gy, gx, gy, td, to);
+      tc = projection_test_cost<MODEL>(td, to, target);
+    }
+    const bool acc_c = mine && (tc < cost);
+    const unsigned m = (unsigned)((__ballot(acc_c) >> gbase) & ((1u << kSlowCand) - 1));
+    const int w = m ? (__ffs(m) - 1) : -1;
+    const int src = gbase + (w < 0 ? 0 : w);
+    const double wtx = __shfl(tx, src, 64), wty = __shfl(ty, src, 64);
+    __syncthreads();                                        // (B)
     if (active) {
-      if (!accepted) { result = cost < kEpsilon; active = false; }
-      else if (cost < kEpsilon) { result = true; active = false; }
+      if (w >= 0) {
+        double l = lambda;
+        for (int k = 0; k < w; ++k) l *= 2.0;                // the rejected attempts before the accepted one
+        lambda = l * 0.5;
+        px = wtx; py = wty;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dir[k] = s_j[k][src];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) jd[k] = s_j[3 + k][src];
+        if (MODEL != kCentral) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) org[k] = s_j[9 + k][src];
+#pragma unroll
+          for (int k = 0; k < 6; ++k) jo[k] = s_j[12 + k][src];
+        }
+        cur_in = s_in[src] != 0;
+        if (cost < kEpsilon) { result = true; active = false; }
+      } else {
+        for (int k = 0; k < kSlowCand; ++k) lambda *= 2.0;
+        result = cost < kEpsilon; active = false;
+      }
     }
   }
   // still active after 100 outer iterations: not converged (result stays false)
-  const int first = lane & ~15;
-  const int ok0 = __shfl((int)result, first, 64), ok1 = __shfl((int)result, first + 8, 64);
+  if (live && cand == 0) {
+    if (period == 1) atomicAdd(stats + 0, 1);
+    else if (period >= 2) atomicAdd(stats + 1, 1);
+    else if (active) atomicAdd(stats + 2, 1);
+  }
+  const int first = slot * kSlowLanes;
+  const int ok0 = __shfl((int)result, first, 64), ok1 = __shfl((int)result, first + kSlowCand, 64);
   const double px0 = __shfl(px, first, 64), py0 = __shfl(py, first, 64);
-  const double px1 = __shfl(px, first + 8, 64), py1 = __shfl(py, first + 8, 64);
-  if (live && (lane & 15) == 0)
+  const double px1 = __shfl(px, first + kSlowCand, 64), py1 = __shfl(py, first + kSlowCand, 64);
+  if (live && lane == first)
     store_base_projection(a, o, ok0 || ok1, ok0 ? px0 : px1, ok0 ? py0 : py1, cost_vec, pixels, flags);
 }
 
@@ -285,7 +325,7 @@ __global__ void __launch_bounds__(256) k_base_project_slow(PassArgs a, double* _
 int launch_base_project(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, StragglerSplit& slow, bool use_fd_slow,
                         hipStream_t s) {
   if (a.n_obs == 0) return CBA_OK;
-  CBA_TRY(slow.count.zero_async(1, s));
+  CBA_TRY(slow.count.zero_async(kSlowCounters, s));      // the list's fill count and the straggler kernel's counters
   dim3 grid((unsigned)((a.n_obs + 255) / 256)), block(256);
   double* cost_vec = test_cost ? out.cost_test : out.cost_ref;
   const uint8_t* fd_slow = use_fd_slow ? (const uint8_t*)slow.fd_slow : nullptr;
@@ -295,12 +335,13 @@ int launch_base_project(const PassArgs& a, int model_mask, PassOutputs& out, boo
   return CBA_OK;
 }
 // `a.obs_list / obs_count / obs_list_cap` = the straggler list filled by launch_base_project
-int launch_base_project_slow(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, hipStream_t s) {
+int launch_base_project_slow(const PassArgs& a, int model_mask, PassOutputs& out, bool test_cost, StragglerSplit& slow, hipStream_t s) {
   if (a.n_obs == 0) return CBA_OK;
   double* cost_vec = test_cost ? out.cost_test : out.cost_ref;
-  dim3 grid((unsigned)(((int64_t)a.obs_list_cap * 16 + 255) / 256)), block(256);
-  if (model_mask & 1) hipLaunchKernelGGL(k_base_project_slow<kCentral>, grid, block, 0, s, a, cost_vec, out.pixels, out.flags);
-  if (model_mask & 2) hipLaunchKernelGGL(k_base_project_slow<kNoncentral>, grid, block, 0, s, a, cost_vec, out.pixels, out.flags);
+  int* stats = (int*)slow.count + kSlowStatPeriod1;
+  dim3 grid((unsigned)((a.obs_list_cap + kSlowObs - 1) / kSlowObs)), block(128);
+  if (model_mask & 1) hipLaunchKernelGGL(k_base_project_slow<kCentral>, grid, block, 0, s, a, cost_vec, out.pixels, out.flags, stats);
+  if (model_mask & 2) hipLaunchKernelGGL(k_base_project_slow<kNoncentral>, grid, block, 0, s, a, cost_vec, out.pixels, out.flags, stats);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

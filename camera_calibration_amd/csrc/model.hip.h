@@ -317,7 +317,7 @@ __device__ __forceinline__ void tangent_derivs(const double* d, const double* jd
     }
 }
 
-// ---- pieces of the iterative projection, shared by the one-lane loop (project_target) and the 16-lanes-per-observation
+// ---- pieces of the iterative projection, shared by the one-lane loop (project_target) and the 2 x 20-lanes-per-observation
 // ---- straggler kernel (kernels_project.hip: k_base_project_slow), so that both evaluate the same expressions ----
 // cost and 2 x 2 normal equations of one LM iteration from UnprojectWithJacobian's outputs at the current pixel
 template <int MODEL>

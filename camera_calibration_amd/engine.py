@@ -250,6 +250,10 @@ class CbaStereoOptions(C.Structure):
 
 # The same table for include/cba_stereo.h (tests/test_stereo_cases.py checks it against that header)
 _I8P, _SOPT = C.POINTER(C.c_int8), C.POINTER(CbaStereoOptions)
+# The same table for include/cba_diagnostics.h
+DIAGNOSTICS_PROTOTYPES = {
+    "cba_debug_straggler_stats": (_I, [_VP, _I64P]),
+}
 STEREO_PROTOTYPES = {
     "cba_stereo_create": (_I, [_I32, _I32, _I32, _I32, _F32P, C.c_float, C.c_float, C.c_float, C.c_float, _I32, _I32, _F32P, _F32P, _I32,
                                C.POINTER(_VP)]),
@@ -296,7 +300,7 @@ def load() -> C.CDLL:
         raise EngineError(f"{LIB_PATH} is missing -- run `python -c 'import __graft_entry__ as g; g.build()'`; "
                           "the engine has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **UNDISTORT_PROTOTYPES, **STEREO_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **UNDISTORT_PROTOTYPES, **STEREO_PROTOTYPES, **DIAGNOSTICS_PROTOTYPES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -429,6 +433,10 @@ class Engine:
         self._cfg = cfg
         self._h = C.c_void_p()
         _check(self.L.cba_create(C.byref(cfg), C.byref(self._h)), "cba_create")
+        self.set_observations(problem, last_projection)
+
+    def set_observations(self, problem: Problem, last_projection: Optional[np.ndarray] = None) -> None:
+        """cba_set_observations: replaces the observations (same cameras, imagesets and points); last_projection = warm starts or None."""
         _check(self.L.cba_set_observations(
             self._h, problem.n_obs, problem.obs_xy.ctypes.data_as(C.POINTER(C.c_float)),
             problem.obs_point.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -436,6 +444,7 @@ class Engine:
             problem.obs_camera.ctypes.data_as(C.POINTER(C.c_int32)),
             None if last_projection is None else _dp(np.ascontiguousarray(last_projection, dtype=np.float64).reshape(-1, 2))),
             "cba_set_observations")
+        self.problem = problem
 
     @staticmethod
     def reduce_buffer_doubles(problem: Problem, distributed_solve: bool = False, world_size: int = 1) -> int:
@@ -520,6 +529,12 @@ class Engine:
         out = (C.c_int64 * 3)()
         _check(self.L.cba_debug_fd_redo_counts(self._h, out), "cba_debug_fd_redo_counts")
         return int(out[0]), int(out[1]), int(out[2])
+
+    def straggler_stats(self) -> dict:
+        """cba_debug_straggler_stats: counters of the base projection's straggler kernel in the last pass over the observations."""
+        out = (C.c_int64 * 5)()
+        _check(self.L.cba_debug_straggler_stats(self._h, out), "cba_debug_straggler_stats")
+        return dict(zip(("predicted", "listed", "period_1", "period_2_or_more", "full_budget"), (int(v) for v in out)))
 
     def debug_accumulate(self) -> float:
         cost = C.c_double(0)

@@ -570,10 +570,10 @@ enum {
 };
 int cba_debug_dump(cba_problem* p, int32_t what, void* out, size_t bytes);
 /* Tuning knob of the base projection (AddReprojectionResidual's ProjectWithInitialEstimate, joint_optimization.cc:325-343).
- * The one-lane-per-observation kernel hands an observation to the straggler kernel (16 lanes per observation, the same
+ * The one-lane-per-observation kernel hands an observation to the straggler kernel (2 x 20 lanes per observation, the same
  * 100 x 10-iteration procedure evaluated speculatively) after this many outer iterations; default 8.  0 sends every
  * observation there (the tests use it to compare the two kernels), >= 100 disables the hand-over.  Results do not depend
- * on the value. */
+ * on the value.  Counters of the straggler kernel: cba_diagnostics.h. */
 int cba_set_straggler_threshold(cba_problem* p, int32_t outer_iterations);
 /* Scheduling knob of the finite-difference re-projections (joint_optimization.cc:357-372, APP/models/central_grid.h:187-245,
  * noncentral_generic.h:224-283): 0 = a workgroup takes a pool of tasks and every lane runs ONE damping attempt of its current

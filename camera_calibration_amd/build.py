@@ -13,7 +13,7 @@ SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "c
            "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "kernels_undistort.hip", "kernels_features.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip", "cba_stereo.hip", "kernels_stereo.hip"]
 HEADERS = ["cba_internal.h", "hip_buf.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "block_device.hip.h", "localize_device.hip.h", "gridfirst_plan.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
 # public headers besides cba.h that a unit includes (cba_undistort.h: cba_undistort.hip; cba_features.h: cba_internal.h;
-# cba_stereo.h: cba_stereo.hip, kernels_stereo.hip; cba_diagnostics.h: cba_api.hip)
+# cba_stereo.h: cba_stereo.hip, kernels_stereo.hip; cba_diagnostics.h: cba_api.hip, cba_gridfirst.hip)
 PUBLIC_HEADERS = [os.path.join("..", "..", "include", "cba_undistort.h"), os.path.join("..", "..", "include", "cba_features.h"),
                   os.path.join("..", "..", "include", "cba_stereo.h"), os.path.join("..", "..", "include", "cba_diagnostics.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",

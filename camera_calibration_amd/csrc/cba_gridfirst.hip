@@ -4,6 +4,7 @@
 #include <cstring>
 #include <limits>
 
+#include "../../include/cba_diagnostics.h"
 #include "cba_problem.h"
 
 namespace cba {
@@ -61,8 +62,8 @@ int alloc_gridfirst_system(cba_problem* p) {
     CBA_TRY(d.gridrow.assign(reinterpret_cast<const unsigned long long*>(g.gridrow.data()), g.gridrow.size()));
     {
       const size_t nt = (size_t)d.n_act_tiles;
-      // entries of four ints (tm, tn, K-slab range), eight interleaved per-XCD lists padded to the longest: 4 x 8 x (tiles in up to three
-      // parts each, dealt evenly) is a quarter of this
+      // entries of four ints (tm, tn, K-slab range), eight interleaved per-XCD lists padded to the longest: 4 x 8 x (tiles in up to four
+      // parts each, dealt evenly) is a quarter of this (tests/test_gridfirst_tile_list.py holds every list against it)
       CBA_TRY(p->gf.tile_list.alloc((size_t)32 * nt * (nt + 1) + 4096));
       CBA_TRY(p->gf.tile_list_host.alloc(p->gf.tile_list.size()));
     }
@@ -187,81 +188,14 @@ int gridfirst_pass_activity(cba_problem* p, const PassArgs& a, hipStream_t aux) 
 // End of a Jacobian pass: image sharding exchanges the accumulated system and the activity words
 int gridfirst_pass_end(cba_problem* p) { return p->gf_sharded ? gf_exchange(p) : CBA_OK; }
 
-// Order in which the border update hands out its 128 x 128 tiles (GemmArgs::tile_list): workgroup b of the launch runs on XCD b % 8 and
-// the dispatcher hands workgroups out strictly in order, so (a) the list as a whole is sorted by executed K slabs, heaviest first --
-// list scheduling: the light tiles fill the gaps behind the heavy ones, and every XCD (every eighth entry) sees the same sequence of
-// weights, which keeps the in-order dispatcher from waiting for one XCD -- and (b) inside a run of tiles of about the same weight (7 %
-// buckets) the tiles are dealt so that one XCD walks a CONTIGUOUS piece of the run in row-major order: its tiles in flight share an A
-// panel and neighbouring B panels in that XCD's L2 instead of 64 unrelated pairs (FETCH_SIZE of the launch:
-// profiles/r06_update_tile_order.txt).  Short lists are padded with (-1, -1) (the workgroup leaves).  weight(tm, tn): executed K slabs
-// (or anything proportional) of upper tile (tm, tn), tm <= tn < nt.  Host work; the list is uploaded by the next solve.
-// A tile with all K slabs runs for most of the launch (2.7 of 3.5 ms at BASELINE configs[1]); tiles heavier than a third of the heaviest
-// are therefore handed out in PARTS (K ranges with equal shares of the executed slabs, GemmArgs::tile_list) that add to C atomically --
-// not in the deterministic mode, where the additions must keep one order.  split(tm, tn, target): the K slab in front of which
-// `target` units of the tile's weight lie; n_slabs: K slabs of the launch.
-template <class Weight, class Split>
-static void gf_build_tile_list(cba_problem* p, int nt, int n_slabs, Weight weight, Split split) {
-  struct Tile { int w, tm, tn, s0, s1; };
-  std::vector<Tile> all;
-  all.reserve((size_t)nt * (nt + 1));
-  int w_max = 0;
-  for (int tm = 0; tm < nt; ++tm)
-    for (int tn = tm; tn < nt; ++tn) { const int w = weight(tm, tn); all.push_back(Tile{w, tm, tn, 0, 0}); w_max = std::max(w_max, w); }
-  // (image sharding: not either -- every rank must factor F bit for bit alike, or the replicas' LM decisions and collectives part)
-  if (!p->cfg.deterministic && !p->gf_sharded) {
-    // unit: a third of the heaviest tile (measured at BASELINE configs[1] / [2] / [3], launch ms with units of 1/2, 1/3, 1/4, 1/6:
-    // 3.31 / 3.31 / 3.26 / 3.26, 12.17 / 12.03 / 12.09 / 12.18, 5.40 / 5.27 / 5.37 / 5.41; whole tiles: 3.50 / 12.34 / 5.53)
-    const int unit = std::max(8, w_max / 3);
-    const size_t n0 = all.size();
-    for (size_t i = 0; i < n0; ++i) {
-      const int w = all[i].w, parts = (w + unit - 1) / unit;
-      if (parts < 2) continue;
-      int prev = 0, done = 0;
-      bool ok = true;
-      std::vector<Tile> add;
-      for (int q = 1; q < parts && ok; ++q) {
-        const int target = (int)((long long)w * q / parts);
-        const int sq = split(all[i].tm, all[i].tn, target);
-        if (sq <= prev || sq >= n_slabs) { ok = false; break; }
-        add.push_back(Tile{target - done, all[i].tm, all[i].tn, prev, sq});
-        prev = sq; done = target;
-      }
-      if (!ok) continue;
-      add.push_back(Tile{w - done, all[i].tm, all[i].tn, prev, n_slabs});
-      all[i] = add[0];
-      for (size_t q = 1; q < add.size(); ++q) all.push_back(add[q]);
-    }
-  }
-  std::stable_sort(all.begin(), all.end(), [](const Tile& u, const Tile& v) { return u.w > v.w; });      // row-major among equals
-  std::vector<Tile> lists[8];
-  size_t i0 = 0;
-  while (i0 < all.size()) {
-    size_t i1 = i0 + 1;
-    while (i1 < all.size() && (double)all[i1].w >= 0.93 * all[i0].w) ++i1;                               // one bucket
-    std::stable_sort(all.begin() + i0, all.begin() + i1, [](const Tile& u, const Tile& v) { return u.tm != v.tm ? u.tm < v.tm : (u.tn != v.tn ? u.tn < v.tn : u.s0 < v.s0); });
-    const size_t L = i1 - i0;
-    int start = 0;
-    for (int x = 1; x < 8; ++x) if (lists[x].size() < lists[start].size()) start = x;
-    size_t pos = i0;
-    for (int k = 0; k < 8; ++k) {
-      const size_t len = L / 8 + ((size_t)k < L % 8 ? 1 : 0);
-      std::vector<Tile>& dst = lists[(start + k) % 8];
-      dst.insert(dst.end(), all.begin() + pos, all.begin() + pos + len);
-      pos += len;
-    }
-    i0 = i1;
-  }
-  size_t longest = 0;
-  for (int x = 0; x < 8; ++x) longest = std::max(longest, lists[x].size());
-  if (4 * 8 * longest > p->gf.tile_list_host.size()) return;      // (cannot happen with the sizing of cba_create; the previous list stays)
-  p->gf.tile_list_entries = (int)(8 * longest);
-  for (size_t i = 0; i < longest; ++i)
-    for (int x = 0; x < 8; ++x) {
-      const bool have = i < lists[x].size();
-      int* e = p->gf.tile_list_host + 4 * (8 * i + x);
-      e[0] = have ? lists[x][i].tm : -1; e[1] = have ? lists[x][i].tn : -1;
-      e[2] = have ? lists[x][i].s0 : 0; e[3] = have ? lists[x][i].s1 : 0;
-    }
+// A tile list of the border update (gf_build_tile_list, gridfirst_plan.h) becomes the problem's: host copy, uploaded by the next solve.
+// Parts only where the additions need not keep one order (deterministic mode) and the ranks need not factor F bit for bit alike
+// (image sharding: the replicas' LM decisions and collectives would part).
+static bool gf_allow_parts(const cba_problem* p) { return !p->cfg.deterministic && !p->gf_sharded; }
+static void gf_install_tile_list(cba_problem* p, const std::vector<int>& list) {
+  if (list.size() > p->gf.tile_list_host.size()) return;      // (cannot happen with the sizing of cba_create; the previous list stays)
+  p->gf.tile_list_entries = (int)(list.size() / 4);
+  std::memcpy(p->gf.tile_list_host, list.data(), sizeof(int) * list.size());
   p->gf.tile_list_valid = true;
   p->gf.tile_list_dirty = true;
 }
@@ -320,18 +254,7 @@ void gridfirst_finish(cba_problem* p) {
   // (cba_set_observations leaves a first list predicted from the measured pixels; the first solve's masks replace it, then every 8th)
   ++p->gf.tile_list_age;
   if (!p->gf.tile_list_valid || p->gf.tile_list_age == 1 || (p->gf.tile_list_age & 7) == 0)
-    gf_build_tile_list(p, nt, g.Gf / 16, [&](int tm, int tn) { return common_slabs(row(tm), row(tn), kw); }, [&](int tm, int tn, int target) {
-      int seen = 0;
-      for (int w = 0; w < kw; ++w) {
-        const unsigned long long bits = row(tm)[w] & row(tn)[w];
-        const int c = __builtin_popcountll(bits);
-        if (seen + c < target) { seen += c; continue; }
-        for (int b = 0; b < 64; ++b)
-          if ((bits >> b) & 1ull) { if (seen == target) return 64 * w + b; ++seen; }
-        return 64 * (w + 1);
-      }
-      return 0;
-    });
+    gf_install_tile_list(p, gf_tile_list_from_kmask(reinterpret_cast<const uint64_t*>(row(0)), kw, nt, g.Gf / 16, gf_allow_parts(p)));
 }
 
 // ---- cba_debug_gridfirst: the stages of a solve one by one, on the problem's own buffers (tests/test_gpu_gridfirst_stages.py) ----
@@ -452,6 +375,29 @@ extern "C" int cba_debug_gridfirst(cba_problem* p, double lambda, int32_t stage,
   return rc;
 }
 
+// ---- cba_diagnostics.h: the tile list of the border update (tests/test_gridfirst_tile_list.py, test_gpu_gridfirst_default_update.py) ----
+extern "C" int64_t cba_debug_gridfirst_tile_list_query(int32_t mode, int32_t nt, int32_t words, const uint64_t* mask_words, int32_t n_slabs,
+                                                       int32_t allow_parts, int32_t* entries, int64_t capacity_entries) {
+  if ((mode != 0 && mode != 1) || nt < 1 || words < 1 || !mask_words || n_slabs < 1 || capacity_entries < 0 || (capacity_entries > 0 && !entries)) {
+    set_error("cba_debug_gridfirst_tile_list_query: bad argument"); return CBA_ERR_ARG;
+  }
+  const std::vector<int> list = mode == 0 ? gf_tile_list_from_kmask(mask_words, words, nt, n_slabs, allow_parts != 0)
+                                          : gf_tile_list_from_rows(mask_words, words, 64 * words, nt, n_slabs, allow_parts != 0);
+  const int64_t n = (int64_t)(list.size() / 4);
+  if (n && capacity_entries >= n) std::memcpy(entries, list.data(), sizeof(int) * list.size());
+  return n;
+}
+
+extern "C" int64_t cba_debug_gridfirst_tile_list(cba_problem* p, int32_t* entries, int64_t capacity_entries, int32_t info[4]) {
+  if (!p || !info || capacity_entries < 0 || (capacity_entries > 0 && !entries)) { set_error("cba_debug_gridfirst_tile_list: bad argument"); return CBA_ERR_ARG; }
+  if (!p->gridfirst || !p->gf.tile_list_host) { set_error("cba_debug_gridfirst_tile_list: not the grid-first order"); return CBA_ERR_UNSUPPORTED; }
+  const int64_t n = p->gf.tile_list_valid ? p->gf.tile_list_entries : 0;
+  info[0] = p->gf.tile_list_valid ? 1 : 0; info[1] = (int32_t)p->gf.tile_list_age; info[2] = p->gf.tile_list_dirty ? 1 : 0;
+  info[3] = p->gf.plan.Gf / 16;
+  if (n && capacity_entries >= n) std::memcpy(entries, p->gf.tile_list_host, sizeof(int) * 4 * (size_t)n);
+  return n;
+}
+
 namespace cba {
 
 // ---- block order of the imagesets (cba_set_observations): refinement of the Z-order `order` (order_imagesets) ----
@@ -500,19 +446,7 @@ void order_imagesets_gridfirst(cba_problem* p, int64_t n, const float* xy, const
       for (int w = 0; w < W; ++w)
         if (64 * w + 64 > g.nbg) a[w] &= (64 * w >= g.nbg) ? 0ull : (~0ull >> (64 - (g.nbg - 64 * w)));
     }
-    gf_build_tile_list(p, nt, g.Gf / 16, [&](int tm, int tn) {
-      int rows = 0;
-      for (int w = 0; w < W; ++w) rows += __builtin_popcountll(tact[(size_t)tm * W + w] & tact[(size_t)tn * W + w]);
-      return 4 * rows;                                   // K slabs of 16 rows: four per block row
-    }, [&](int tm, int tn, int target) {
-      int seen = 0;
-      for (int r = 0; r < g.nbg; ++r)
-        if (((tact[(size_t)tm * W + (r >> 6)] & tact[(size_t)tn * W + (r >> 6)]) >> (r & 63)) & 1ull) {
-          if (seen + 4 > target) return 4 * r;
-          seen += 4;
-        }
-      return 0;
-    });
+    gf_install_tile_list(p, gf_tile_list_from_rows(tact.data(), W, g.nbg, nt, g.Gf / 16, gf_allow_parts(p)));
     p->gf.tile_list_age = 0;
   }
 }

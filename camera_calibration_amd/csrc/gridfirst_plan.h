@@ -21,6 +21,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <functional>
 #include <vector>
 
 #include "../../include/cba.h"
@@ -77,6 +78,30 @@ int gf_build_plan(const cba_camera* cams, int n_cameras, int n_images, int n_poi
 // imagesets that enlarge the tile's union (closed under the fill of the grid factor) least.  first_col: border index of slot 0's
 // first column (tiles are counted in border columns).
 void gf_order_imagesets(const GfPlan& plan, const std::vector<uint64_t>& touched_rows, int n_images, int first_col, std::vector<int>* slot_of_image);
+
+// Order in which the border update hands out its 128 x 128 tiles (GemmArgs::tile_list): workgroup b of the launch runs on XCD b % 8 and
+// the dispatcher hands workgroups out strictly in order, so (a) the list as a whole is sorted by executed K slabs, heaviest first --
+// list scheduling: the light tiles fill the gaps behind the heavy ones, and every XCD (every eighth entry) sees the same sequence of
+// weights, which keeps the in-order dispatcher from waiting for one XCD -- and (b) inside a run of tiles of about the same weight (7 %
+// buckets) the tiles are dealt so that one XCD walks a CONTIGUOUS piece of the run in row-major order: its tiles in flight share an A
+// panel and neighbouring B panels in that XCD's L2 instead of 64 unrelated pairs (FETCH_SIZE of the launch:
+// profiles/r06_update_tile_order.txt).  Short lists are padded with (-1, -1, 0, 0) (the workgroup leaves).  weight(tm, tn): executed K
+// slabs (or anything proportional) of upper tile (tm, tn), tm <= tn < nt.
+// A tile with all K slabs runs for most of the launch (2.7 of 3.5 ms at BASELINE configs[1]); tiles heavier than a third of the heaviest
+// (and than 8 slabs) are therefore handed out in PARTS (K ranges [s0, s1) with equal shares of the executed slabs, cut in front of slab
+// w q / parts) that add to C atomically -- allow_parts: not in the deterministic mode, where the additions must keep one order, and not
+// with image sharding, where every rank must factor F bit for bit alike.  parts = ceil(w / max(8, w_max / 3)) with the integer
+// quotient: up to FOUR (w_max = 25: ceil(25 / 8)), three when w_max is a multiple of 3.  split(tm, tn, target): the K slab in front of
+// which `target` units of the tile's weight lie; a split outside (previous cut, n_slabs) leaves the tile whole.  n_slabs: K slabs of
+// the launch.  Returns the entries (tm, tn, s0, s1), s1 = 0: the whole tile; a multiple of 8 of them (eight interleaved per-XCD lists).
+std::vector<int> gf_build_tile_list(int nt, int n_slabs, bool allow_parts, const std::function<int(int, int)>& weight,
+                                    const std::function<int(int, int, int)>& split);
+// The two sources of a list.  From the K-slab masks of a pass (gridfirst_finish): kmask = nt rows of `words` words, bit s = slab s of
+// the grid part is executed for a column of border tile t; weight = common bits.
+std::vector<int> gf_tile_list_from_kmask(const uint64_t* kmask, int words, int nt, int n_slabs, bool allow_parts);
+// From the activity of the grid block rows predicted by cba_set_observations (order_imagesets_gridfirst): rows = nt rows of `words`
+// words, bit r = block row r (< nbg) reaches border tile t; weight = four K slabs of 16 rows per common block row.
+std::vector<int> gf_tile_list_from_rows(const uint64_t* rows, int words, int nbg, int nt, int n_slabs, bool allow_parts);
 
 // Image sharding with the grid-first order: the ONE buffer of shared blocks that is all-reduced per Gauss-Newton
 // step -- [grid x grid, banded | rig / point rows x grid columns | rig rows x (rig, point) columns | 3 x 3 point blocks (upper) | J^T r of

@@ -253,6 +253,8 @@ _I8P, _SOPT = C.POINTER(C.c_int8), C.POINTER(CbaStereoOptions)
 # The same table for include/cba_diagnostics.h
 DIAGNOSTICS_PROTOTYPES = {
     "cba_debug_straggler_stats": (_I, [_VP, _I64P]),
+    "cba_debug_gridfirst_tile_list_query": (_I64, [_I32, _I32, _I32, C.POINTER(C.c_uint64), _I32, _I32, _I32P, _I64]),
+    "cba_debug_gridfirst_tile_list": (_I64, [_VP, _I32P, _I64, _I32P]),
 }
 STEREO_PROTOTYPES = {
     "cba_stereo_create": (_I, [_I32, _I32, _I32, _I32, _F32P, C.c_float, C.c_float, C.c_float, C.c_float, _I32, _I32, _F32P, _F32P, _I32,
@@ -342,6 +344,24 @@ def gridfirst_plan(cameras: Sequence[Camera], n_images: int, n_points: int, stri
     plan["shared"] = {k: int(v) for k, v in zip(["doubles", "off_rp_grid", "off_rig", "off_pp", "off_b", "G"], sh)}
     plan["shared"]["band_ref_col"] = q(8, np.int32)
     return plan
+
+
+def gridfirst_tile_list_query(mode: int, masks: np.ndarray, n_slabs: int, allow_parts: bool) -> np.ndarray:
+    """cba_debug_gridfirst_tile_list_query: the tile list of the border update that the library builds from `masks` (nt, words) uint64
+    (host only, no device) -- mode 0: K-slab masks, mode 1: block-row activity words.  Returns the entries (n, 4): tm, tn, s0, s1."""
+    L = load()
+    m = np.ascontiguousarray(masks, dtype=np.uint64)
+    assert m.ndim == 2
+    mp = m.ctypes.data_as(C.POINTER(C.c_uint64))
+    n = int(L.cba_debug_gridfirst_tile_list_query(int(mode), m.shape[0], m.shape[1], mp, int(n_slabs), int(bool(allow_parts)), None, 0))
+    if n < 0:
+        _check(n, "cba_debug_gridfirst_tile_list_query")
+    out = np.zeros((n, 4), dtype=np.int32)
+    if n:
+        got = int(L.cba_debug_gridfirst_tile_list_query(int(mode), m.shape[0], m.shape[1], mp, int(n_slabs), int(bool(allow_parts)),
+                                                        out.ctypes.data_as(_I32P), n))
+        assert got == n
+    return out
 
 
 def prepare(device: int = 0) -> None:
@@ -535,6 +555,18 @@ class Engine:
         out = (C.c_int64 * 5)()
         _check(self.L.cba_debug_straggler_stats(self._h, out), "cba_debug_straggler_stats")
         return dict(zip(("predicted", "listed", "period_1", "period_2_or_more", "full_budget"), (int(v) for v in out)))
+
+    def gridfirst_tile_list(self):
+        """cba_debug_gridfirst_tile_list: (entries (n, 4): tm, tn, s0, s1, info) of the problem's current host tile list of the border
+        update; info: valid, age (solves since cba_set_observations built the list), dirty (rebuilt since the last upload), n_slabs."""
+        info = (C.c_int32 * 4)()
+        n = int(self.L.cba_debug_gridfirst_tile_list(self._h, None, 0, info))
+        if n < 0:
+            _check(n, "cba_debug_gridfirst_tile_list")
+        out = np.zeros((n, 4), dtype=np.int32)
+        if n:
+            assert int(self.L.cba_debug_gridfirst_tile_list(self._h, out.ctypes.data_as(_I32P), n, info)) == n
+        return out, dict(valid=int(info[0]), age=int(info[1]), dirty=int(info[2]), n_slabs=int(info[3]))
 
     def debug_accumulate(self) -> float:
         cost = C.c_double(0)

@@ -19,6 +19,24 @@ extern "C" {
  * only the straggler kernel counts.  Waits for the pass. */
 int cba_debug_straggler_stats(cba_problem* p, int64_t out[5]);
 
+/* The tile list of the grid-first order's border update: entries of four ints (tm, tn, s0, s1) -- upper
+ * 128 x 128 tile (tm, tn) of the border, whole (s1 = 0) or the part over the K slabs [s0, s1) that is added to C atomically;
+ * (-1, -1, 0, 0) pads the eight interleaved per-XCD lists to one length.
+ *
+ * cba_debug_gridfirst_tile_list_query builds a list from the caller's words on the host and touches no device (like
+ * cba_gridfirst_plan_query).  mode 0: mask_words = nt rows of `words` words, bit s of row t = K slab s is executed for border tile
+ * t (what a solve builds its list from).  mode 1: bit r of row t = grid block row r reaches border tile t, four K slabs per block row
+ * (what cba_set_observations predicts the first list from).  n_slabs: K slabs of the launch; allow_parts: 0 = whole tiles only (the
+ * deterministic mode and image sharding).  Returns the number of entries, or an error code (< 0); `entries` is written if
+ * capacity_entries (in entries of four ints) is large enough.
+ *
+ * cba_debug_gridfirst_tile_list reads the CURRENT host list of a grid-first problem, also an image-sharded one: returns
+ * tile_list_entries (0 = no list yet), writes the entries under the same rule and info = {valid, age (solves since
+ * cba_set_observations built the list), dirty (rebuilt since the last upload), n_slabs}.  No device access. */
+int64_t cba_debug_gridfirst_tile_list_query(int32_t mode, int32_t nt, int32_t words, const uint64_t* mask_words, int32_t n_slabs,
+                                            int32_t allow_parts, int32_t* entries, int64_t capacity_entries);
+int64_t cba_debug_gridfirst_tile_list(cba_problem* p, int32_t* entries, int64_t capacity_entries, int32_t info[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -372,6 +372,19 @@ int launch_stereo_stage(const StereoArgs& a, int stage, hipStream_t s);
 int launch_stereo_cost(const StereoArgs& a, hipStream_t s);
 int launch_stereo_filter(const StereoArgs& a, hipStream_t s);
 
+// ---- kernels_stereo_post.hip (post-processing of a stereo depth map, the POST-PROCESSING section of include/cba_stereo.h) ----
+// One stage reads `in` (and cost_in, the median alone) and writes `out` (and cost_out), W H floats each, never the same array.
+struct StereoPostArgs {
+  int W, H, r;
+  const float* in; const float* cost_in; float* out; float* cost_out;
+  int radius; float denom_xy, denom_v;                        // the bilateral's
+  int* label; int* count; int min_size; float ratio;          // the components': W H ints each; min_size <= 0 keeps every component
+};
+static_assert(std::is_trivially_copyable_v<StereoPostArgs>);
+// stage: CBA_STEREO_POST_MEDIAN .. CBA_STEREO_POST_COMPONENTS (include/cba_stereo_post.h); launches over the image (the components:
+// four launches, or the clearing one alone when every component is kept)
+int launch_stereo_post(const StereoPostArgs& a, int stage, hipStream_t s);
+
 // ---- kernels_features.hip (refinement of star-pattern feature positions, include/cba_features.h) ----
 // n features, one workgroup each.  pattern_tr_pixel: the inverses of pixel_tr_pattern (9 n floats each, row-major); rendered:
 // n * (n_samples / 8) floats of working memory; matched / out_positions 2 n, final_cost / status n.

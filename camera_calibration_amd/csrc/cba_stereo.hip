@@ -1,10 +1,11 @@
 // Entry points of the C ABI (include/cba_stereo.h) behind the dense two-view stereo matcher: the cba_stereo_* handle.
-// Kernels: kernels_stereo.hip.
+// Kernels: kernels_stereo.hip, and kernels_stereo_post.hip for the post-processing (include/cba_stereo_post.h).
 #include <cmath>
 #include <memory>
 #include <utility>
 
 #include "../../include/cba_stereo.h"
+#include "../../include/cba_stereo_post.h"
 #include "cba_internal.h"
 
 using namespace cba;
@@ -24,6 +25,8 @@ struct cba_stereo {
   DevBuf<float> other, filtered;                // the filter's, allocated on first use
   DevBuf<float> tmp_inv_depth, tmp_cost;        // cba_stereo_cost's
   DevBuf<int8_t> tmp_normal;
+  DevBuf<float> post_map[2], post_cost[2];      // the post-processing's maps, allocated on first use
+  DevBuf<int> post_label, post_count;           // the components' parent pointers and sizes
 };
 }
 
@@ -76,6 +79,60 @@ int run_stage(cba_stereo* s, const cba_stereo_options* o, int stage, int pass) {
   CBA_TRY(launch_stereo_stage(a, stage, nullptr));
   if (stage == CBA_STEREO_PROPAGATION) s->cur = 1 - s->cur;
   return CBA_OK;
+}
+
+// cba_stereo_post_options with the defaults put in, and the bilateral's derived numbers (float, as the header writes them)
+struct PostParams { int radius, fill_iterations, min_size; float denom_xy, denom_v, ratio; };
+
+int check_post_options(const cba_stereo_post_options* po, const char* who, PostParams& q) {
+#pragma clang fp contract(off)
+  const std::string w(who);
+  if (!po) { set_error(w + ": bad argument"); return CBA_ERR_ARG; }
+  const float sigma_xy = po->bilateral_sigma_xy == 0 ? 1.5f : po->bilateral_sigma_xy;
+  const float factor = po->bilateral_radius_factor == 0 ? 2.0f : po->bilateral_radius_factor;
+  const float sigma_v = po->bilateral_sigma_inv_depth == 0 ? 0.005f : po->bilateral_sigma_inv_depth;
+  for (float v : {sigma_xy, factor, sigma_v})
+    if (!std::isfinite(v) || !(v > 0)) { set_error(w + ": a bilateral sigma or radius factor is not finite and positive"); return CBA_ERR_ARG; }
+  const float reach = factor * sigma_xy;
+  const float reach_half = reach + 0.5f;
+  if (!(reach_half < (float)(CBA_STEREO_POST_MAX_RADIUS + 1))) { set_error(w + ": bilateral radius above the cap"); return CBA_ERR_ARG; }
+  q.radius = (int)reach_half;
+  q.denom_xy = (2.f * sigma_xy) * sigma_xy; q.denom_v = (2.f * sigma_v) * sigma_v;
+  if (!(q.denom_xy > 0) || !(q.denom_v > 0) || !std::isfinite(q.denom_xy) || !std::isfinite(q.denom_v)) {
+    set_error(w + ": a bilateral sigma squared is not a positive float"); return CBA_ERR_ARG;
+  }
+  q.fill_iterations = po->hole_filling_iterations == 0 ? 3 : po->hole_filling_iterations == -1 ? 0 : po->hole_filling_iterations;
+  if (q.fill_iterations < 0 || q.fill_iterations > CBA_STEREO_POST_MAX_HOLE_FILLING_ITERATIONS) { set_error(w + ": bad hole_filling_iterations"); return CBA_ERR_ARG; }
+  q.min_size = po->min_component_size == 0 ? 50 : po->min_component_size == -1 ? 0 : po->min_component_size;
+  if (q.min_size < 0) { set_error(w + ": bad min_component_size"); return CBA_ERR_ARG; }
+  q.ratio = po->similar_depth_ratio == 0 ? 1.005f : po->similar_depth_ratio;
+  if (!(q.ratio >= 1)) { set_error(w + ": similar_depth_ratio < 1"); return CBA_ERR_ARG; }
+  return CBA_OK;
+}
+
+StereoPostArgs post_args(const cba_stereo* s, const cba_stereo_options* o, const PostParams& q) {
+  StereoPostArgs a{};
+  a.W = s->W; a.H = s->H; a.r = o->context_radius;
+  a.radius = q.radius; a.denom_xy = q.denom_xy; a.denom_v = q.denom_v;
+  a.label = s->post_label; a.count = s->post_count; a.min_size = q.min_size; a.ratio = q.ratio;
+  return a;
+}
+
+int reserve_post(cba_stereo* s, bool costs, bool components) {
+  const size_t n = (size_t)s->W * s->H;
+  for (int b = 0; b < 2; ++b) {
+    CBA_TRY(s->post_map[b].reserve(n));
+    if (costs) CBA_TRY(s->post_cost[b].reserve(n));
+  }
+  if (components) { CBA_TRY(s->post_label.reserve(n)); CBA_TRY(s->post_count.reserve(n)); }
+  return CBA_OK;
+}
+
+// one post-processing stage from `in` to `out` on the null stream
+int run_post(const StereoPostArgs& base, int stage, const float* in, const float* cost_in, float* out, float* cost_out) {
+  StereoPostArgs a = base;
+  a.in = in; a.cost_in = cost_in; a.out = out; a.cost_out = cost_out;
+  return launch_stereo_post(a, stage, nullptr);
 }
 
 }  // namespace
@@ -196,6 +253,57 @@ int cba_stereo_filter(cba_stereo* s, const cba_stereo_options* o, const float* o
   }
   CBA_TRY(launch_stereo_filter(a, nullptr));
   return s->filtered.download(out, n);
+}
+
+int cba_stereo_post_stage(cba_stereo* s, const cba_stereo_options* o, const cba_stereo_post_options* po, int32_t stage,
+                          const float* inv_depth_in, const float* cost_in, float* inv_depth_out, float* cost_out) {
+  CBA_TRY(check_options(s, o, "cba_stereo_post_stage"));
+  PostParams q;
+  CBA_TRY(check_post_options(po, "cba_stereo_post_stage", q));
+  if (stage < CBA_STEREO_POST_MEDIAN || stage > CBA_STEREO_POST_COMPONENTS) { set_error("cba_stereo_post_stage: unknown stage"); return CBA_ERR_ARG; }
+  const bool median = stage == CBA_STEREO_POST_MEDIAN;
+  if (!inv_depth_in || !inv_depth_out || (median && (!cost_in || !cost_out))) { set_error("cba_stereo_post_stage: bad argument"); return CBA_ERR_ARG; }
+  CBA_HIP(hipSetDevice(s->device));
+  const size_t n = (size_t)s->W * s->H;
+  CBA_TRY(reserve_post(s, median, stage == CBA_STEREO_POST_COMPONENTS));
+  CBA_TRY(s->post_map[0].upload(inv_depth_in, n));
+  if (median) CBA_TRY(s->post_cost[0].upload(cost_in, n));
+  CBA_TRY(run_post(post_args(s, o, q), stage, s->post_map[0], median ? (const float*)s->post_cost[0] : nullptr, s->post_map[1],
+                   median ? (float*)s->post_cost[1] : nullptr));
+  CBA_TRY(s->post_map[1].download(inv_depth_out, n));
+  return median ? s->post_cost[1].download(cost_out, n) : CBA_OK;
+}
+
+int cba_stereo_finish(cba_stereo* s, const cba_stereo_options* o, const cba_stereo_post_options* po,
+                      const float* other_inv_depth, float* out) {
+  CBA_TRY(check_options(s, o, "cba_stereo_finish"));
+  PostParams q;
+  CBA_TRY(check_post_options(po, "cba_stereo_finish", q));
+  if (!out) { set_error("cba_stereo_finish: bad argument"); return CBA_ERR_ARG; }
+  CBA_HIP(hipSetDevice(s->device));
+  const size_t n = (size_t)s->W * s->H, ns = (size_t)s->Ws * s->Hs;
+  CBA_TRY(reserve_post(s, false, true));
+  CBA_TRY(s->filtered.reserve(n));
+  if (other_inv_depth) {
+    CBA_TRY(s->other.reserve(ns));
+    CBA_TRY(s->other.upload(other_inv_depth, ns));
+  }
+  const StereoPostArgs pa = post_args(s, o, q);
+  // the median of the state goes to the second buffers of inv_depth and cost, which then become the state's; the normals stay
+  const int cur = s->cur, nxt = 1 - s->cur;
+  CBA_TRY(run_post(pa, CBA_STEREO_POST_MEDIAN, s->inv_depth[cur], s->cost[cur], s->inv_depth[nxt], s->cost[nxt]));
+  std::swap(s->inv_depth[cur], s->inv_depth[nxt]);
+  std::swap(s->cost[cur], s->cost[nxt]);
+  StereoArgs a = stereo_args(s, o);
+  a.filtered = s->filtered;
+  if (other_inv_depth) a.other_inv_depth = s->other;
+  CBA_TRY(launch_stereo_filter(a, nullptr));
+  CBA_TRY(run_post(pa, CBA_STEREO_POST_BILATERAL, s->filtered, nullptr, s->post_map[0], nullptr));
+  int at = 0;
+  for (int it = 0; it < q.fill_iterations; ++it, at = 1 - at)
+    CBA_TRY(run_post(pa, CBA_STEREO_POST_FILL_HOLES, s->post_map[at], nullptr, s->post_map[1 - at], nullptr));
+  CBA_TRY(run_post(pa, CBA_STEREO_POST_COMPONENTS, s->post_map[at], nullptr, s->post_map[1 - at], nullptr));
+  return s->post_map[1 - at].download(out, n);
 }
 
 }  // extern "C"

@@ -271,6 +271,21 @@ STEREO_PROTOTYPES = {
 }
 STEREO_INIT, STEREO_MUTATION, STEREO_PROPAGATION, STEREO_REFINEMENT = 0, 1, 2, 3
 
+
+class CbaStereoPostOptions(C.Structure):
+    _fields_ = [("bilateral_sigma_xy", C.c_float), ("bilateral_radius_factor", C.c_float), ("bilateral_sigma_inv_depth", C.c_float),
+                ("hole_filling_iterations", C.c_int32), ("min_component_size", C.c_int32), ("similar_depth_ratio", C.c_float)]
+
+
+# The same table for include/cba_stereo_post.h (tests/test_stereo_post_cases.py checks it against that header)
+_SPOPT = C.POINTER(CbaStereoPostOptions)
+STEREO_POST_PROTOTYPES = {
+    "cba_stereo_post_stage": (_I, [_VP, _SOPT, _SPOPT, _I32, _F32P, _F32P, _F32P, _F32P]),
+    "cba_stereo_finish": (_I, [_VP, _SOPT, _SPOPT, _F32P, _F32P]),
+}
+STEREO_POST_MEDIAN, STEREO_POST_BILATERAL, STEREO_POST_FILL_HOLES, STEREO_POST_COMPONENTS = 0, 1, 2, 3
+STEREO_POST_MAX_RADIUS = 32
+
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
 DUMP_BLOCK_DIAG_H, DUMP_BLOCK_DIAG_B, DUMP_OFF_DIAG_H, DUMP_DENSE_H, DUMP_DENSE_B, DUMP_X = 5, 6, 7, 8, 9, 10
 DUMP_TEST_COST_VECTOR = 11
@@ -302,7 +317,8 @@ def load() -> C.CDLL:
         raise EngineError(f"{LIB_PATH} is missing -- run `python -c 'import __graft_entry__ as g; g.build()'`; "
                           "the engine has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **UNDISTORT_PROTOTYPES, **STEREO_PROTOTYPES, **DIAGNOSTICS_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **UNDISTORT_PROTOTYPES, **STEREO_PROTOTYPES, **STEREO_POST_PROTOTYPES,
+                                      **DIAGNOSTICS_PROTOTYPES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -959,6 +975,14 @@ def stereo_options(context_radius: int = 10, iterations: int = 50, min_depth: fl
                             float(cost_threshold), float(angle_threshold), float(lr_consistency_factor_threshold), int(seed) & (2 ** 64 - 1))
 
 
+def stereo_post_options(bilateral_sigma_xy: float = 1.5, bilateral_radius_factor: float = 2.0, bilateral_sigma_inv_depth: float = 0.005,
+                        hole_filling_iterations: int = 3, min_component_size: int = 50, similar_depth_ratio: float = 1.005) -> CbaStereoPostOptions:
+    """cba_stereo_post_options (include/cba_stereo_post.h; a 0 selects the member's default, -1 no hole filling / every component kept);
+    the defaults are the reference matcher's and its tool's."""
+    return CbaStereoPostOptions(float(bilateral_sigma_xy), float(bilateral_radius_factor), float(bilateral_sigma_inv_depth),
+                                int(hole_filling_iterations), int(min_component_size), float(similar_depth_ratio))
+
+
 class StereoHandle:
     """cba_stereo (include/cba_stereo.h): one matching direction on the device.  unprojection (H, W, 2) and projection (PH, PW, 2)
     float32, grid = (fx, fy, cx, cy) of the projection lookup's pinhole, stereo_tr_reference 12 floats (row-major 3 x 4)."""
@@ -1040,6 +1064,36 @@ class StereoHandle:
         out = np.zeros((self.height, self.width), dtype=np.float32)
         _check(self.L.cba_stereo_filter(self._h, C.byref(options), other.ctypes.data_as(_F32P) if other is not None else None,
                                         out.ctypes.data_as(_F32P)), "cba_stereo_filter")
+        return out
+
+    def _other_map(self, other_inv_depth, who: str):
+        if other_inv_depth is None:
+            return None
+        other = np.ascontiguousarray(other_inv_depth, dtype=np.float32)
+        if other.shape != (self.stereo_height, self.stereo_width):
+            raise ValueError(f"StereoHandle.{who}: the other direction's map has the stereo image's size")
+        return other
+
+    def post_stage(self, options: CbaStereoOptions, post_options: CbaStereoPostOptions, stage: int, inv_depth, cost=None):
+        """cba_stereo_post_stage: one post-processing stage on a given map; the state is not touched.  Returns the map, and for the
+        median (which needs `cost`) the pair (map, cost)."""
+        d = np.ascontiguousarray(inv_depth, dtype=np.float32)
+        c = None if cost is None else np.ascontiguousarray(cost, dtype=np.float32)
+        if d.shape != (self.height, self.width) or (c is not None and c.shape != d.shape):
+            raise ValueError("StereoHandle.post_stage: maps of the reference image's size")
+        out = np.zeros_like(d)
+        cost_out = None if c is None else np.zeros_like(d)
+        _check(self.L.cba_stereo_post_stage(self._h, C.byref(options), C.byref(post_options), int(stage), d.ctypes.data_as(_F32P),
+                                            c.ctypes.data_as(_F32P) if c is not None else None, out.ctypes.data_as(_F32P),
+                                            cost_out.ctypes.data_as(_F32P) if c is not None else None), "cba_stereo_post_stage")
+        return out if c is None else (out, cost_out)
+
+    def finish(self, options: CbaStereoOptions, post_options: CbaStereoPostOptions, other_inv_depth: Optional[np.ndarray] = None) -> np.ndarray:
+        """cba_stereo_finish: median of the state, filter, bilateral, hole filling, components, all on the device."""
+        other = self._other_map(other_inv_depth, "finish")
+        out = np.zeros((self.height, self.width), dtype=np.float32)
+        _check(self.L.cba_stereo_finish(self._h, C.byref(options), C.byref(post_options),
+                                        other.ctypes.data_as(_F32P) if other is not None else None, out.ctypes.data_as(_F32P)), "cba_stereo_finish")
         return out
 
 

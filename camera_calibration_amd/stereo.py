@@ -11,16 +11,18 @@ the reference draws from curand and its propagation races); tests/stereo_referen
   ``cba_stereo_create``.
 * ``StereoMatcher``      -- two ``engine.StereoHandle`` (this direction and the other one).  ``compute(reference_image, stereo_image)``
   is the tool's sequence: the other direction with 30 iterations, filtered; this direction with 50, filtered against the other
-  direction's map; small components removed from both.
+  direction's map; small components removed from both.  With ``StereoOptions.postprocess`` each direction's filter and component
+  removal are replaced by ``StereoHandle.finish``: the reference's whole chain after the matching (3 x 3 median, filter, bilateral
+  filter, hole filling, components) on the device, include/cba_stereo_post.h.
 * ``remove_small_components`` -- host, from the rule: 4-connected components of valid inner pixels, neighbours joined when the ratio of
   their inverse depths (inverted when below 1) is below `similar_depth_ratio`; components smaller than `min_component_size` are set to 0.
 * ``stereo_depth_estimation`` -- a saved state with exactly two central-generic cameras -> ``metadata.yaml``, ``depth_image.bin``,
   ``point_cloud.ply``, the reference's three files.
 
-Not built: the second-best pass, the median and bilateral filters, hole filling, the epipolar-gradient and required-range tests, more
-than two views, masks, the thin-prism branch of the tool; non-central cameras are refused.
+Not built: the second-best pass, the epipolar-gradient and required-range tests, more than two views, masks, the thin-prism branch of
+the tool; non-central cameras are refused.
 
-CLI: ``python -m camera_calibration_amd.stereo --state_directory DIR --images a.png,b.png --output_directory OUT``.
+CLI: ``python -m camera_calibration_amd.stereo --state_directory DIR --images a.png,b.png --output_directory OUT [--postprocess]``.
 """
 from __future__ import annotations
 
@@ -57,10 +59,23 @@ class StereoOptions:
     similar_depth_ratio: float = 1.005
     lookup_scale: float = 1.0
     seed: int = 0
+    # the rest of ComputeDepthMap on the device (median, bilateral, hole filling, components: include/cba_stereo_post.h); off = the
+    # filter alone and the host's component removal
+    postprocess: bool = False
+    bilateral_sigma_xy: float = 1.5
+    bilateral_radius_factor: float = 2.0
+    bilateral_sigma_inv_depth: float = 0.005
+    hole_filling_iterations: int = 3          # 0 = none
 
     def engine_options(self, iterations: int) -> "_engine.CbaStereoOptions":
         return _engine.stereo_options(self.context_radius, iterations, self.min_depth, self.max_depth, self.max_normal_2d_length,
                                       self.cost_threshold, self.angle_threshold, self.lr_consistency_factor_threshold, self.seed)
+
+    def engine_post_options(self) -> "_engine.CbaStereoPostOptions":
+        """The C structure reads 0 as "the default": no hole filling and "keep every component" are its -1."""
+        return _engine.stereo_post_options(self.bilateral_sigma_xy, self.bilateral_radius_factor, self.bilateral_sigma_inv_depth,
+                                           self.hole_filling_iterations if self.hole_filling_iterations > 0 else -1,
+                                           self.min_component_size if self.min_component_size > 1 else -1, self.similar_depth_ratio)
 
 
 def unprojection_lookup(directions: np.ndarray, ok: np.ndarray) -> np.ndarray:
@@ -195,6 +210,15 @@ class StereoMatcher:
     def compute(self, reference_image: np.ndarray, stereo_image: np.ndarray, return_other: bool = False):
         """(H, W) float32 inverse depth of the reference image, 0 where invalid."""
         o = self.options
+        if o.postprocess:                    # both directions through the device chain; the host's component removal is not called
+            po = o.engine_post_options()
+            self.backward.set_images(stereo_image, reference_image)
+            self.backward.match(o.engine_options(o.consistency_iterations))
+            other = self.backward.finish(o.engine_options(o.consistency_iterations), po, None)
+            self.forward.set_images(reference_image, stereo_image)
+            self.forward.match(o.engine_options(o.iterations))
+            out = self.forward.finish(o.engine_options(o.iterations), po, other)
+            return (out, other) if return_other else out
         self.backward.set_images(stereo_image, reference_image)
         self.backward.match(o.engine_options(o.consistency_iterations))
         other = self._clean(self.backward.filter(o.engine_options(o.consistency_iterations), None))
@@ -295,10 +319,12 @@ def main(argv=None) -> int:
     ap.add_argument("--lookup_scale", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--postprocess", action="store_true",
+                    help="median, bilateral filter, hole filling and component removal on the device (the rest of the reference's pipeline)")
     args = ap.parse_args(argv)
     try:
         o = StereoOptions(context_radius=args.context_radius, min_depth=args.min_depth, max_depth=args.max_depth,
-                          lookup_scale=args.lookup_scale, seed=args.seed)
+                          lookup_scale=args.lookup_scale, seed=args.seed, postprocess=args.postprocess)
         m = stereo_depth_estimation(args.state_directory, [p for p in args.images.split(",") if p], args.output_directory, o, device=args.device)
     except (ValueError, OSError, KeyError) as e:
         print(e, file=sys.stderr)

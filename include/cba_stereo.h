@@ -70,10 +70,40 @@
  *   with another direction's map (Ws x Hs), kernel_consistency.cu:42-97: depth = 1 / inv_depth, t = M (depth c.x, depth c.y, depth),
  *     t_z > 0, s = the projection of t as in the cost, q = (s.x + 0.5f, s.y + 0.5f) with r <= q.x < Ws - 1 - r, r <= q.y < Hs - 1 - r,
  *     l = other[(int)q.y Ws + (int)q.x] != 0, f = t_z l, f = 1 / f if f < 1, f <= lr_consistency_factor_threshold.
- * Small connected components are removed by the caller on the host.
+ * Small connected components are removed by the caller on the host, or by the COMPONENTS stage below.
  *
- * NOT BUILT: the second-best pass, the median and bilateral filters, hole filling, the epipolar-gradient and required-range tests,
- * more than two views, masks, the thin-prism branch of the tool, non-central cameras.
+ * POST-PROCESSING (declared in cba_stereo_post.h; libvis/cuda/patch_match_stereo.cu and ComputeDepthMap's order: median, the FILTER
+ * above, bilateral, hole filling, components).  "Invalid" is inv_depth == 0.  Every stage reads one map and writes another and never
+ * reads what its own launch writes.  A pixel outside the inner region ALWAYS GETS 0 (and cost NaN where a cost is written): the one
+ * exception to "the state outside it is never changed" is cba_stereo_finish, whose median leaves 0 / NaN there.  The arithmetic rule
+ * above holds; the one operation outside it is the bilateral's fp64 exp.
+ *   MEDIAN (:41-143, without the second-best cost)  an invalid inner pixel stays invalid, cost NaN.  Otherwise gather (inv_depth,
+ *     cost) pairs: THE CENTRE FIRST, then the valid ones of its eight neighbours THAT LIE IN THE INNER REGION in row-major order (dy
+ *     outer, dx inner).  Partial selection: for i = 0..4, for k = i + 1 .. count - 1: swap pairs i and k if d[i] > d[k], STRICTLY (a
+ *     tie never swaps, so among equal depths the gather order decides whose cost is taken).  Odd count: entry count / 2.  Even count:
+ *     avg = 0.5f (d[count/2 - 1] + d[count/2]); the lower entry only if fabsf(avg - lower) < fabsf(avg - upper), else the upper one
+ *     (so the upper one when both are equally near).  The cost written is the chosen entry's; it may be NaN.
+ *   BILATERAL (:172-225)  radius = (int)(radius_factor sigma_xy + 0.5f), denom_xy = (2.f sigma_xy) sigma_xy, denom_v = (2.f sigma_v)
+ *     sigma_v.  An invalid centre stays 0.  Otherwise the samples of the window [x - radius, x + radius] x [y - radius, y + radius]
+ *     CLIPPED TO THE IMAGE (not to the inner region: after the FILTER the map is 0 outside it anyway) are visited in row-major order;
+ *     those with g = dx dx + dy dy > radius radius and the invalid ones are skipped.  For the others v = centre - sample,
+ *     a = (-(float)g / denom_xy) + (-(v v) / denom_v), w = (float)exp((double)a), sum += w sample, weight += w (float sums; the
+ *     centre itself has w = 1, so weight is never 0).  Result sum / weight.  DEVIATION: the reference calls CUDA's float exp.  Two
+ *     fp64 exp implementations may differ in the last place, so this stage alone is not bit-reproducible against numpy.
+ *   FILL_HOLES, one round (:254-328)  a valid inner pixel keeps its value.  For an invalid one, over its valid 8-neighbours THAT LIE
+ *     IN THE INNER REGION in row-major order: avg = (float sum) / (float)count (no valid neighbour: 0 / 0 = NaN, and the pixel stays 0);
+ *     then over the same neighbours f = d / avg, f = 1 / f if f < 1, and those with f <= 1.01f are summed and counted again; with at
+ *     least 6 of them the pixel gets sum / (float)count, else it stays 0.  The reference runs over the image minus a one-pixel rim;
+ *     its input is 0 outside the inner region, where a pixel has at most three neighbours inside and can never be filled: the same
+ *     rule, and nothing outside the inner region is touched.
+ *   COMPONENTS  4-connectivity inside the inner region; a valid pixel a and its valid right or lower neighbour b are joined if
+ *     q = a / b, q = 1 / q if q < 1, q < similar_depth_ratio, STRICTLY; components of fewer than min_component_size pixels are set to 0
+ *     (stereo.remove_small_components is the same rule on the host).  Labels are unions by integer atomicMin on roots (a component's
+ *     label is its smallest pixel index), a compression pass, integer atomicAdd counts per root and a clearing pass: integer atomics
+ *     only, so the result does not depend on scheduling.
+ *
+ * NOT BUILT: the second-best pass, the epipolar-gradient and required-range tests, the reference's depth-difference normal in the
+ * angle test, more than two views, masks, the thin-prism branch of the tool, non-central cameras.
  */
 #ifndef CBA_STEREO_H_
 #define CBA_STEREO_H_

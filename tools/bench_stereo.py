@@ -7,10 +7,14 @@ the other tools use, context radius 10, the tool's depth range.
   before each window is the same: init, then two iterations (mutation, propagation), restored with set_state.
 * filter: host clock around cba_stereo_filter without the left-right map (it ends in the download of the map).
 
-No threshold is set on these figures: there is no earlier code and no AMD build of the reference to compare with.  Writes the
-"stage_times" entry of profiles/stereo.json (the other entries are kept) and prints it.
+* post-processing (post_times): host clock around each stage of include/cba_stereo_post.h, around the two ways of removing small
+  components (the host's numpy rule, which is the parent path and the yardstick, and the device stage) and around the whole chain.
 
-    python tools/bench_stereo.py [--out profiles/stereo.json] [--width 1920 --height 1200 --grid 84 60 --radius 10]
+No threshold is set on these figures: there is no earlier code and no AMD build of the reference to compare with.  Writes the
+"stage_times" entry of profiles/stereo.json and of profiles/stereo_postprocess.json (the other entries are kept) and prints them.
+
+    python tools/bench_stereo.py [--out profiles/stereo.json] [--post_out profiles/stereo_postprocess.json]
+                                 [--width 1920 --height 1200 --grid 84 60 --radius 10]
 """
 import argparse
 import json
@@ -49,9 +53,47 @@ def _image(h, w, seed):
     return np.clip(v + 0.5, 0, 255).astype(np.uint8)
 
 
+def _host_clock(fn, repeats):
+    seconds = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        out = fn()
+        seconds.append(time.perf_counter() - t0)
+    return out, dict(seconds=seconds, median=float(np.median(seconds)))
+
+
+def post_times(h, o, r, repeats=3):
+    """Host clock (every call ends in the download of its result) around the post-processing of the matched state `h` holds:
+    each stage through cba_stereo_post_stage (which also uploads its input), the two ways of removing small components from the same
+    filtered map (stereo.remove_small_components on the host, the parent commit's path and the yardstick, once; the COMPONENTS stage on
+    the device), and the whole chain (cba_stereo_finish) next to the filter plus the host's component removal."""
+    po = engine.stereo_post_options()
+    state = h.get_state()
+    filtered = h.filter(o, None)
+    rows = {}
+    (med, med_cost), rows["median"] = _host_clock(lambda: h.post_stage(o, po, engine.STEREO_POST_MEDIAN, state[0], state[2]), repeats)
+    bil, rows["bilateral"] = _host_clock(lambda: h.post_stage(o, po, engine.STEREO_POST_BILATERAL, filtered), repeats)
+    _, rows["fill_holes_one_round"] = _host_clock(lambda: h.post_stage(o, po, engine.STEREO_POST_FILL_HOLES, bil), repeats)
+    dev, rows["components_device"] = _host_clock(lambda: h.post_stage(o, po, engine.STEREO_POST_COMPONENTS, filtered), repeats)
+    host, rows["components_host_numpy"] = _host_clock(lambda: stereo.remove_small_components(filtered, r, 50, 1.005), 1)
+    same = bool(np.array_equal(dev.view(np.uint32), host.view(np.uint32)))
+
+    def chain():
+        h.set_state(*state)
+        return h.finish(o, po, None)
+    _, rows["finish_with_set_state"] = _host_clock(chain, repeats)
+    _, rows["set_state"] = _host_clock(lambda: h.set_state(*state), repeats)
+    _, rows["filter_with_download"] = _host_clock(lambda: h.filter(o, None), repeats)
+    return dict(stages=rows, valid_pixels_of_the_filtered_map=int((filtered != 0).sum()), device_components_equal_host=same,
+                note="host clock; every post_stage call uploads its input and downloads its result; finish_with_set_state includes "
+                     "the set_state that restores the matched state before each call (set_state is timed alone next to it)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join("profiles", "stereo.json"))
+    ap.add_argument("--post_out", default=os.path.join("profiles", "stereo_postprocess.json"),
+                    help="where the post-processing times go ('' = do not measure them)")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1200)
     ap.add_argument("--grid", type=int, nargs=2, default=[84, 60])
@@ -101,7 +143,20 @@ def main():
         t0 = time.perf_counter()
         h.filter(o, None)
         seconds.append(time.perf_counter() - t0)
+    post = post_times(h, o, r) if args.post_out else None
     h.close()
+    if post is not None:
+        post.update(image=[W, H], context_radius=r)
+        merged = {}
+        if os.path.exists(args.post_out):
+            with open(args.post_out) as f:
+                merged = json.load(f)
+        merged["stage_times"] = post
+        os.makedirs(os.path.dirname(os.path.abspath(args.post_out)), exist_ok=True)
+        with open(args.post_out, "w") as f:
+            json.dump(merged, f, indent=1)
+            f.write("\n")
+        print(json.dumps(post))
     result = dict(image=[W, H], grid=list(args.grid), context_radius=r, inner_pixels=inner, launches_per_window=args.launches,
                   windows=args.repeats, lookups_seconds=lookups_seconds, stages=rows,
                   filter_with_download=dict(seconds=seconds, median=float(np.median(seconds))),

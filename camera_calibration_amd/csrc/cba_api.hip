@@ -102,6 +102,8 @@ int cba_create(const cba_config* config, cba_problem** out) {
   CBA_TRY(alloc_system(p.get()));
   CBA_TRY(alloc_reduce_buffer(p.get(), config));
   CBA_TRY(setup_gf_sharding(p.get()));
+  hdd_clear_list_host(p.get());
+  CBA_TRY(upload_hdd_clear_list(p.get()));
   CBA_TRY(alloc_ldlt_workspace(p.get()));
   *out = p.release();
   return CBA_OK;
@@ -569,6 +571,43 @@ int cba_debug_straggler_stats(cba_problem* p, int64_t out[5]) {
   out[0] = 0;                                                  // no pass keeps a prediction
   out[1] = v[kSlowListCount] < p->slow.cap ? v[kSlowListCount] : p->slow.cap;
   out[2] = v[kSlowStatPeriod1]; out[3] = v[kSlowStatPeriodN]; out[4] = v[kSlowStatFullBudget];
+  return CBA_OK;
+}
+
+// ---- cba_diagnostics.h: the clear list of H_dd (tests/test_hdd_clear_list.py, test_gpu_hdd_clear.py) ----
+static int64_t give_hdd_clear_list(const cba_problem* p, int32_t* segments, int64_t capacity_segments, int64_t info[4]) {
+  const int64_t n = (int64_t)p->hddc.segs.size();
+  if (info) {
+    int n_pad = 0, n_fact = 0;
+    padded_dims(p->L.dense_dof, &n_pad, &n_fact);
+    info[0] = n_pad; info[1] = p->L.dense_dof; info[2] = p->hddc.entries; info[3] = p->hddc.selective ? 1 : 0;
+  }
+  if (segments && capacity_segments >= n)
+    for (int64_t i = 0; i < n; ++i) { segments[3 * i] = p->hddc.segs[i].row; segments[3 * i + 1] = p->hddc.segs[i].col; segments[3 * i + 2] = p->hddc.segs[i].len; }
+  return n;
+}
+int64_t cba_debug_hdd_clear_list_query(const cba_config* config, int32_t* segments, int64_t capacity_segments, int64_t info[4]) {
+  CBA_TRY(check_config(config));
+  cba_problem tmp;            // the host half of cba_create: layout, elimination order, grid order -- no device buffer is allocated
+  tmp.cfg = *config;
+  tmp.cams.assign(config->cameras, config->cameras + config->n_cameras);
+  tmp.cfg.cameras = tmp.cams.data();
+  make_layout(tmp.cfg, tmp.L);
+  if (tmp.L.total_dof <= 0) { set_error("empty problem"); return CBA_ERR_ARG; }
+  CBA_TRY(choose_elimination_order(&tmp, config));
+  grid_order_host(&tmp);
+  hdd_clear_list_host(&tmp);
+  return give_hdd_clear_list(&tmp, segments, capacity_segments, info);
+}
+int64_t cba_debug_hdd_clear_list(cba_problem* p, int32_t* segments, int64_t capacity_segments, int64_t info[4]) {
+  if (!p) { set_error("cba_debug_hdd_clear_list: bad argument"); return CBA_ERR_ARG; }
+  const int64_t n = give_hdd_clear_list(p, segments, capacity_segments, info);
+  if (info) info[3] = (p->hddc.selective && !p->hddc.force_full) ? 1 : 0;
+  return n;
+}
+int cba_debug_set_hdd_full_clear(cba_problem* p, int32_t on) {
+  if (!p) { set_error("cba_debug_set_hdd_full_clear: bad argument"); return CBA_ERR_ARG; }
+  p->hddc.force_full = on != 0;
   return CBA_OK;
 }
 

@@ -243,6 +243,11 @@ int launch_reduce_costs(const double* ref, const double* test, const uint8_t* fl
 int launch_apply_update(const Layout& L, const std::vector<cba_camera>& cams, const DevState& in, const double* x,
                         DevState& out, const int* pose_slot, int* const* gperm, hipStream_t s);
 int launch_update_direction_grid(const double* in, const double* x, int G, double* out, hipStream_t s);
+// A piece of a row segment of H_dd (hdd_clear_list.h): `len` doubles from element `off`.  det_scale = null: the pieces are cleared;
+// else they are converted from the fixed-point sums of the deterministic mode (launch_det_convert on the pieces)
+struct HddPiece { long long off; int len, pad; };
+constexpr int kHddPieceMax = 1024;
+int launch_hdd_segments(double* H, const HddPiece* pieces, int n_pieces, const double* det_scale, hipStream_t s);
 // ---- kernels_fit.hip (grid-only LM) ----
 int launch_fit_pass(bool jac, int gw, int gh, const double* grid, const double* tang, int64_t n, const double* gp,
                     const double* dirs, double* cost_vec, double* rec, int* keys, int* status, hipStream_t s);

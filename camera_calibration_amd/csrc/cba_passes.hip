@@ -101,8 +101,8 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   CBA_TRY(timer_begin(p, kTimerFd));
   CBA_TRY(launch_fd_tasks(a, p->model_mask, L.localize_only, p->out, p->fd, kFdMainList, p->stream));
   CBA_TRY(timer_end(p, kTimerFd, 0, 0, 1));
-  // Third stream: the accumulation targets are cleared (1.3 GB for H_dd at cfg 2) underneath the finite-difference launch.  Round 3
-  // issued the memsets first, on the side stream: the 0.2 ms fill of H_dd then held the chip before the base projection of the pass
+  // Third stream: the accumulation targets are cleared (0.45 GB for S0 at cfg 2) underneath the finite-difference launch.  Round 3
+  // issued the memsets first, on the side stream: the 0.2 ms fill of the whole of H_dd (1.3 GB) then held the chip before the base projection of the pass
   // got a workgroup slot (profiles/r04_v2_step_timeline_cfg2.txt: base projection 0.25 ms after the tangents); queued behind the
   // VALU-bound FD kernel the fill's workgroups take slots as they come free.
   CBA_HIP(hipStreamWaitEvent(clr, p->ev_aux2, 0));            // behind the base projection of this pass
@@ -112,7 +112,11 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
     CBA_TRY(p->sys.B.zero_async(clr));
   else                                // padding rows of B (the strips below overwrite everything else, zeros included)
     CBA_TRY(p->sys.B.zero_async((size_t)(p->sys.Kpad - L.block_dof) * p->sys.n_pad, clr, (size_t)L.block_dof * p->sys.n_pad));
-  CBA_TRY(p->sys.Hdd.zero_async(clr));
+  // H_dd: only the row segments a pass can write (hdd_clear_list.h; 3.8 MB of the 1.28 GB at cfg 2) -- everything else is still the
+  // zero it was allocated with (profiles/jacobian_pass_clears.json).
+  const bool hdd_list = p->hddc.selective && !p->hddc.force_full;
+  if (hdd_list) CBA_TRY(launch_hdd_segments(p->sys.Hdd, p->hddc.pieces, p->hddc.n_pieces, nullptr, clr));
+  else CBA_TRY(p->sys.Hdd.zero_async(clr));
   CBA_TRY(p->sys.bd.zero_async(clr));
   if (p->gf.S0) CBA_TRY(p->gf.S0.zero_async(clr));      // grid-first order: the strips of F (the accumulation stores only what it reaches)
   CBA_HIP(hipEventRecord(p->ev_clear, clr));
@@ -155,7 +159,8 @@ int jacobian_pass_and_accumulate(cba_problem* p, double* t_acc) {
   if (det) {   // fixed point -> fp64, in place
     CBA_TRY(launch_det_convert(p->sys.Dblk, nb * bs * bs, det, p->stream));
     CBA_TRY(launch_det_convert(p->sys.bblk, nb * bs, det + 1, p->stream));      // J^T r: second scale
-    CBA_TRY(launch_det_convert(p->sys.Hdd, (size_t)L.dense_dof * p->sys.n_pad, det, p->stream));
+    if (hdd_list) CBA_TRY(launch_hdd_segments(p->sys.Hdd, p->hddc.pieces, p->hddc.n_pieces, det, p->stream));
+    else CBA_TRY(launch_det_convert(p->sys.Hdd, (size_t)L.dense_dof * p->sys.n_pad, det, p->stream));
     CBA_TRY(launch_det_convert(p->sys.bd, (size_t)p->sys.n_pad, det + 1, p->stream));
     CBA_TRY(launch_det_convert(p->sys.B, (size_t)L.block_dof * p->sys.n_pad, det, p->stream));   // strips store integers, the pose x rig atomics add to them
     if (p->gf.S0) CBA_TRY(launch_det_convert(p->gf.S0, p->gf.S0.size(), det, p->stream));

@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "cba_internal.h"
+#include "hdd_clear_list.h"
 
 using namespace cba;      // (cba_problem is the C ABI's struct: it lives outside the namespace)
 
@@ -78,6 +79,14 @@ struct GfShardState {
   DevBuf<double> gDblk, gbblk, gB;          // pose rows of ALL ranks (border order)
   DevBuf<double> gsend, grecv; int64_t gblk = 0;                   // all-gather staging: [words | D | b | B] of one rank, padded
 };
+// Clear of H_dd per Jacobian pass (hdd_clear_list.h): H_dd is allocated zeroed, and where the entries a pass can write cover at most
+// half of its used upper triangle the pass clears their row segments alone (deterministic mode: converts them alone)
+struct HddClearState {
+  std::vector<HddSeg> segs; int64_t entries = 0;
+  DevBuf<HddPiece> pieces; int n_pieces = 0;      // the segments cut into pieces of at most kHddPieceMax doubles
+  bool selective = false;                         // false: small problems, one fill of the whole (hdd_clear_list_host)
+  bool force_full = false;                        // cba_debug_set_hdd_full_clear
+};
 #pragma GCC visibility pop
 
 struct cba_problem {
@@ -110,9 +119,11 @@ struct cba_problem {
   Event ev_aux0, ev_aux1, ev_aux2, ev_clear;
   // control point -> rank in the engine's tiled order of the grid unknowns, per camera (see build_grid_order)
   DevBuf<int> gperm[kMaxCameras];
+  std::vector<int> gperm_host[kMaxCameras];
   std::vector<int> dense_perm_host;   // reference dense column -> engine dense column (identity outside the grids)
   DevBuf<double> red_partials, red8;
   NormalSystem sys;       // the accumulated normal equations (both elimination orders read them)
+  HddClearState hddc;
   double* P = nullptr; DevBuf<double> P_own;   // reduce buffer of the multi-rank paths: the caller's cba_config.reduce_buffer, or P_own
   DevBuf<double> P2;                           // receive buffer of the distributed solve
   int64_t P_cap = 0;                           // doubles of the reduce buffer P
@@ -163,6 +174,11 @@ int check_config(const cba_config* config);
 int choose_elimination_order(cba_problem* p, const cba_config* config);
 int alloc_pass_buffers(cba_problem* p);
 int alloc_system(cba_problem* p);
+// the host half of alloc_pass_buffers' grid order (gperm_host, dense_perm_host) and the list of H_dd's writable segments from it and
+// the elimination order; neither touches the device (cba_debug_hdd_clear_list_query)
+void grid_order_host(cba_problem* p);
+void hdd_clear_list_host(cba_problem* p);
+int upload_hdd_clear_list(cba_problem* p);
 int alloc_reduce_buffer(cba_problem* p, const cba_config* config);
 int alloc_ldlt_workspace(cba_problem* p);
 void order_imagesets(cba_problem* p, int64_t n, const float* xy, const int32_t* point_index, const int32_t* image_index,

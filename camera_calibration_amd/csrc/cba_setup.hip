@@ -131,11 +131,11 @@ static int alloc_state(cba_problem* p, DevState& s) {
 // region of the grid; with 2-D tiles that region intersects about half as many 128-column tiles of
 // the Schur product as with 1-D runs of a grid row, and the block-sparse K loop skips the rest.
 // The order is internal: cba_debug_dump / cba_get_state present everything in the reference order.
-static int build_grid_order(cba_problem* p) {
+void grid_order_host(cba_problem* p) {
   const Layout& L = p->L;
   p->dense_perm_host.resize(L.dense_dof);
   for (int i = 0; i < L.dense_dof; ++i) p->dense_perm_host[i] = i;
-  if (L.localize_only) return CBA_OK;
+  if (L.localize_only) return;
   for (int c = 0; c < L.n_cameras; ++c) {
     const int gw = p->cams[c].grid_w, gh = p->cams[c].grid_h;
     const int per = unknowns_per_point(p->cams[c].model_type);
@@ -148,11 +148,47 @@ static int build_grid_order(cba_problem* p) {
       for (int tx = 0; tx < gw; tx += tile)
         for (int y = ty; y < std::min(gh, ty + tile); ++y)
           for (int x = tx; x < std::min(gw, tx + tile); ++x) perm[x + (size_t)y * gw] = rank++;
-    CBA_TRY(p->gperm[c].assign(perm));
     for (size_t g = 0; g < perm.size(); ++g)
       for (int d = 0; d < per; ++d)
         p->dense_perm_host[L.intr_offset[c] + per * g + d] = L.intr_offset[c] + per * perm[g] + d;
+    p->gperm_host[c] = std::move(perm);
   }
+}
+static int build_grid_order(cba_problem* p) {
+  grid_order_host(p);
+  if (p->L.localize_only) return CBA_OK;
+  for (int c = 0; c < p->L.n_cameras; ++c) CBA_TRY(p->gperm[c].assign(p->gperm_host[c]));
+  return CBA_OK;
+}
+
+// The row segments of H_dd a Jacobian pass can write, for this problem's layout, grid order and elimination order
+void hdd_clear_list_host(cba_problem* p) {
+  const Layout& L = p->L;
+  HddWriteSet w;
+  w.cams = p->cams.data(); w.n_cameras = L.n_cameras; w.n_images = L.n_images; w.n_points = L.n_points;
+  w.eliminate_points = L.eliminate_points; w.localize_only = L.localize_only;
+  for (int c = 0; c < L.n_cameras; ++c) w.gperm[c] = p->gperm_host[c].empty() ? nullptr : p->gperm_host[c].data();
+  w.point_rows_in_strips = p->gridfirst && !p->gf_sharded;      // GfStrips (alloc_gridfirst_system)
+  std::vector<int> col;
+  if (p->gf_sharded) {          // band position -> engine dense column, as setup_gf_sharding hands it to the unpack kernel
+    col.resize(p->sh.shared.ref_col.size());
+    for (size_t k = 0; k < col.size(); ++k) col[k] = p->dense_perm_host[p->sh.shared.ref_col[k]];
+    w.shared = &p->sh.shared; w.shared_col = col.data();
+  }
+  p->hddc.entries = hdd_write_segments(w, &p->hddc.segs);
+  // small problems, where the list covers more than half of the upper triangle the dense unknowns span, keep the one fill
+  p->hddc.selective = 4 * p->hddc.entries <= (int64_t)L.dense_dof * (L.dense_dof + 1);
+}
+int upload_hdd_clear_list(cba_problem* p) {
+  const int64_t ld = p->sys.n_pad;
+  std::vector<HddPiece> pieces;
+  for (const HddSeg& s : p->hddc.segs) {
+    if (s.row < 0 || s.col < s.row || s.len <= 0 || s.col + s.len > p->L.dense_dof) { set_error("cba_create: bad segment of H_dd"); return CBA_ERR_STATE; }
+    for (int c = 0; c < s.len; c += kHddPieceMax) pieces.push_back(HddPiece{s.row * ld + s.col + c, std::min(kHddPieceMax, s.len - c), 0});
+  }
+  if (pieces.size() > 0x7fffff00u) p->hddc.selective = false;
+  p->hddc.n_pieces = p->hddc.selective ? (int)pieces.size() : 0;
+  if (p->hddc.selective) CBA_TRY(p->hddc.pieces.assign(pieces));
   return CBA_OK;
 }
 
@@ -298,7 +334,7 @@ int alloc_system(cba_problem* p) {
   CBA_TRY(p->sys.Dblk.alloc(nb * bs * bs));
   CBA_TRY(p->sys.bblk.alloc(nb * bs));
   CBA_TRY(p->sys.B.alloc((size_t)p->sys.Kpad * p->sys.n_pad));
-  CBA_TRY(p->sys.Hdd.alloc((size_t)p->sys.n_pad * p->sys.n_pad));
+  CBA_TRY(p->sys.Hdd.alloc_zero((size_t)p->sys.n_pad * p->sys.n_pad));      // zero for ever outside the pass's write set (hdd_clear_list.h)
   CBA_TRY(p->sys.bd.alloc((size_t)p->sys.n_pad));
   CBA_TRY(p->gridfirst ? alloc_gridfirst_system(p) : alloc_posefirst_system(p));
   CBA_TRY(p->x.alloc_zero((size_t)L.block_dof + p->sys.n_pad));

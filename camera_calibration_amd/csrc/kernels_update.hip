@@ -2,6 +2,9 @@
 //
 //  k_reduce_costs    cost sums and CostIsSmallerThan                           (lm_optimizer.h:993-1011)
 //  k_update_*        JointOptimizationState::operator-=                        (joint_optimization.cc:172-214)
+//  k_hdd_segments    clear / fixed-point conversion of the entries of H_dd a Jacobian pass writes (hdd_clear_list.h)
+#include <algorithm>
+
 #include "block_device.hip.h"
 #include "obs_device.hip.h"
 
@@ -124,6 +127,44 @@ int launch_apply_update(const Layout& L, const std::vector<cba_camera>& cams, co
 int launch_update_direction_grid(const double* in, const double* x, int G, double* out, hipStream_t s) {
   if (G == 0) return CBA_OK;
   hipLaunchKernelGGL(k_update_grid, dim3((G + 255) / 256), dim3(256), 0, s, in, x, G, 2, 1, (const int*)nullptr, out);
+  CBA_HIP(hipGetLastError());
+  return CBA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The entries of H_dd a Jacobian pass can write (hdd_clear_list.h), as pieces of at most kHddPieceMax doubles of one row: cleared
+// before the accumulation (CONVERT = false), or turned from the fixed-point sums of the deterministic mode into doubles behind it
+// (CONVERT = true: k_det_convert on the pieces).  Sixteen lanes per piece, sixteen pieces per workgroup and trip; a piece starts
+// at any double, so its odd first and last entries move as 8 bytes and everything between as 16-byte pairs.
+// ------------------------------------------------------------------------------------------------
+template <bool CONVERT>
+__global__ void __launch_bounds__(256) k_hdd_segments(double* __restrict__ H, const HddPiece* __restrict__ pieces, int n_pieces,
+                                                      const double* __restrict__ det_scale) {
+  const double inv = CONVERT ? 1.0 / *det_scale : 0.0;       // power of two: exact
+  auto put = [&](double* q) { *q = CONVERT ? (double)(*reinterpret_cast<const long long*>(q)) * inv : 0.0; };
+  const int sub = threadIdx.x & 15;
+  for (int i = blockIdx.x * 16 + (threadIdx.x >> 4); i < n_pieces; i += gridDim.x * 16) {
+    const HddPiece pc = pieces[i];
+    double* q = H + pc.off;
+    const int head = (int)(pc.off & 1), pairs = (pc.len - head) >> 1;
+    if (head && sub == 0) put(q);
+    if (sub == 15 && ((pc.len - head) & 1)) put(q + pc.len - 1);
+    double2* q2 = reinterpret_cast<double2*>(q + head);
+    for (int j = sub; j < pairs; j += 16) {
+      if (CONVERT) {
+        const longlong2 v = *reinterpret_cast<const longlong2*>(q2 + j);
+        q2[j] = make_double2((double)v.x * inv, (double)v.y * inv);
+      } else {
+        q2[j] = make_double2(0.0, 0.0);
+      }
+    }
+  }
+}
+int launch_hdd_segments(double* H, const HddPiece* pieces, int n_pieces, const double* det_scale, hipStream_t s) {
+  if (n_pieces <= 0) return CBA_OK;
+  const unsigned blocks = (unsigned)std::min((n_pieces + 15) / 16, 4096);
+  if (det_scale) hipLaunchKernelGGL(k_hdd_segments<true>, dim3(blocks), dim3(256), 0, s, H, pieces, n_pieces, det_scale);
+  else hipLaunchKernelGGL(k_hdd_segments<false>, dim3(blocks), dim3(256), 0, s, H, pieces, n_pieces, det_scale);
   CBA_HIP(hipGetLastError());
   return CBA_OK;
 }

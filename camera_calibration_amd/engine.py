@@ -255,6 +255,9 @@ DIAGNOSTICS_PROTOTYPES = {
     "cba_debug_straggler_stats": (_I, [_VP, _I64P]),
     "cba_debug_gridfirst_tile_list_query": (_I64, [_I32, _I32, _I32, C.POINTER(C.c_uint64), _I32, _I32, _I32P, _I64]),
     "cba_debug_gridfirst_tile_list": (_I64, [_VP, _I32P, _I64, _I32P]),
+    "cba_debug_hdd_clear_list_query": (_I64, [_CFG, _I32P, _I64, _I64P]),
+    "cba_debug_hdd_clear_list": (_I64, [_VP, _I32P, _I64, _I64P]),
+    "cba_debug_set_hdd_full_clear": (_I, [_VP, _I32]),
 }
 STEREO_PROTOTYPES = {
     "cba_stereo_create": (_I, [_I32, _I32, _I32, _I32, _F32P, C.c_float, C.c_float, C.c_float, C.c_float, _I32, _I32, _F32P, _F32P, _I32,
@@ -319,7 +322,11 @@ def load() -> C.CDLL:
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **UNDISTORT_PROTOTYPES, **STEREO_PROTOTYPES, **STEREO_POST_PROTOTYPES,
                                       **DIAGNOSTICS_PROTOTYPES}.items():
-        fn = getattr(L, name)
+        fn = getattr(L, name, None)
+        if fn is None and name in DIAGNOSTICS_PROTOTYPES and os.environ.get("CBA_HIP_LIB"):
+            continue      # an older build under CBA_HIP_LIB may lack a diagnostic: calling it raises AttributeError
+        if fn is None:
+            raise AttributeError(f"{LIB_PATH} does not export {name}")
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
@@ -378,6 +385,33 @@ def gridfirst_tile_list_query(mode: int, masks: np.ndarray, n_slabs: int, allow_
                                                         out.ctypes.data_as(_I32P), n))
         assert got == n
     return out
+
+
+HDD_CLEAR_INFO = ("n_pad", "dense_dof", "entries", "selective")
+
+
+def _hdd_clear_list(call, what: str):
+    info = (C.c_int64 * 4)()
+    n = int(call(None, 0, info))
+    if n < 0:
+        _check(n, what)
+    out = np.zeros((n, 3), dtype=np.int32)
+    if n:
+        assert int(call(out.ctypes.data_as(_I32P), n, info)) == n
+    return out, {k: int(v) for k, v in zip(HDD_CLEAR_INFO, info)}
+
+
+def hdd_clear_list_query(problem: Problem, elimination: int = 0, grid_strips: int = 0):
+    """cba_debug_hdd_clear_list_query: (segments (n, 3): row, first column, length; info) -- the row segments of H_dd that a Jacobian
+    pass of the problem an Engine would create can write (host only, no device).  info: n_pad (row stride of H_dd), dense_dof,
+    entries (covered by the list), selective (1 = the pass clears the list, 0 = the whole of H_dd)."""
+    L = load()
+    cams = (CbaCamera * problem.n_cameras)(*[_cam_struct(c) for c in problem.cameras])
+    cfg = CbaConfig(problem.n_cameras, cams, problem.n_images, problem.n_points, problem.fd_delta,
+                    int(problem.localize_only), int(problem.eliminate_points), 0, ALLREDUCE_FN(0), None, 0, None, 0, 0,
+                    0, 0, 1, COLLECTIVE_FN(0), None, CbaSolverOptions(0, 0, int(elimination), int(grid_strips), 0))
+    return _hdd_clear_list(lambda seg, cap, info: L.cba_debug_hdd_clear_list_query(C.byref(cfg), seg, cap, info),
+                           "cba_debug_hdd_clear_list_query")
 
 
 def prepare(device: int = 0) -> None:
@@ -583,6 +617,15 @@ class Engine:
         if n:
             assert int(self.L.cba_debug_gridfirst_tile_list(self._h, out.ctypes.data_as(_I32P), n, info)) == n
         return out, dict(valid=int(info[0]), age=int(info[1]), dirty=int(info[2]), n_slabs=int(info[3]))
+
+    def hdd_clear_list(self):
+        """cba_debug_hdd_clear_list: (segments (n, 3), info) of this problem, as hdd_clear_list_query; info["selective"] is 0 as well
+        while set_hdd_full_clear(True) holds."""
+        return _hdd_clear_list(lambda seg, cap, info: self.L.cba_debug_hdd_clear_list(self._h, seg, cap, info), "cba_debug_hdd_clear_list")
+
+    def set_hdd_full_clear(self, on: bool) -> None:
+        """cba_debug_set_hdd_full_clear: every later Jacobian pass clears the whole of H_dd (A/B runs and tests); same results."""
+        _check(self.L.cba_debug_set_hdd_full_clear(self._h, int(bool(on))), "cba_debug_set_hdd_full_clear")
 
     def debug_accumulate(self) -> float:
         cost = C.c_double(0)

@@ -37,6 +37,24 @@ int64_t cba_debug_gridfirst_tile_list_query(int32_t mode, int32_t nt, int32_t wo
                                             int32_t allow_parts, int32_t* entries, int64_t capacity_entries);
 int64_t cba_debug_gridfirst_tile_list(cba_problem* p, int32_t* entries, int64_t capacity_entries, int32_t info[4]);
 
+/* The clear list of H_dd, the dense part of the normal equations (n_pad x n_pad doubles, upper triangle, row-major, the engine's order
+ * of the unknowns): the row segments (row, first column, length) that the accumulation kernels of a Jacobian pass (and the unpack
+ * kernel of image sharding) can write for this problem.  H_dd is allocated zeroed; a pass clears these segments alone, every other
+ * entry stays +0 for the life of the problem.  Where the list would cover more than half of the upper triangle that the dense
+ * unknowns span (small problems) the pass clears all of H_dd with one fill, as it always did.
+ *
+ * Both functions return the number of segments, or an error code (< 0); `segments` (three ints each, ascending (row, column),
+ * disjoint, adjacent ones merged) is written if capacity_segments is large enough; info = {n_pad (the row stride), dense unknowns,
+ * entries the list covers, 1 = the pass clears the list / 0 = the pass clears the whole}.  cba_debug_hdd_clear_list_query builds the
+ * list of the problem cba_create would build from `config` on the host and touches no device (like cba_gridfirst_plan_query);
+ * cba_debug_hdd_clear_list reads the list of a problem.
+ *
+ * cba_debug_set_hdd_full_clear(p, 1) makes every later pass of `p` clear (deterministic mode: convert) the whole of H_dd as if the
+ * list covered too much, 0 returns to the problem's own choice: A/B measurements and tests.  The results are the same bit for bit. */
+int64_t cba_debug_hdd_clear_list_query(const cba_config* config, int32_t* segments, int64_t capacity_segments, int64_t info[4]);
+int64_t cba_debug_hdd_clear_list(cba_problem* p, int32_t* segments, int64_t capacity_segments, int64_t info[4]);
+int cba_debug_set_hdd_full_clear(cba_problem* p, int32_t on);
+
 #ifdef __cplusplus
 }
 #endif

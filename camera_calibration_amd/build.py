@@ -10,14 +10,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcalib_ba_hip.so")
 SOURCES = ["cba_api.hip", "cba_setup.hip", "cba_passes.hip", "cba_solve.hip", "cba_posefirst.hip", "cba_gridfirst.hip", "cba_oneshot.hip", "cba_report.hip", "cba_compare.hip", "cba_undistort.hip", "cba_features.hip",
-           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "hdd_clear_list.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "kernels_undistort.hip", "kernels_features.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip", "cba_stereo.hip", "kernels_stereo.hip", "kernels_stereo_post.hip"]
+           "kernels_project.hip", "kernels_fd.hip", "kernels_obs.hip", "kernels_update.hip", "kernels_linalg.hip", "kernels_ldlt.hip", "kernels_ldlt_dist.hip", "kernels_backsolve.hip", "kernels_fit.hip", "gridfirst_plan.hip", "hdd_clear_list.hip", "kernels_gridfirst.hip", "kernels_report.hip", "kernels_compare.hip", "kernels_undistort.hip", "kernels_features.hip", "cba_localize.hip", "kernels_localize.hip", "cba_localize_images.hip", "kernels_localize_images.hip", "cba_parametric.hip", "kernels_parametric.hip", "cba_stereo.hip", "kernels_stereo.hip", "kernels_stereo_post.hip",
+           "cba_point_cloud.hip", "kernels_point_cloud.hip"]
 HEADERS = ["cba_internal.h", "hip_buf.h", "cba_problem.h", "cba_model.h", "model.hip.h", "obs_device.hip.h", "block_device.hip.h", "localize_device.hip.h", "gridfirst_plan.h", "hdd_clear_list.h", "linalg_internal.h", "ldlt_dataflow.hip.h", os.path.join("..", "..", "include", "cba.h")]
 # public headers besides cba.h that a unit includes (cba_undistort.h: cba_undistort.hip; cba_features.h: cba_internal.h;
 # cba_stereo.h: cba_stereo.hip, kernels_stereo.hip; cba_stereo_post.h: cba_stereo.hip, kernels_stereo_post.hip;
-# cba_diagnostics.h: cba_api.hip, cba_gridfirst.hip)
+# cba_diagnostics.h: cba_api.hip, cba_gridfirst.hip; cba_point_cloud.h: cba_point_cloud.hip, kernels_point_cloud.hip)
 PUBLIC_HEADERS = [os.path.join("..", "..", "include", "cba_undistort.h"), os.path.join("..", "..", "include", "cba_features.h"),
                   os.path.join("..", "..", "include", "cba_stereo.h"), os.path.join("..", "..", "include", "cba_stereo_post.h"),
-                  os.path.join("..", "..", "include", "cba_diagnostics.h")]
+                  os.path.join("..", "..", "include", "cba_diagnostics.h"), os.path.join("..", "..", "include", "cba_point_cloud.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]  # keep MFMA accumulators in VGPRs: no AGPR<->VGPR copies in the K loop
 
@@ -150,6 +151,8 @@ NO_SCRATCH = {
     # the median keeps its nine (inv_depth, cost) pairs, the hole filling its eight neighbours, in registers: unrolled indices only
     "kernels_stereo_post.o": ("k_stereo_post_median", "k_stereo_post_bilateral", "k_stereo_post_fill", "k_stereo_post_cc_init",
                               "k_stereo_post_cc_union", "k_stereo_post_cc_count", "k_stereo_post_cc_clear"),
+    # streaming kernels with a handful of values per lane (the second moment pass: 10 fp64 accumulators, unrolled indices only)
+    "kernels_point_cloud.o": ("k_cloud_count", "k_cloud_gather", "k_cloud_moments", "k_cloud_align"),
 }
 
 

@@ -390,6 +390,34 @@ static_assert(std::is_trivially_copyable_v<StereoPostArgs>);
 // four launches, or the clearing one alone when every component is kept)
 int launch_stereo_post(const StereoPostArgs& a, int stage, hipStream_t s);
 
+// ---- kernels_point_cloud.hip (comparison of two stereo point clouds, include/cba_point_cloud.h) ----
+// The inner region of the two maps and what the three launches of the compaction read and write.  n_blocks workgroups of
+// CBA_CLOUD_PIXELS_PER_BLOCK inner pixels; count: 3 x n_blocks (target, source, common), start: 3 x (n_blocks + 1), row k the
+// exclusive scan of row k of count with its total last.
+struct CloudArgs {
+  int W, H, r, n_blocks;
+  int64_t n_inner;
+  const float* map_t; const float* map_s;                     // validity: value != 0
+  int* count; const int* start;
+  // the gather: from_depth != 0 computes the points from the maps (inverse depths) and the lookups, grey from the images at the pixel;
+  // else cloud_* / cloud_grey_* are indexed with the ranks
+  int from_depth;
+  const float* cloud_t; const float* cloud_s; const uint8_t* cloud_grey_t; const uint8_t* cloud_grey_s;   // grey: may be null
+  const float2* unprojection_t; const float2* unprojection_s;
+  int* pixel; float* xyz_t; float* xyz_s; uint8_t* grey_t; uint8_t* grey_s;                               // per common pixel
+};
+static_assert(std::is_trivially_copyable_v<CloudArgs>);
+int launch_cloud_count(const CloudArgs& a, hipStream_t s);       // launch (i)
+int launch_cloud_gather(const CloudArgs& a, hipStream_t s);      // launch (iii)
+constexpr int kCloudSumBlocks = 256;                             // the fixed number of workgroups of the moment and distance sums
+constexpr int kCloudSums = 16;                                   // [0..2] sum x, [3..5] sum y, [6..14] sum dy dx^T, [15] sum |dx|^2
+// partials: kCloudSumBlocks * 10 doubles.  Two passes: sums[0..5], then sums[6..15] about the means sums[0..5] / n
+int launch_cloud_moments(int64_t n, const float* xyz_s, const float* xyz_t, double* partials, double* sums, hipStream_t s);
+// aligned / distance_image[pixel[i]] / max_bits (cleared here) / stats[3] = n, sum d, sum d^2; At: A (9) and t (3)
+struct CloudAlign { float A[9], t[3]; };
+int launch_cloud_align(int64_t n, const CloudAlign& At, const float* xyz_s, const float* xyz_t, const int* pixel, float* aligned,
+                       float* distance_image, int* max_bits, double* partials, double* stats, hipStream_t s);
+
 // ---- kernels_features.hip (refinement of star-pattern feature positions, include/cba_features.h) ----
 // n features, one workgroup each.  pattern_tr_pixel: the inverses of pixel_tr_pattern (9 n floats each, row-major); rendered:
 // n * (n_samples / 8) floats of working memory; matched / out_positions 2 n, final_cost / status n.

@@ -289,6 +289,17 @@ STEREO_POST_PROTOTYPES = {
 STEREO_POST_MEDIAN, STEREO_POST_BILATERAL, STEREO_POST_FILL_HOLES, STEREO_POST_COMPONENTS = 0, 1, 2, 3
 STEREO_POST_MAX_RADIUS = 32
 
+# The same table for include/cba_point_cloud.h (tests/test_point_cloud_cases.py checks it against that header)
+POINT_CLOUD_PROTOTYPES = {
+    "cba_cloud_pair_create": (_I, [_I32, _I32, _I32, _F32P, _F32P, _F32P, _I64, _U8, _F32P, _I64, _U8, _I32, C.POINTER(_VP)]),
+    "cba_cloud_pair_create_from_depth": (_I, [_I32, _I32, _I32, _F32P, _F32P, _U8, _F32P, _F32P, _U8, _I32, C.POINTER(_VP)]),
+    "cba_cloud_pair_destroy": (None, [_VP]),
+    "cba_cloud_pair_counts": (_I, [_VP, _I64P]),
+    "cba_cloud_pair_moments": (_I, [_VP, _D]),
+    "cba_cloud_pair_align": (_I, [_VP, _F32P, _F32P, _F32P, _D, _F32P]),
+    "cba_cloud_pair_get_clouds": (_I, [_VP, _F32P, _U8, _F32P, _U8]),
+}
+
 DUMP_COST_VECTOR, DUMP_PIXELS, DUMP_FLAGS, DUMP_JACOBIANS = 1, 2, 3, 4
 DUMP_BLOCK_DIAG_H, DUMP_BLOCK_DIAG_B, DUMP_OFF_DIAG_H, DUMP_DENSE_H, DUMP_DENSE_B, DUMP_X = 5, 6, 7, 8, 9, 10
 DUMP_TEST_COST_VECTOR = 11
@@ -321,7 +332,7 @@ def load() -> C.CDLL:
                           "the engine has no CPU fallback")
     L = C.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **UNDISTORT_PROTOTYPES, **STEREO_PROTOTYPES, **STEREO_POST_PROTOTYPES,
-                                      **DIAGNOSTICS_PROTOTYPES}.items():
+                                      **POINT_CLOUD_PROTOTYPES, **DIAGNOSTICS_PROTOTYPES}.items():
         fn = getattr(L, name, None)
         if fn is None and name in DIAGNOSTICS_PROTOTYPES and os.environ.get("CBA_HIP_LIB"):
             continue      # an older build under CBA_HIP_LIB may lack a diagnostic: calling it raises AttributeError
@@ -1138,6 +1149,96 @@ class StereoHandle:
         _check(self.L.cba_stereo_finish(self._h, C.byref(options), C.byref(post_options),
                                         other.ctypes.data_as(_F32P) if other is not None else None, out.ctypes.data_as(_F32P)), "cba_stereo_finish")
         return out
+
+
+def _u8_or_none(a):
+    return None if a is None else a.ctypes.data_as(_U8)
+
+
+class CloudPair:
+    """cba_cloud_pair (include/cba_point_cloud.h): the common pixels of two depth maps of one image and their two clouds on the
+    device.  Build one with ``from_clouds`` (the files' path) or ``from_depth`` (two in-memory stereo results)."""
+
+    def __init__(self, handle, width: int, height: int):
+        self.L = load()
+        self._h, self.width, self.height = handle, int(width), int(height)
+
+    @classmethod
+    def from_clouds(cls, depth_target, depth_source, context_radius: int, xyz_target, grey_target, xyz_source, grey_source, device: int = 0):
+        """Depth maps (H, W) float32, positions (n, 3) float32, grey (n,) uint8 or None."""
+        L = load()
+        dt, ds = np.ascontiguousarray(depth_target, dtype=np.float32), np.ascontiguousarray(depth_source, dtype=np.float32)
+        if dt.ndim != 2 or ds.shape != dt.shape:
+            raise ValueError("CloudPair: two depth maps (H, W) of the same size")
+        xt, xs = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3) for a in (xyz_target, xyz_source))
+        gt, gs = (None if g is None else np.ascontiguousarray(g, dtype=np.uint8).reshape(-1) for g in (grey_target, grey_source))
+        if (gt is not None and gt.size != xt.shape[0]) or (gs is not None and gs.size != xs.shape[0]):
+            raise ValueError("CloudPair: one grey value per point")
+        h = C.c_void_p()
+        _check(L.cba_cloud_pair_create(dt.shape[1], dt.shape[0], int(context_radius), dt.ctypes.data_as(_F32P), ds.ctypes.data_as(_F32P),
+                                       xt.ctypes.data_as(_F32P), xt.shape[0], _u8_or_none(gt), xs.ctypes.data_as(_F32P), xs.shape[0],
+                                       _u8_or_none(gs), int(device), C.byref(h)), "cba_cloud_pair_create")
+        return cls(h, dt.shape[1], dt.shape[0])
+
+    @classmethod
+    def from_depth(cls, inv_depth_target, unprojection_target, image_target, inv_depth_source, unprojection_source, image_source,
+                   context_radius: int, device: int = 0):
+        """Inverse-depth maps (H, W) float32, un-projection lookups (H, W, 2) float32, grey images (H, W) uint8 or None."""
+        L = load()
+        mt, ms = np.ascontiguousarray(inv_depth_target, dtype=np.float32), np.ascontiguousarray(inv_depth_source, dtype=np.float32)
+        ut, us = np.ascontiguousarray(unprojection_target, dtype=np.float32), np.ascontiguousarray(unprojection_source, dtype=np.float32)
+        if mt.ndim != 2 or ms.shape != mt.shape or ut.shape != mt.shape + (2,) or us.shape != ut.shape:
+            raise ValueError("CloudPair: maps (H, W) and lookups (H, W, 2) of the same size")
+        it, is_ = (None if g is None else np.ascontiguousarray(g, dtype=np.uint8) for g in (image_target, image_source))
+        if (it is not None and it.shape != mt.shape) or (is_ is not None and is_.shape != mt.shape):
+            raise ValueError("CloudPair: grey images of the maps' size")
+        h = C.c_void_p()
+        _check(L.cba_cloud_pair_create_from_depth(mt.shape[1], mt.shape[0], int(context_radius), mt.ctypes.data_as(_F32P),
+                                                  ut.ctypes.data_as(_F32P), _u8_or_none(it), ms.ctypes.data_as(_F32P),
+                                                  us.ctypes.data_as(_F32P), _u8_or_none(is_), int(device), C.byref(h)),
+               "cba_cloud_pair_create_from_depth")
+        return cls(h, mt.shape[1], mt.shape[0])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.cba_cloud_pair_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def counts(self):
+        """(valid inner pixels of the target, of the source, common pixels)"""
+        out = np.zeros(3, dtype=np.int64)
+        _check(self.L.cba_cloud_pair_counts(self._h, out.ctypes.data_as(_I64P)), "cba_cloud_pair_counts")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def moments(self) -> np.ndarray:
+        """17 doubles: n, mean of the source, mean of the target, covariance (target x source, row-major), variance of the source."""
+        out = np.zeros(17)
+        _check(self.L.cba_cloud_pair_moments(self._h, _dp(out)), "cba_cloud_pair_moments")
+        return out
+
+    def align(self, A, t):
+        """(distance image (H, W) float32, stats (n, sum d, sum d^2), max distance as a float32 scalar)"""
+        A32, t32 = np.ascontiguousarray(A, dtype=np.float32).reshape(9), np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        image = np.zeros((self.height, self.width), dtype=np.float32)
+        stats, largest = np.zeros(3), np.zeros(1, dtype=np.float32)
+        _check(self.L.cba_cloud_pair_align(self._h, A32.ctypes.data_as(_F32P), t32.ctypes.data_as(_F32P), image.ctypes.data_as(_F32P),
+                                           _dp(stats), largest.ctypes.data_as(_F32P)), "cba_cloud_pair_align")
+        return image, stats, largest[0]
+
+    def clouds(self):
+        """(target positions (n, 3), target grey (n,), source positions after the last align (n, 3), source grey (n,))"""
+        n = self.counts()[2]
+        xt, xs = np.zeros((n, 3), dtype=np.float32), np.zeros((n, 3), dtype=np.float32)
+        gt, gs = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        _check(self.L.cba_cloud_pair_get_clouds(self._h, xt.ctypes.data_as(_F32P), gt.ctypes.data_as(_U8), xs.ctypes.data_as(_F32P),
+                                                gs.ctypes.data_as(_U8)), "cba_cloud_pair_get_clouds")
+        return xt, gt, xs, gs
 
 
 def render_nearest_feature_image(width: int, height: int, site_xy_quarter_px: np.ndarray, site_rgb: np.ndarray, device: int = 0,
